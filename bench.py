@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — nodes/sec of one full-batch GraphTextLM forward+backward (BASELINE.json metric) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]        # N>1: launched by torch.distributed.run
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]   # N>1: launched by torch.distributed.run
 
 Workload (SURVEY.md §8d "S3", BASELINE configs[2], the config the metric is quoted on): synthetic
 Squirrel-size graph (5,201 nodes, 217,073 edges, F_in=2089, 5 classes), hidden_channels=768,
@@ -11,17 +11,20 @@ fp32 accumulation and statistics.  A "step" = soft-mask -> forward -> CE(label_s
 (the optimiser is outside the metric: SURVEY.md §8d).  With N > 1 every rank owns a Squirrel-size
 partition of an N x 5,201-node graph (1-D node partition, halo exchange + RCCL collectives): weak scaling.
 
-Prints ONE JSON line (rank 0).  Extra objects (N = 1):
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the headline ("value" nodes/s,
+"ms_per_step" = wall time of one timed step); nothing else runs.  ``--dump-outputs DIR`` then writes what the last timed
+step computed (see dump_outputs).  ``--full`` adds the extra objects (N = 1):
   "roofline"      the RGCN aggregation kernel in the regime where HBM is the binding roof: a 1.25M-node / 12.5M-edge
                   power-law shard (one GPU's share of the 10M-node S5 config), F = 768 bf16, X = 1.9 GB >> the 256 MiB
                   Infinity Cache; algorithmic bytes (SURVEY section 8d formula) / HIP-event launch time; "traffic" = HBM
                   bytes per launch from the committed rocprofv3 PMC passes (profiles/)
   "attention"     the MFMA-bound kernels: CrossAttention geometry (h=8, d=96, N=20,804) and masked MHA (B=32, h=12, L=512,
                   d=64), padded AND executed flops, HIP-event time, PMC MFMA-busy fraction from profiles/
-  "kernels"       every hand-written kernel of the timed step (HIP events on the launch stream inside the timed region);
+  "kernels"       every hand-written kernel of the step (HIP events on the launch stream, K more steps after the timed ones);
                   the in-step aggregation launches run on a cache-resident X (8-32 MB) and are reported against the
                   L2 / Infinity-Cache gather rates of the guide, not against 8 TB/s
   "fp32"          the same step with fp32 operands (the north_star parity dtype), 3 timed steps
+  "reference_recompute"  the same step with the reference's activation + PLM gradient checkpointing, 3 timed steps
   "power_law_variant"  the same step on a heavy-tailed graph of the same size (R_a = 4 instead of the headline's 1)
   "cpu_baseline"  the CPU oracle timed on this box's host cores on a bounded sample (1 warm-up + median of 3)
 
@@ -493,6 +496,33 @@ def s5_strong(dev, args, world, rank):
                    "peak_mem_GB": round(torch.cuda.max_memory_allocated() / 1e9, 1)}}
 
 
+DUMP_SAMPLE = 32768              # elements kept per gradient tensor (seeded, fixed positions); 269 tensors -> < 35 MB in all
+
+
+def dump_outputs(out_dir, loss, logits, model):
+    """What the last timed step hands its caller, as float32 .npy files: ``loss`` (0-d), ``logits`` [local nodes, C] and one
+    ``grad.<parameter name>.npy`` per parameter that has a gradient: the whole gradient up to DUMP_SAMPLE elements, else
+    DUMP_SAMPLE elements of the flattened gradient at sorted positions drawn from a generator seeded with crc32(name), i.e.
+    the same positions in every run and every build."""
+    import zlib
+
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    files = {"loss": loss.detach().float().reshape(()), "logits": logits.detach().float()}
+    for name, p in model.named_parameters():
+        if p.grad is None:
+            continue
+        g = p.grad.detach().reshape(-1)
+        if g.numel() > DUMP_SAMPLE:
+            gen = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+            idx = torch.randint(0, g.numel(), (DUMP_SAMPLE,), generator=gen).sort().values
+            g = g[idx.to(g.device)]
+        files["grad." + name] = g.float()
+    for name, t in files.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
+    return len(files)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -540,7 +570,13 @@ def main():
     ap.add_argument("--micro-select", default="spmm,attn", help="comma list of micro-benchmark groups: spmm, attn")
     ap.add_argument("--micro-nodes", type=int, default=1_250_000)
     ap.add_argument("--micro-edges", type=int, default=12_500_000)
+    ap.add_argument("--full", action="store_true", help="also the per-kernel, micro-benchmark / roofline, fp32, reference_recompute, "
+                    "power_law_variant and cpu_baseline legs (a plain run times the headline step only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write the last step's loss, logits and "
+                    "(sampled) parameter gradients to DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.dump_outputs and (args.gnn_large or args.micro_only or args.workload == "s5"):
+        raise SystemExit("--dump-outputs writes the GraphTextLM step's outputs: not with --gnn-large, --micro-only or --workload s5")
 
     import gmlm_amd
     from gmlm_amd import ops, tuning
@@ -633,7 +669,7 @@ def main():
         loss.backward()
         if part is not None:
             part.grad_buckets(model).finish()
-        return loss
+        return loss, logits
 
     def fence():
         if distributed:
@@ -642,8 +678,6 @@ def main():
 
     for _ in range(args.warmup):
         step()
-    timer = None if args.no_kernel_timers else ops.KernelTimer()
-    ops.TIMER = timer
     fence()
     prof = None
     if args.host_profile:                                # where a launch-bound step spends its HOST time (not a bench number)
@@ -652,7 +686,7 @@ def main():
         prof.enable()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = step()
+        loss, logits = step()
     fence()
     dt = time.perf_counter() - t0
     if prof is not None:
@@ -663,7 +697,19 @@ def main():
         pstats.Stats(prof, stream=buf).sort_stats("tottime").print_stats(45)
         with open(args.host_profile, "w") as f:
             f.write(f"{args.steps} steps, {dt / args.steps * 1e3:.3f} ms/step under cProfile\n" + buf.getvalue())
-    ops.TIMER = None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, logits, model)
+    del logits
+    timer = None
+    if args.full and not args.no_kernel_timers:
+        # per-kernel figures: K more steps with HIP events around every hand-written launch (the events cost host time, so
+        # they stay out of the timed steps above)
+        timer = ops.KernelTimer()
+        ops.TIMER = timer
+        for _ in range(args.steps):
+            step()
+        fence()
+        ops.TIMER = None
     if distributed:
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
@@ -726,7 +772,7 @@ def main():
                 k["note"] = ("text-encoder attention at <= 128 tokens per sequence: <= 64 flop per byte of q/k/v/o, a fifth of the MFMA/HBM "
                              "ridge (312): HBM-side kernel; frac_mfma_peak is reported for completeness only")
         out["kernels"] = kern
-    if rank == 0 and world == 1 and not args.no_micro and args.workload == "squirrel":
+    if args.full and rank == 0 and world == 1 and not args.no_micro and args.workload == "squirrel":
         del model
         torch.cuda.empty_cache()
         out["micro"] = mi = micro(dev, args)
@@ -766,7 +812,7 @@ def main():
                     "achieved_padded": ml["fwd_TFLOPs"], "frac_padded": ml["fwd_frac_mfma_peak"],
                     "achieved_executed": ml.get("fwd_TFLOPs_executed"), "avg_launch_ms": ml["fwd_ms"],
                     "pmc": _pmc_attn("attn_fwd_pipe_kernel<64, 4", 16 * 12 * 16 * 256)}
-    if rank == 0 and world == 1 and not args.no_fp32_leg and args.dtype == "bf16" and args.workload == "squirrel":
+    if args.full and rank == 0 and world == 1 and not args.no_fp32_leg and args.dtype == "bf16" and args.workload == "squirrel":
         # the same step with fp32 operands (the dtype the 1e-4 parity bar is stated in)
         args32 = argparse.Namespace(**{**vars(args), "dtype": "f32"})
         m32 = build_model(args32, data, dev)
@@ -788,7 +834,7 @@ def main():
                        "note": "same workload, fp32 operands (exact-f32 MFMA attention, fp32 GEMMs)"}
         del m32
         torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and not args.no_fp32_leg and args.dtype == "bf16" and args.workload == "squirrel" and not args.reference_recompute:
+    if args.full and rank == 0 and world == 1 and not args.no_fp32_leg and args.dtype == "bf16" and args.workload == "squirrel" and not args.reference_recompute:
         # the same step the way the reference runs it: every RGCN block and every BertLayer recomputed in backward
         argsr = argparse.Namespace(**{**vars(args), "reference_recompute": True})
         mr = build_model(argsr, data, dev)
@@ -814,7 +860,7 @@ def main():
                                       "note": "same workload with the reference's recomputation (main.py:217-219, 278-314): identical results, forward of every block runs twice"}
         del mr
         torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and not args.no_fp32_leg and args.dtype == "bf16" and args.workload == "squirrel":
+    if args.full and rank == 0 and world == 1 and not args.no_fp32_leg and args.dtype == "bf16" and args.workload == "squirrel":
         # the headline graph's uniform edges put every edge in degree bucket 3 (R_a = 1); real Squirrel is heavy-tailed.  Same
         # sizes with Chung-Lu power-law out-degrees (alpha = 2.2): all four degree buckets occur, the relation-segmented
         # aggregation and the one-GEMM H W_cat path run with R_a = 4
@@ -844,18 +890,19 @@ def main():
                                     "note": "same sizes, Chung-Lu power-law out-degrees: all degree buckets occur (the headline graph has R_a = 1)"}
         del mpl, ei_pl
         torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and data["n"] > 16384:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and data["n"] > 16384:
         # the oracle follows the reference and materialises the [1, 8, N, N] scores of both cross-attentions (main.py:159-160):
         # 918 GB at ogbn-arxiv size - the reference cannot run this workload at all, so there is no CPU leg
         out["cpu_baseline"] = {"value": None, "unit": "nodes/s", "cores": os.cpu_count(), "kind": "port",
                                "sample": f"not run: the dense N x N cross-attention of the reference needs {8 * data['n'] ** 2 * 4 / 1e9:.0f} GB of host memory per module at N = {data['n']}"}
-    elif rank == 0 and world == 1 and not args.no_cpu_baseline:
+    elif args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline(args, data, ids, am)
         except Exception as exc:  # the baseline is a reported number, never a reason to lose the bench line
             out["cpu_baseline"] = {"value": None, "unit": "nodes/s", "cores": os.cpu_count(), "kind": "port", "sample": f"failed: {exc!r}"}
     if rank == 0:
-        out["child_processes_at_exit"] = child_processes()
+        if args.full:
+            out["child_processes_at_exit"] = child_processes()
         print(json.dumps(out))
     if distributed:
         torch.distributed.destroy_process_group()

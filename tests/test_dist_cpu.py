@@ -1,6 +1,7 @@
 """world_size-2 gloo tests (CPU) of the 1-D node partition: plan, halo exchange (+ backward),
 GraphNorm statistic all-reduce, K|V all-gather (+ reduce-scatter backward), gradient bucket all-reduce.
 The oracle is the checker: partitioned aggregation over local+halo rows must equal the global one."""
+import gc
 import os
 import sys
 
@@ -194,6 +195,11 @@ def test_ring_attention_matches_all_gather(world, n):
 
 
 def _bucket_worker(rank, world, port):
+    _bucket_steps(rank, world, port)
+    gc.collect()        # the test's Function class holds the context (and the subgroup) in a cycle: free it before exit
+
+
+def _bucket_steps(rank, world, port):
     sys.path.insert(0, ROOT)
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -265,6 +271,11 @@ def _bucket_worker(rank, world, port):
             if 1 <= step <= 4:                                  # learned set: gradients are views of the flat buckets (no copies)
                 assert all(p.grad.data_ptr() >= f.data_ptr() and p.grad.data_ptr() < f.data_ptr() + f.numel() * 4
                            for i, p in enumerate(gb.params) if gb.expected[i] for f in [gb.flats[gb.bucket_of[i]]])
+        # the reducer's gradient hooks, and the Function class above, hold the reducer's gloo subgroup in reference cycles
+        # (the hooks' through C++, where the collector cannot see them).  A subgroup still alive at interpreter exit has its
+        # worker threads running while the process tears down, which aborts it now and then ("terminate called without an
+        # active exception") after every assertion has passed: unhook here, collect the rest in _bucket_worker
+        gb.remove()
     finally:
         dist.destroy_process_group()
 
