@@ -60,6 +60,8 @@ SIGNATURES = {
     "gmlm_bias_gelu_fwd": (C.c_int, [_p, _p, _i64, _i64, _f32, _u64, _p, _p, _i32, _p]),
     "gmlm_bias_gelu_bwd_workspace_bytes": (_sz, [_i64, _i64, _i32]),
     "gmlm_bias_gelu_bwd": (C.c_int, [_p, _p, _p, _i64, _i64, _f32, _u64, _p, _p, _p, _i32, _p, _sz, _p]),
+    "gmlm_wgrad_workspace_bytes": (_sz, [_i64, _i64, _i64, _i32]),
+    "gmlm_wgrad_bf16": (C.c_int, [_p, _i64, _p, _i64, _i64, _i64, _i64, _i32, _p, _i64, _i32, _p, _sz, _p]),
 }
 
 

@@ -75,12 +75,32 @@ _F32_MM = [True]           # torch.mm(..., out_dtype=float32) likewise
 
 _SLICES_MEASURED = {(2304, 768): 14, (3072, 768): 14, (768, 3072): 14}
 SPLITK_ROW_QUANTUM = 112   # lcm(14, 16): a token count that is a multiple of it leaves no tail rows for either slice count
+# bf16 -> fp32 weight gradients at T >= NATIVE_WGRAD_MIN_T with N, K multiples of 256 and at least NATIVE_WGRAD_MIN_TILES
+# 256 x 256 output tiles run on the split-K kernel of libgmlm_hip.so (wgrad_kernels.hip) instead of the batched hipBLASLt
+# GEMM + ATen slice sum (MI355X, T = 91,712, tools/ubench/wgrad_native.py: 1.2-1.4x on every BERT-base weight).  The
+# BERT-mini weights (1-4 tiles) stay on the library path: alone 1.3x except 256 x 256 (90 vs 50 us), but the chameleon
+# whole-step graph, where they share the chip with the GNN branch, measured 6.41-6.44 vs 6.33 ms.  False = library path (A/B).
+NATIVE_WGRAD = True
+NATIVE_WGRAD_MIN_T = 16384
+NATIVE_WGRAD_MIN_TILES = 9
+
+
+def _native_wgrad_ok(dy2: torch.Tensor, x2: torch.Tensor, keep_fp32: bool) -> bool:
+    t, n = dy2.shape
+    k = x2.shape[1]
+    return (NATIVE_WGRAD and keep_fp32 and dy2.is_cuda and dy2.dtype == torch.bfloat16 and x2.dtype == torch.bfloat16
+            and t >= NATIVE_WGRAD_MIN_T and n % ops.WGRAD_TILE == 0 and k % ops.WGRAD_TILE == 0
+            and (n // ops.WGRAD_TILE) * (k // ops.WGRAD_TILE) >= NATIVE_WGRAD_MIN_TILES
+            and dy2.stride(1) == 1 and x2.stride(1) == 1 and dy2.stride(0) % 8 == 0 and x2.stride(0) % 8 == 0
+            and dy2.data_ptr() % 16 == 0 and x2.data_ptr() % 16 == 0)
 
 
 def _splitk_wgrad(dy2: torch.Tensor, x2: torch.Tensor, keep_fp32: bool = False) -> torch.Tensor:
     """dW [N, K] = dy2^T [N, T] @ x2 [T, K] (returned in fp32 when ``keep_fp32``, else in dy2's dtype).  The reduction dim is the token count (10^4..10^5) while the
     output is only a few 256x256 tiles, so one hipBLASLt call leaves most CUs idle; cutting T into S
     slices (batched GEMM, fp32 partials) and adding them fills the chip (measured 1.5-2.7x on MI355X)."""
+    if _native_wgrad_ok(dy2, x2, keep_fp32):
+        return ops.wgrad_bf16(dy2, x2)
     t, n = dy2.shape
     k = x2.shape[1]
     tiles = ((n + 255) // 256) * ((k + 255) // 256)

@@ -185,6 +185,24 @@ def column_sum(x: torch.Tensor) -> torch.Tensor:
     return out[0]
 
 
+WGRAD_TILE = 256           # N and K granularity of gmlm_wgrad_bf16
+WGRAD_NO_REMAP = 1         # gmlm_wgrad_bf16 flag: plain workgroup order
+
+
+def wgrad_bf16(dy: torch.Tensor, x: torch.Tensor, splits: int = 0, flags: int = 0) -> torch.Tensor:
+    """fp32 dW [N, K] = dy^T [N, T] @ x [T, K] for bf16 ``dy`` [T, N] / ``x`` [T, K] with unit column stride (a column slice
+    of a wider tensor is fine): the split-K weight-gradient kernel, slice partials added in fixed order (deterministic).
+    N and K multiples of WGRAD_TILE, T >= 32.  ``splits`` 0 = the kernel's default plan."""
+    _cuda(dy, x)
+    t, n = dy.shape
+    k = x.shape[1]
+    out = torch.empty(n, k, dtype=torch.float32, device=dy.device)
+    ws = _ws(lib().gmlm_wgrad_workspace_bytes(t, n, k, splits), dy.device)
+    check(lib().gmlm_wgrad_bf16(_ptr(dy), dy.stride(0), _ptr(x), x.stride(0), t, n, k, splits, _ptr(out), k, flags, _ptr(ws),
+                                ws.numel(), _stream()), "gmlm_wgrad_bf16")
+    return out
+
+
 def device_split_plan(rowptr: torch.Tensor, num_items: int, thresh: int = 64):
     """``graph.SplitPlan`` for segments known only on the device (they change every step): capacity-sized arrays filled by ONE
     kernel, no host round trip; unused slots are -1 and skipped by the aggregation kernels (gmlm_split_plan_build)."""

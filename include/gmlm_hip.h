@@ -275,6 +275,20 @@ int gmlm_bias_gelu_bwd(const void* dy, const void* x, const float* bias, int64_t
                        uint64_t seed, const uint64_t* seed_dev, void* dx, float* dbias, int dtype, void* workspace, size_t workspace_bytes,
                        gmlm_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Split-K weight gradient of the dense layers (bf16 operands, fp32 result)
+ * out[n, k] (row stride ld_out) = sum_{t < T} dy[t, n] * x[t, k], dy [T, N] (row stride ld_dy) and x [T, K] (ld_x) bf16.
+ * N and K multiples of 256, T >= 32, row strides multiples of 8 elements (4 for out), pointers 16-byte aligned.
+ * T is cut into `splits` contiguous slices (0 = the default plan: about 256 workgroups); each slice of each 256 x 256
+ * tile goes to a fp32 partial in the workspace, which a second launch adds in slice order: deterministic.
+ * flags: GMLM_WGRAD_NO_REMAP = plain workgroup order (no XCD grouping of the slices).
+ * workspace: gmlm_wgrad_workspace_bytes(T, N, K, splits), no initialisation needed.
+ * ------------------------------------------------------------------------------------------- */
+#define GMLM_WGRAD_NO_REMAP 1
+size_t gmlm_wgrad_workspace_bytes(int64_t t, int64_t n, int64_t k, int splits);
+int gmlm_wgrad_bf16(const void* dy, int64_t ld_dy, const void* x, int64_t ld_x, int64_t t, int64_t n, int64_t k, int splits,
+                    float* out, int64_t ld_out, int flags, void* workspace, size_t workspace_bytes, gmlm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
