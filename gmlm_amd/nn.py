@@ -522,15 +522,15 @@ class _SplitLast(torch.autograd.Function):
 
 
 def attention_any_dim(q, k, v, kv_len, num_heads, scale, dropout_p, training):
-    """K5/K7 with head dims the MFMA tiling does not cover natively zero-padded to 64 / 96 (exact:
+    """K5/K7 with head dims the MFMA tiling does not cover natively zero-padded to 64 / 96 / 128 (exact:
     zero columns change neither the scores nor the real output columns)."""
     b, lq, hd = q.shape
     d = hd // num_heads
-    if d in (64, 96):
+    if d in (64, 96, 128):
         return ops.attention(q, k, v, kv_len, num_heads, scale, dropout_p, training)
-    if d > 96:
-        raise NotImplementedError(f"attention head dim {d} > 96 is not supported by the gfx950 kernels")
-    dp = 64 if d < 64 else 96
+    if d > 128:
+        raise NotImplementedError(f"attention head dim {d} > 128 is not supported by the gfx950 kernels")
+    dp = 64 if d < 64 else (96 if d < 96 else 128)
 
     def pad(t):
         return F.pad(t.reshape(t.shape[0], t.shape[1], num_heads, d), (0, dp - d)).reshape(t.shape[0], t.shape[1], num_heads * dp)

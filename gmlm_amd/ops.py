@@ -410,6 +410,40 @@ def _short_path(dtype, d: int, rows: int, pairs: int) -> bool:
     return dtype == torch.bfloat16 and d == 64 and rows <= 128 and pairs >= 512
 
 
+def _attention_d128_fwd(ctx, q, k, v, kv_len, h, scale, p, seed, qs, ks, vs):
+    """Head dim 128 (gmlm_attention_d128_fwd): q [b, lq, h*128], k / v [b, lk, h*128].  Saves what the backward needs on
+    ``ctx`` and returns the dense output [b, lq, h*128]."""
+    b, lq, _ = q.shape
+    lk = k.shape[1]
+    out = torch.empty(b, lq, h * 128, dtype=q.dtype, device=q.device)
+    lse = torch.empty(b, h, lq, dtype=torch.float32, device=q.device)
+    # bf16: keep the rounding residual of the output for the backward's delta (gmlm_hip.h, out_lo)
+    out_lo = torch.empty_like(out) if q.dtype == torch.bfloat16 and any(t.requires_grad for t in (q, k, v)) else None
+    with _span("attn_fwd_d128", flops=4.0 * b * h * lq * lk * 128):
+        sd = ctx.sd = _sd()
+        check(lib().gmlm_attention_d128_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(kv_len), b, h, lq, lk, 128, qs, ks, vs, float(scale),
+                                            float(p), seed, sd, _ptr(out), _ptr(out_lo), _ptr(lse), _dt(q), _stream()),
+              "gmlm_attention_d128_fwd")
+    ctx.save_for_backward(q, k, v, out, lse, kv_len, out_lo)
+    ctx.cfg = (h, float(scale), float(p), seed)
+    return out
+
+
+def _attention_d128_bwd(ctx, q, k, v, out, out_lo, gout, lse, kv_len, h, scale, p, seed):
+    b, lq, hd = q.shape
+    lk = k.shape[1]
+    dq = torch.empty(b, lq, hd, dtype=q.dtype, device=q.device)
+    dk = torch.empty(b, lk, hd, dtype=q.dtype, device=q.device)
+    dv = torch.empty(b, lk, hd, dtype=q.dtype, device=q.device)
+    ws = _ws(lib().gmlm_attention_d128_workspace_bytes(b, h, lq), q.device)
+    with _span("attn_bwd_d128", flops=10.0 * b * h * lq * lk * 128):
+        check(lib().gmlm_attention_d128_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(out_lo), _ptr(gout), _ptr(lse), _ptr(kv_len),
+                                            b, h, lq, lk, 128, q.stride(1), k.stride(1), v.stride(1), scale, p, seed, ctx.sd,
+                                            _ptr(dq), _ptr(dk), _ptr(dv), hd, hd, hd, _dt(q), _ptr(ws), ws.numel(), _stream()),
+              "gmlm_attention_d128_bwd")
+    return dq, dk, dv
+
+
 class Attention(torch.autograd.Function):
     """out[b, lq, h*d] = softmax(q k^T * scale + key-padding mask) v with streaming softmax.
 
@@ -424,6 +458,8 @@ class Attention(torch.autograd.Function):
         lk = k.shape[1]
         d = hd // h
         qs, ks, vs = _rows_view(q, h, d), _rows_view(k, h, d), _rows_view(v, h, d)
+        if d == 128:
+            return _attention_d128_fwd(ctx, q, k, v, kv_len, h, scale, p, seed, qs, ks, vs)
         out = torch.empty(b, lq, hd, dtype=q.dtype, device=q.device)
         lse = torch.empty(b, h, lq, dtype=torch.float32, device=q.device)
         # bf16 streaming path: keep the rounding residual of the output for the backward's delta (gmlm_hip.h, out_lo)
@@ -447,6 +483,9 @@ class Attention(torch.autograd.Function):
         lk = k.shape[1]
         d = hd // h
         gout = gout.contiguous().to(q.dtype)
+        if d == 128:
+            dq, dk, dv = _attention_d128_bwd(ctx, q, k, v, out, out_lo, gout, lse, kv_len, h, scale, p, seed)
+            return dq, dk, dv, None, None, None, None, None
         # one fused [.., 3*h*d] gradient buffer when q/k/v came from a fused QKV GEMM, else three
         dq = torch.empty(b, lq, hd, dtype=q.dtype, device=q.device)
         dk = torch.empty(b, lk, hd, dtype=q.dtype, device=q.device)
@@ -571,7 +610,8 @@ class AttentionBlock:
         b, lq, hd = q.shape
         lk, d = k.shape[1], hd // self.h
         if d not in (64, 96):
-            raise NotImplementedError("ring attention needs a native head dim (64 or 96)")
+            raise NotImplementedError(f"ring attention needs a native head dim (64 or 96), got {d}: the head-dim-128 kernels "
+                                      "(gmlm_attention_d128_*) have no ring-block form")
         out = torch.empty(b, lq, hd, dtype=q.dtype, device=q.device)
         lse = torch.empty(b, self.h, lq, dtype=torch.float32, device=q.device)
         with _span("attn_fwd_d%d" % d, flops=4.0 * b * self.h * lq * lk * d):
@@ -631,6 +671,7 @@ def pack_sequence_groups(lens) -> torch.Tensor:
 def attention(q, k, v, kv_len, num_heads, scale, dropout_p=0.0, training=False):
     p = float(dropout_p) if training else 0.0
     return Attention.apply(q, k, v, kv_len, num_heads, scale, p, draw_seed() if p > 0 else 0)
+
 
 
 # ---------------------------------------------------------------------------------------------

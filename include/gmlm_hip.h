@@ -233,6 +233,26 @@ int gmlm_attention_bwd(const void* q, const void* k, const void* v, const void* 
  * QKV projection, sum over rows of [dq | dk | dv], formed inside the backward kernel from tiles it already holds
  * (three matrix-vector products on the MFMA pipe) instead of a separate pass over dqkv. */
 
+/* ---------------------------------------------------------------------------------------------
+ * Attention at head dim 128 (d must be 128; gmlm_attention_fwd / _bwd keep taking 64 and 96 only).
+ * Same layout and semantics as the padded mode of gmlm_attention_fwd / _bwd: q [b, lq, h, 128], k / v [b, lk, h, 128] at
+ * row strides *_stride, out / out_lo / dout [b, lq, h, 128] dense, dq / dk / dv at their row strides, lse / delta
+ * [b, h, lq] fp32, kv_len int32 [b] or NULL, probability dropout with the same replayable hash and row offsets,
+ * out_lo (bf16 only, optional) the residual of the output for an exact delta.  The dK/dV sums run in a fixed order
+ * (no atomics): identical calls give identical bits.  Backward workspace: gmlm_attention_d128_workspace_bytes(b, h, lq).
+ * ------------------------------------------------------------------------------------------- */
+int gmlm_attention_d128_fwd(const void* q, const void* k, const void* v, const int32_t* kv_len, int64_t b, int64_t h,
+                            int64_t lq, int64_t lk, int64_t d, int64_t q_stride, int64_t k_stride, int64_t v_stride,
+                            float scale, float dropout_p, uint64_t seed, const uint64_t* seed_dev, void* out,
+                            void* out_lo, float* lse, int dtype, gmlm_stream_t stream);
+size_t gmlm_attention_d128_workspace_bytes(int64_t b, int64_t h, int64_t lq);
+int gmlm_attention_d128_bwd(const void* q, const void* k, const void* v, const void* out, const void* out_lo,
+                            const void* dout, const float* lse, const int32_t* kv_len, int64_t b, int64_t h,
+                            int64_t lq, int64_t lk, int64_t d, int64_t q_stride, int64_t k_stride, int64_t v_stride,
+                            float scale, float dropout_p, uint64_t seed, const uint64_t* seed_dev, void* dq, void* dk,
+                            void* dv, int64_t dq_stride, int64_t dk_stride, int64_t dv_stride, int dtype,
+                            void* workspace, size_t workspace_bytes, gmlm_stream_t stream);
+
 /* BERT embedding sum (hf:modeling_bert.py:53-108 ahead of the LayerNorm): out[t] = word[tok[t]] + type0 + pos[pos_ids[t]],
  * fp32 tables, stored as `dtype` [rows, p]; replaces two gathers, two adds and a cast.  Its backward is a segment sum of the
  * output gradient by token id / position id (gmlm_segment_sort + gmlm_rgcn_mean_spmm with mean = 0).
