@@ -208,7 +208,14 @@ int gmlm_bias_res_layernorm_bwd(const void* dy, const void* x, const float* bias
  * forward and three backward launches (delta = rowsum(dO * O), dQ, dK/dV).
  * seq_groups (packed mode, optional; int32 [num_groups + 1], device): work item g of the short-sequence kernels is the run
  * of sequences [seq_groups[g], seq_groups[g+1]) - at most 13 sequences and 128 rows in total (the caller guarantees both;
- * rows past 128 would be ignored) - attended block-diagonally.  Ignored by the streaming kernels.
+ * rows past 128 would be ignored) - attended block-diagonally.  Ignored by the streaming kernels.  With dropout, a work
+ * item draws ONE mask for its whole row range: slab h_index * total_rows + cu[seq_groups[g]] and query / key indices counted
+ * from the group's first row, where the ungrouped packed mode uses cu[seq] and indices local to each sequence.  Forward and
+ * backward agree as long as both get the same groups; the same batch grouped differently draws a different (equally
+ * distributed) mask.  This is intended: the group is the kernels' unit of work.
+ * kv_len[b] = 0: zero output, lse = -inf, zero dQ / dK / dV for that sequence; kv_len[b] > lk counts as lk.
+ * A sequence with ONE valid key has exact dK = 0; in bf16 the forward rounds P to bf16 but normalises by the unrounded sum,
+ * so O = V (1 +- 2^-9) and dK of that key is rounding noise of that size (summed over the queries), not exactly 0.
  * out_lo (bf16 only, optional): the forward also stores lo = bf16(O - bf16(O)); handed to the backward, delta is formed
  * from out + out_lo, i.e. with fp32-like accuracy.  With `out` alone delta carries the 2^-9 rounding of the stored
  * output, which does NOT cancel in dS = P (dP - delta) and dominates the query / key gradients whenever those are small

@@ -1,4 +1,5 @@
-"""Shared test helpers: golden loading, oracle model construction from the parameter recipe."""
+"""Shared test helpers: golden loading, oracle model construction from the parameter recipe, the float64 attention reference
+and the device kernel names a call launches."""
 import json
 import os
 
@@ -117,3 +118,77 @@ def attn_dropout_scale(seed: int, slab: int, nq: int, nk: int, p: float, device=
     u = u ^ (u >> 15)
     field = (u >> (16 * (q & 1) + 8 * (k & 1))) & 0xFF
     return (field >= th).to(torch.float64) * ks
+
+
+def _dense_reference(q, k, v, go, h, scale, kv_len=None, drop=None):
+    """Dense softmax attention in float64, forward and autograd backward: q, go [b, lq, h*d], k, v [b, lk, h*d] (any float
+    dtype, any device) -> out, dq, dk, dv as float64 tensors of the same shapes.  Keys at or past ``kv_len[bi]`` (clamped to
+    [0, lk], as the kernels do) take no part; a sequence with no valid key has zero output and zero gradients (the kernels'
+    contract, gmlm_hip.h).  ``drop(bi, hi)`` -> [lq, lk] multiplier of the probabilities (0 or the keep scale).  Heads are
+    batched, a few at a time so that one [heads, lq, lk] float64 tensor stays below 1 GiB."""
+    b, lq, hd = q.shape
+    lk, d = k.shape[1], hd // h
+    outs = [torch.zeros(b, t_.shape[1], hd, dtype=torch.float64, device=q.device) for t_ in (q, q, k, v)]
+    chunk = max(1, (1 << 27) // max(1, lq * lk))
+    for bi in range(b):
+        n = lk if kv_len is None else max(0, min(lk, int(kv_len[bi])))
+        if n == 0:
+            continue                                              # no valid key: zero output, zero gradients
+        for h0 in range(0, h, chunk):
+            h1 = min(h, h0 + chunk)
+            heads = lambda t_, rows: t_[bi, :rows].detach().reshape(rows, h, d)[:, h0:h1].transpose(0, 1).double().contiguous()
+            qq, kk, vv = (heads(t_, rows).requires_grad_(True) for t_, rows in ((q, lq), (k, n), (v, n)))
+            p = torch.softmax((qq @ kk.transpose(1, 2)) * scale, -1)
+            if drop is not None:
+                p = p * torch.stack([drop(bi, hi)[:, :n] for hi in range(h0, h1)]).to(p)
+            o = p @ vv
+            o.backward(heads(go, lq))
+            cols = slice(h0 * d, h1 * d)
+            back = lambda t_: t_.transpose(0, 1).reshape(t_.shape[1], -1)
+            outs[0][bi, :, cols], outs[1][bi, :, cols] = back(o.detach()), back(qq.grad)
+            outs[2][bi, :n, cols], outs[3][bi, :n, cols] = back(kk.grad), back(vv.grad)
+            del p, o
+    return outs
+
+
+def _close(name, got, ref, max_rel, l2_rel):
+    """max |got - ref| / max |ref| <= max_rel and ||got - ref|| / ||ref|| <= l2_rel over the whole tensor."""
+    got = got.double()
+    e = got - ref
+    mx, l2 = float(e.abs().max()) / float(ref.abs().max()), float(e.norm()) / float(ref.norm())
+    print(f"  {name}: max|err| / max|ref| = {mx:.2e}, l2 rel = {l2:.2e}")
+    assert mx <= max_rel and l2 <= l2_rel, (name, mx, l2)
+
+
+def _bare_kernel_name(name):
+    """'void gmlm::attn_fwd_kernel<float, 64, 2, false>(gmlm::AttnParams)' (or its mangled form) ->
+    'attn_fwd_kernel<float, 64, 2, false>': no return type, no parameter list, no leading 'gmlm::'."""
+    if name.startswith("_Z"):
+        name = torch._C._demangle(name)
+    if name.startswith("void "):
+        name = name[5:]
+    depth = 0
+    for i, c in enumerate(name):
+        if c == "<":
+            depth += 1
+        elif c == ">":
+            depth -= 1
+        elif c == "(" and depth == 0:
+            name = name[:i]
+            break
+    return name[len("gmlm::"):] if name.startswith("gmlm::") else name
+
+
+def kernels_run(fn):
+    """Runs ``fn`` under the torch profiler and returns the set of the project's device kernels it launched, as bare template
+    ids ('attn_bwd_dkv_kernel<unsigned short, 64, 4, true, 128>'; bf16 shows up as 'unsigned short').  Fails when the
+    profiler saw no device kernel at all, so that a profiler that records nothing cannot make a name assertion pass."""
+    from torch.autograd import DeviceType
+    from torch.profiler import ProfilerActivity, profile
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CUDA]) as prof:
+        fn()
+        torch.cuda.synchronize()
+    names = [e.name for e in prof.events() if e.device_type == DeviceType.CUDA]
+    assert names, "the profiler recorded no device kernel"
+    return {_bare_kernel_name(n) for n in names if "gmlm::" in n or n.startswith("_ZN4gmlm")}

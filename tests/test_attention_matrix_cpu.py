@@ -1,0 +1,72 @@
+"""Coverage guard of the attention dispatch matrix (no GPU needed): the attention kernels compiled into the library's gfx950
+code objects must be exactly the kernels that tests/test_gpu_attention_matrix.py runs against float64 (``CASES``) plus
+those it lists as unreachable (``UNREACHABLE``).  A new instantiation without a parity case, or a stale table entry, fails
+here, by name."""
+import os
+import shutil
+import subprocess
+import tempfile
+
+import pytest
+import torch
+
+from gmlm_amd import _lib
+from helpers import _bare_kernel_name
+from test_gpu_attention_matrix import CASES, UNREACHABLE, _is_attention
+from test_wgrad_cpu import LLVM, _code_objects
+
+
+def _compiled_attention_kernels():
+    """Bare template ids of the attention kernels (gmlm::attn_*, gmlm::d128::*) that have a kernel descriptor (.kd) in a
+    device code object of the built library; the host part of the .so (launch stubs) is not read."""
+    if not os.path.exists(_lib.LIB_PATH):
+        pytest.skip("libgmlm_hip.so not built")
+    if not all(os.path.exists(os.path.join(LLVM, t)) for t in ("llvm-readelf", "llvm-objcopy")):
+        pytest.skip("ROCm llvm tools not found")
+    tmp = tempfile.mkdtemp()
+    try:
+        names = set()
+        for co in _code_objects(_lib.LIB_PATH, tmp):
+            syms = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--syms", "--wide", co], check=True, capture_output=True,
+                                  text=True).stdout
+            for line in syms.splitlines():
+                f = line.split()
+                if f and f[-1].endswith(".kd") and f[-1].startswith("_ZN4gmlm"):
+                    names.add(_bare_kernel_name(torch._C._demangle(f[-1][:-3])))
+        return {n for n in names if _is_attention(n)}
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+
+
+def test_every_attention_instantiation_has_a_parity_case_or_a_reason():
+    compiled = _compiled_attention_kernels()
+    run = set().union(*(c.fwd | c.bwd for c in CASES))
+    listed = run | set(UNREACHABLE)
+    assert compiled, "no attention kernel found in the code objects"
+    assert not sorted(compiled - listed), f"compiled but neither in CASES nor in UNREACHABLE: {sorted(compiled - listed)}"
+    assert not sorted(listed - compiled), f"listed but not compiled: {sorted(listed - compiled)}"
+    assert not sorted(run & set(UNREACHABLE)), f"both run by a case and listed as unreachable: {sorted(run & set(UNREACHABLE))}"
+
+
+def test_every_dropout_template_runs_both_ways():
+    """Each reachable kernel with a DROP template parameter runs in CASES with dropout and without."""
+    run = set().union(*(c.fwd | c.bwd for c in CASES))
+    for n in run:
+        for a, b in ((", true", ", false"), (", false", ", true")):
+            if a in n:
+                assert n.replace(a, b) in run, (n, "its other dropout variant has no case")
+
+
+def test_case_table_is_consistent():
+    ids = [c.id for c in CASES]
+    assert len(ids) == len(set(ids))
+    for c in CASES:
+        assert c.mode in ("pad", "kvlen", "packed", "groups") and c.layout in ("contig", "fused"), c.id
+        assert all(_is_attention(n) for n in c.fwd | c.bwd), c.id
+        assert (c.p > 0) == any(", true" in n for n in c.fwd | c.bwd), c.id
+        if c.mode == "kvlen":
+            assert len(c.lens) == c.b, c.id
+        if c.mode in ("packed", "groups"):
+            assert len(c.lens) == c.b and sum(c.lens) == c.lq == c.lk, c.id
+        if c.layout == "fused":
+            assert c.lq == c.lk and c.mode in ("pad", "kvlen"), c.id

@@ -418,6 +418,7 @@ def test_attention_online_softmax_rescale_branch(dev, dt):
     reference-max schedule per 32-query wave and 32-key block, same split lse / delta terms in the backward): forward AND
     all three gradients within 5e-2 relative, elementwise."""
     from gmlm_amd.ops import attention
+    from helpers import kernels_run
     b, h, l, d = 1, 2, 400, 64
     g = torch.Generator().manual_seed(17)
     q, k, v = (torch.randn(b, l, h * d, generator=g) for _ in range(3))
@@ -427,7 +428,11 @@ def test_attention_online_softmax_rescale_branch(dev, dt):
     q, k, v = q.to(dt), k.to(dt), v.to(dt)
     go = torch.randn(b, l, h * d, generator=g).to(dt)
     qd, kd, vd = (x.to(dev).requires_grad_(True) for x in (q, k, v))
-    y = attention(qd, kd, vd, None, h, d ** -0.5)
+    box = {}
+    ran = kernels_run(lambda: box.setdefault("y", attention(qd, kd, vd, None, h, d ** -0.5)))
+    y = box["y"]
+    want = "attn_fwd_kernel<float, 64, 2, false>" if dt == torch.float32 else "attn_fwd_pipe_kernel<64, 4, false, 2>"
+    assert {n for n in ran if n.startswith("attn_")} == {want}, ran
     y.backward(go.to(dev))
     qr, kr, vr = (x.float().clone().requires_grad_(True) for x in (q, k, v))
     ref = _attn_ref(qr, kr, vr, None, h, d ** -0.5)
@@ -453,6 +458,77 @@ def test_attention_online_softmax_rescale_branch(dev, dt):
         print(f"  rescale branch bf16 {name}: max|err|/max = {float((a - r_).abs().max()) / sc:.2e}, elements off = {int(bad.sum())}")
         assert int(bad.sum()) == 0, name
 
+
+
+# one spiked input per copy of the deferred online-softmax rescale (kDefer in attn_fwd_kernel and attn_d128.hip, kSumDefer /
+# settle() in attn_fwd_pipe.hip): id -> (dtype, d, b, h, lq, lk, forward kernel that must run, checker)
+_RESCALE_FAMILIES = {
+    "f32_d64_w8": (torch.float32, 64, 8, 8, 2100, 2100, "attn_fwd_kernel<float, 64, 8, false>", "fp64"),
+    "f32_d96_w2": (torch.float32, 96, 1, 2, 400, 400, "attn_fwd_kernel<float, 96, 2, false>", "fp64"),
+    "f32_d96_w8": (torch.float32, 96, 8, 8, 2100, 2100, "attn_fwd_kernel<float, 96, 8, false>", "fp64"),
+    "bf16_d64_w2": (torch.bfloat16, 64, 1, 2, 100, 400, "attn_fwd_kernel<unsigned short, 64, 2, false>", "fp64"),
+    "pipe_d96_w4": (torch.bfloat16, 96, 1, 2, 400, 400, "attn_fwd_pipe_kernel<96, 4, false, 2>", "emulation"),
+    "pipe_d96_w8": (torch.bfloat16, 96, 8, 8, 2100, 2100, "attn_fwd_pipe_kernel<96, 8, false, 2>", "emulation"),
+    "d128_bf16": (torch.bfloat16, 128, 1, 2, 400, 400, "d128::fwd_kernel<unsigned short, false>", "fp64"),
+    "d128_f32": (torch.float32, 128, 1, 2, 400, 400, "d128::fwd_kernel<float, false>", "fp64"),
+}
+
+
+@pytest.mark.parametrize("family", list(_RESCALE_FAMILIES))
+def test_attention_online_softmax_rescale_branch_every_family(dev, family):
+    """The test above for every other copy of the deferred rescale.  Batch 0 gets three spiked keys: one in the second
+    64-key tile and one in a middle tile, each far above every earlier score of one query, and one in the last (partial)
+    tile that jumps again for the first of those queries.  The forward kernel that ran is asserted by name.
+
+    Spike sizes (natural score units, s = a |q|^2 / sqrt(d) ~ a sqrt(d)): the rescale runs when the running max grows by
+    more than kDefer = 6 in log2 units (4.2 natural) or, in the pipelined forward, when a block sum exceeds kSumDefer = 256
+    (a jump of ~5.5).  fp32 and the pipelined forward take the large spikes of the test above (s ~ 50-120): fp32 is checked
+    against float64 at the fp32 budget, the pipelined forward against its bf16 emulation (its pre-scaled query carries an
+    extra ~|s| 2^-9 rounding that float64 does not model).  The other bf16 kernels do not pre-scale q and are checked
+    against float64 at the bf16 budget, so their spikes stay small: s ~ 10 and 12 after N(0, 1) scores (jumps of ~6-8
+    natural units, above both thresholds) and s ~ 20 for the second jump, where the bf16 rounding of a score (~|s| 2^-9 =
+    0.04) is still inside the budget."""
+    from gmlm_amd.ops import attention
+    from helpers import _close, _dense_reference, kernels_run
+    dt, d, b, h, lq, lk, want, checker = _RESCALE_FAMILIES[family]
+    g = torch.Generator().manual_seed(17 + d)
+    q, go = (torch.randn(b, lq, h * d, generator=g) for _ in range(2))
+    k, v = (torch.randn(b, lk, h * d, generator=g) for _ in range(2))
+    big = dt == torch.float32 or checker == "emulation"
+    a1, a2, a3 = (6.0, 9.0, 12.0) if big else tuple(x * 8.0 / d ** 0.5 for x in (1.25, 1.5, 2.5))
+    mid = lk // 2 + 33                                         # a middle tile, not on a tile boundary
+    k[0, 70] = q[0, 5] * a1                                    # second tile: first jump for query 5
+    k[0, mid] = q[0, min(lq - 1, 60)] * a2                     # middle tile: a jump for another query
+    k[0, lk - 1] = q[0, 5] * a3                                # last (partial) tile: second jump for query 5
+    q, k, v, go = (x.to(dev, dt) for x in (q, k, v, go))
+    qd, kd, vd = (x.clone().requires_grad_(True) for x in (q, k, v))
+    box = {}
+    ran = kernels_run(lambda: box.setdefault("y", attention(qd, kd, vd, None, h, d ** -0.5)))
+    y = box["y"]
+    assert {n for n in ran if n.startswith(("attn_fwd", "d128::fwd"))} == {want}, ran
+    y.backward(go)
+    got = (y.detach(), qd.grad, kd.grad, vd.grad)
+    if checker == "fp64":
+        ref = _dense_reference(q, k, v, go, h, d ** -0.5)
+        for name, a, r_ in zip(("out", "dq", "dk", "dv"), got, ref):
+            if dt == torch.float32:
+                _close(name, a, r_, 1e-4, 1e-5)
+            else:
+                _close(name, a, r_, 2e-2, 6e-3 if name == "out" else 8e-3)
+        return
+    import bf16_emulation as E
+    heads = lambda t_: t_[0].float().cpu().view(-1, h, d).transpose(0, 1).contiguous()           # batch 0 (spiked): [h, L, d]
+    qe, ke, ve = (heads(x).requires_grad_(True) for x in (q, k, v))
+    ye = E._LongAttention.apply(qe, ke, ve, d ** -0.5)
+    ye.backward(heads(go))
+    back = lambda t_: t_.transpose(0, 1).reshape(-1, h * d)
+    for name, a, r_ in (("out", got[0], back(ye.detach())), ("dq", got[1], back(qe.grad)), ("dk", got[2], back(ke.grad)),
+                        ("dv", got[3], back(ve.grad))):
+        a = a[0].float().cpu()
+        sc = float(r_.abs().max())
+        bad = ((a - r_).abs() > 5e-2 * r_.abs() + 4e-3 * sc)
+        print(f"  rescale branch {family} {name}: max|err|/max = {float((a - r_).abs().max()) / sc:.2e}, elements off = {int(bad.sum())}")
+        assert int(bad.sum()) == 0, name
 
 @pytest.mark.parametrize("ra,nb,cols", [(1, 30, 768 * 1536), (4, 30, 64 * 128), (5, 32, 1000), (3, 7, 2096 * 16)])
 def test_basis_compose_fwd_bwd(dev, ra, nb, cols):
