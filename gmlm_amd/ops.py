@@ -253,6 +253,9 @@ class RGCNAggregate(torch.autograd.Function):
 # ---------------------------------------------------------------------------------------------
 # K4: GraphNorm + GELU + dropout
 # ---------------------------------------------------------------------------------------------
+GN_ONE_PASS_MAX_RATIO = 64.0   # R above which a GraphNorm column takes the second statistics pass (row 0 beyond ~8 sigma)
+
+
 class GraphNormAct(torch.autograd.Function):
     """y = dropout(act(GraphNorm(z))).  z [n, f] in the compute dtype (the GEMM output feeds the kernels
     directly: no fp32 staging copy); y and dz in the same dtype; statistics fp32.
@@ -275,7 +278,7 @@ class GraphNormAct(torch.autograd.Function):
         stats = torch.empty(2, f, dtype=torch.float32, device=dev)
         shift = None
         if reducer is None and n > 0:
-            shift = z[0].float().contiguous()          # shifted sums: no cancellation in E[o^2]
+            shift = z[0].float().contiguous()          # shifted sums: no cancellation in E[o^2] unless row 0 lies far out (below)
         ws = _ws(lib().gmlm_colstats_workspace_bytes(n, f), dev)
         check(lib().gmlm_colstats(_ptr(z), dt, _ptr(shift), n, f, _ptr(stats[0]), _ptr(stats[1]), _ptr(ws), ws.numel(), st),
               "gmlm_colstats")
@@ -290,10 +293,22 @@ class GraphNormAct(torch.autograd.Function):
             mean = mu.contiguous()
             rstd = torch.rsqrt(stats[1] / n_total + eps).contiguous()
         else:
-            mean = torch.empty(f, dtype=torch.float32, device=dev)
-            rstd = torch.empty(f, dtype=torch.float32, device=dev)
+            mr = torch.empty(2, f, dtype=torch.float32, device=dev)          # [mean; rstd]
             check(lib().gmlm_graphnorm_finalize(_ptr(stats[0]), _ptr(stats[1]), _ptr(shift), _ptr(ms), n_total, f, eps,
-                                                _ptr(mean), _ptr(rstd), st), "gmlm_graphnorm_finalize")
+                                                _ptr(mr[0]), _ptr(mr[1]), st), "gmlm_graphnorm_finalize")
+            # finalize forms E[o^2] = (s2 - 2 d s1) / n + d^2 with d = mean*ms - z[0]: when row 0 lies far from the column mean
+            # this cancels and loses ~log2(R) bits, R = (s2 / n) / var.  A second pass shifted by that mean (s1 ~ 0: E[o^2] is
+            # the sum of s2 / n and d^2, nothing cancels) replaces the columns with R > GN_ONE_PASS_MAX_RATIO; the others keep
+            # the one-pass values ('GraphNorm statistics').  No host sync: both passes always run, the
+            # choice is per column on the device.
+            stats2 = torch.empty_like(stats)
+            check(lib().gmlm_colstats(_ptr(z), dt, _ptr(mr[0]), n, f, _ptr(stats2[0]), _ptr(stats2[1]), _ptr(ws), ws.numel(),
+                                      st), "gmlm_colstats")
+            mr2 = torch.empty_like(mr)
+            check(lib().gmlm_graphnorm_finalize(_ptr(stats2[0]), _ptr(stats2[1]), _ptr(mr[0]), _ptr(ms), n_total, f, eps,
+                                                _ptr(mr2[0]), _ptr(mr2[1]), st), "gmlm_graphnorm_finalize")
+            mr = torch.where(stats[1] * mr[1] * mr[1] > GN_ONE_PASS_MAX_RATIO * n_total, mr2, mr)
+            mean, rstd = mr[0], mr[1]
         y = torch.empty(n, f, dtype=out_dtype, device=dev)
         sd = ctx.sd = _sd()
         check(lib().gmlm_graphnorm_apply(_ptr(z), _ptr(mean), _ptr(rstd), _ptr(w), _ptr(b), _ptr(ms), n, f, int(act),

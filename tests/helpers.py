@@ -1,5 +1,5 @@
-"""Shared test helpers: golden loading, oracle model construction from the parameter recipe, the float64 attention reference
-and the device kernel names a call launches."""
+"""Shared test helpers: golden loading, oracle model construction from the parameter recipe, the float64 attention reference,
+the restated dropout masks and the device kernel names a call launches."""
 import json
 import os
 
@@ -118,6 +118,35 @@ def attn_dropout_scale(seed: int, slab: int, nq: int, nk: int, p: float, device=
     u = u ^ (u >> 15)
     field = (u >> (16 * (q & 1) + 8 * (k & 1))) & 0xFF
     return (field >= th).to(torch.float64) * ks
+
+
+def _mul32(a, c):
+    """(a * c) mod 2^32 for int64 tensors a < 2^32 and a 32-bit constant c, in 16-bit halves (no int64 overflow)."""
+    return ((a & 0xFFFF) * c + ((((a >> 16) * c) & 0xFFFF) << 16)) & 0xFFFFFFFF
+
+
+def elem_dropout_scale(seed: int, idx, p: float):
+    """The element-wise dropout mask of the GraphNorm, LayerNorm and bias+GELU kernels (``hash_u32`` / ``dropout_scale`` /
+    ``dropout_keep_bits``, common.hpp), restated with torch integer arithmetic (checker only; DESIGN.md section 4 'Dropout').
+    ``idx``: int64 tensor of element offsets in the row-major tensor (r * f + c).  One 32-bit word decides the pair idx >> 1:
+    w = lowbias32(lo32(i) * C1 + hi32(i) * C2 + lo32(seed)) ^ hi32(seed) with i = idx >> 1; the element's field is the 16-bit
+    half (idx & 1) of w, kept when field >= th = lround(p * 65536) clamped to 65535.  Returns a float32 tensor of idx's shape:
+    0 or the fp32 keep scale 65536f / (65536f - th)."""
+    m32 = 0xFFFFFFFF
+    th = 0 if p <= 0 else int(np.floor(np.float32(p) * np.float32(65536.0) + np.float32(0.5)))
+    th = max(0, min(65535, th))
+    ks = np.float32(65536.0) / (np.float32(65536.0) - np.float32(th))
+    idx = torch.as_tensor(idx, dtype=torch.int64)
+    i = idx >> 1
+    x = (_mul32(i & m32, 0x9E3779B1) + _mul32(i >> 32, 0x85EBCA77) + (seed & m32)) & m32
+    x = x ^ (x >> 16)
+    x = _mul32(x, 0x7FEB352D)
+    x = x ^ (x >> 15)
+    x = _mul32(x, 0x846CA68B)
+    x = x ^ (x >> 16)
+    x = x ^ ((seed >> 32) & m32)
+    field = (x >> (16 * (idx & 1))) & 0xFFFF
+    return (field >= th).to(torch.float32) * float(ks)
 
 
 def _dense_reference(q, k, v, go, h, scale, kv_len=None, drop=None):

@@ -16,8 +16,8 @@ from test_gpu_attention_matrix import CASES, UNREACHABLE, _is_attention
 from test_wgrad_cpu import LLVM, _code_objects
 
 
-def _compiled_attention_kernels():
-    """Bare template ids of the attention kernels (gmlm::attn_*, gmlm::d128::*) that have a kernel descriptor (.kd) in a
+def _compiled_kernels(keep):
+    """Bare template ids of the project's kernels for which ``keep(name)`` holds and that have a kernel descriptor (.kd) in a
     device code object of the built library; the host part of the .so (launch stubs) is not read."""
     if not os.path.exists(_lib.LIB_PATH):
         pytest.skip("libgmlm_hip.so not built")
@@ -33,13 +33,13 @@ def _compiled_attention_kernels():
                 f = line.split()
                 if f and f[-1].endswith(".kd") and f[-1].startswith("_ZN4gmlm"):
                     names.add(_bare_kernel_name(torch._C._demangle(f[-1][:-3])))
-        return {n for n in names if _is_attention(n)}
+        return {n for n in names if keep(n)}
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
 
 
 def test_every_attention_instantiation_has_a_parity_case_or_a_reason():
-    compiled = _compiled_attention_kernels()
+    compiled = _compiled_kernels(_is_attention)
     run = set().union(*(c.fwd | c.bwd for c in CASES))
     listed = run | set(UNREACHABLE)
     assert compiled, "no attention kernel found in the code objects"
