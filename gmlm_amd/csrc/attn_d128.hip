@@ -2,15 +2,16 @@
 // Shape: padded [b, l, h*128] with an optional per-sequence key length (kv_len) and in-kernel probability dropout: the
 // CrossAttention of a 1024-wide text encoder (8 heads x 128, one sequence of N nodes, main.py:159-163) and the self-attention
 // of any encoder whose head dim is 97..128 (zero-padded to 128 by nn.attention_any_dim).
-// Structure and arithmetic follow the streaming kernels of attn_kernels.hip (S^T = K Q^T with the query on the lane, online
-// softmax in the log2 domain, P fed straight from the accumulators into O^T += V^T P^T, bf16 folding of lse / delta / the
-// key mask into one extra contraction step, exact fp32 delta through out_lo, the replayable 2 x 2 dropout hash of
-// attn_common.hpp with the same row offsets), with:
+// Forward, delta and dK/dV ARE the streaming kernels of attn_kernels.hip: both files instantiate the bodies of attn_stream.hpp
+// (S^T = K Q^T with the query on the lane, online softmax in the log2 domain, P fed straight from the accumulators into
+// O^T += V^T P^T, bf16 folding of lse / delta / the key mask into one extra contraction step, exact fp32 delta through out_lo,
+// the replayable 2 x 2 dropout hash of attn_common.hpp with the same row offsets).  dq_kernel alone keeps its own copy of
+// attn_dq_body's text (reason at the kernel).  This file fixes D = 128, 4 waves, and:
 //  * 1-D grids of (tile, (batch, head)) work items: no 65,535 bound on batch * heads;
 //  * bf16: 64-row K / V (forward, dQ) and 32-row Q / dO (dK/dV) tiles, double-buffered in LDS (68 KiB / 35 KiB per
 //    workgroup); fp32 (the 1e-4 parity path, v_mfma_f32_32x32x2_f32): 32-row tiles, one buffer.  No kernel spills.
 //  * dK/dV without atomics: a workgroup owns 128 keys and walks all query tiles in order (deterministic).
-#include "attn_common.hpp"
+#include "attn_stream.hpp"
 
 namespace gmlm {
 namespace d128 {
@@ -20,195 +21,38 @@ constexpr int D = 128, NW = 4, NT = NW * 64, BQ = NW * 32;   // 4 waves, 32 rows
 struct Params {
   AttnParams a;            // lse / delta are [b, h, lq]
   int64_t dout_stride;     // row stride of dO / O (= h * 128)
-  uint32_t ntiles;         // tiles per (batch, head) pair in the 1-D grid (query tiles: forward, dQ; key tiles: dK/dV)
 };
 
 template <typename T> struct Cfg;
 template <> struct Cfg<bf16_t> { static constexpr int KT = 64, QT = 32; static constexpr bool DBUF = true; };
 template <> struct Cfg<float> { static constexpr int KT = 32, QT = 32; static constexpr bool DBUF = false; };
 
-// ------------------------------------------------------------------------------------------------
-// forward: workgroup = 128 query rows of one (batch, head), loop over key tiles
-// ------------------------------------------------------------------------------------------------
-template <typename T, bool DROP>
-__global__ __launch_bounds__(NT) void fwd_kernel(Params x) {
-  const AttnParams& p = x.a;
-  constexpr bool DBUF = Cfg<T>::DBUF;
-  constexpr int KT = Cfg<T>::KT, KB = KT / 32, PITCH = D + Pad<T>::v, DB = D / 32, NBUF = DBUF ? 2 : 1;
-  __shared__ __attribute__((aligned(16))) T ks[NBUF][KT * PITCH];
-  __shared__ __attribute__((aligned(16))) T vs[NBUF][KT * PITCH];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 31, h = lane >> 5;
+// work item of the 1-D grid -> (tile, batch, head); tiles are outermost
+struct Item { int64_t tile, b, hd; };
+__device__ __forceinline__ Item decode(const AttnParams& p) {
   const int64_t pairs = p.b * p.h, item = blockIdx.x;
-  const int64_t qt = item / pairs, bh = item % pairs;
-  const int64_t b = bh / p.h, hd = bh % p.h;
-  int64_t lq_, lk_, qbase, kbase, lse_base;
-  seq_view(p, b, hd, lq_, lk_, qbase, kbase, lse_base);
-  const int64_t q_tile0 = qt * BQ;
-  if (q_tile0 >= lq_) return;                                  // block-uniform
-  const int64_t q_row = q_tile0 + w * 32 + r;
-  const bool q_ok = q_row < lq_;
-  const bool wave_live = q_tile0 + w * 32 < lq_;
-  int64_t kvlen = lk_;
-  if (p.kv_len) { kvlen = p.kv_len[b]; if (kvlen > lk_) kvlen = lk_; if (kvlen < 0) kvlen = 0; }
-  const T* qg = static_cast<const T*>(p.q) + (qbase + (q_ok ? q_row : 0)) * p.q_stride + hd * D;
-  const T* kg = static_cast<const T*>(p.k) + kbase * p.k_stride + hd * D;
-  const T* vg = static_cast<const T*>(p.v) + kbase * p.v_stride + hd * D;
-  RowFrag<T, D> qf;
-  qf.load(qg, q_ok, h);
-  f32x16 o[DB];
-#pragma unroll
-  for (int d = 0; d < DB; ++d)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) o[d][i] = 0.f;
-  float m = -INFINITY, l = 0.f;
-  const float sl2 = p.scale * kLog2e;
-  const uint32_t dq_u = drop_base(attn_seed(p), lse_base) + (uint32_t)(q_row >> 1) * kDropC1 + (uint32_t)(2 * h) * kDropC2;
-  const int q_odd = (int)(q_row & 1);
-  const int ntiles = (int)((kvlen + KT - 1) / KT);
-  TileRegs<T, D, KT, NT> kr, vr;
-  kr.init(p.k_stride, tid);
-  vr.init(p.v_stride, tid);
-  if (ntiles > 0) {
-    kr.load(kg, p.k_stride, 0, lk_, tid);
-    vr.load(vg, p.v_stride, 0, lk_, tid);
-    kr.store(ks[0], tid);
-    vr.store(vs[0], tid);
-  }
-  __syncthreads();
-  for (int t = 0; t < ntiles; ++t) {
-    const int64_t kv0 = (int64_t)t * KT;
-    const int cur = DBUF ? (t & 1) : 0;
-    const bool more = t + 1 < ntiles;
-    if (DBUF && more) {
-      kr.load(kg, p.k_stride, kv0 + KT, lk_, tid);
-      vr.load(vg, p.v_stride, kv0 + KT, lk_, tid);
-    }
-    if (wave_live) {
-      f32x16 s[KB];
-#pragma unroll
-      for (int kb = 0; kb < KB; ++kb) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) s[kb][i] = 0.f;
-        mma_rows<D>(ks[cur], PITCH, kb * 32, qf, s[kb], r, h);
-      }
-      float rmax = -INFINITY;
-      if (kv0 + KT <= kvlen) {                        // whole tile valid (block-uniform): no per-key compare
-#pragma unroll
-        for (int kb = 0; kb < KB; ++kb)
-#pragma unroll
-          for (int i = 0; i < 16; ++i) rmax = fmaxf(rmax, s[kb][i]);
-      } else {
-#pragma unroll
-        for (int kb = 0; kb < KB; ++kb)
-#pragma unroll
-          for (int i = 0; i < 16; ++i) {
-            const int64_t key = kv0 + kb * 32 + acc_row(i, h);
-            const float v = key < kvlen ? s[kb][i] : -INFINITY;
-            s[kb][i] = v;
-            rmax = fmaxf(rmax, v);
-          }
-      }
-      rmax = xhalf_max(rmax);
-      float m_new = fmaxf(m, rmax * sl2);             // finite: key kv0 is always valid
-      const bool keep = __all(m_new - m <= kDefer);
-      float alpha = 1.f;
-      if (keep) m_new = m;
-      else alpha = fast_exp2(m - m_new);
-      float rsum = 0.f;
-#pragma unroll
-      for (int kb = 0; kb < KB; ++kb)
-#pragma unroll
-        for (int i = 0; i < 16; i += 2) {
-          const float e0 = fast_exp2(fmaf(s[kb][i], sl2, -m_new));
-          const float e1 = fast_exp2(fmaf(s[kb][i + 1], sl2, -m_new));
-          rsum += e0 + e1;
-          if (DROP) {
-            float m0, m1;
-            drop_pair_q(dq_u + ((uint32_t)(t * (KT / 2)) + (uint32_t)((kb * 32 + acc_row(i, 0)) >> 1)) * kDropC2, q_odd, p.drop_thresh, p.keep_scale, m0, m1);
-            s[kb][i] = e0 * m0;
-            s[kb][i + 1] = e1 * m1;
-          } else {
-            s[kb][i] = e0;
-            s[kb][i + 1] = e1;
-          }
-        }
-      rsum = xhalf_sum(rsum);
-      l = l * alpha + rsum;
-      m = m_new;
-      if (!keep) {
-#pragma unroll
-        for (int d = 0; d < DB; ++d)
-#pragma unroll
-          for (int i = 0; i < 16; ++i) o[d][i] *= alpha;
-      }
-#pragma unroll
-      for (int kb = 0; kb < KB; ++kb) mma_acc<D>(vs[cur], PITCH, kb * 32, s[kb], o, lane);
-    }
-    if (DBUF) {
-      if (more) {
-        kr.store(ks[cur ^ 1], tid);
-        vr.store(vs[cur ^ 1], tid);
-      }
-      __syncthreads();
-    } else if (more) {
-      __syncthreads();
-      kr.load(kg, p.k_stride, kv0 + KT, lk_, tid);
-      vr.load(vg, p.v_stride, kv0 + KT, lk_, tid);
-      kr.store(ks[0], tid);
-      vr.store(vs[0], tid);
-      __syncthreads();
-    }
-  }
-  if (q_ok) {
-    const float inv = l > 0.f ? 1.f / l : 0.f;
-    T* og = static_cast<T*>(p.o_w) + (qbase + q_row) * x.dout_stride + hd * D;
-#pragma unroll
-    for (int d = 0; d < DB; ++d) store_t<T>(og + d * 32, o[d], inv, h);
-    if constexpr (sizeof(T) == 2) {
-      if (p.o_lo_w) {
-        T* olg = static_cast<T*>(p.o_lo_w) + (qbase + q_row) * x.dout_stride + hd * D;
-#pragma unroll
-        for (int d = 0; d < DB; ++d) store_t_lo(olg + d * 32, o[d], inv, h);
-      }
-    }
-    if (h == 0 && p.lse_w) p.lse_w[lse_base + q_row] = l > 0.f ? (m + __log2f(l)) * kLn2 : -INFINITY;
-  }
+  const int64_t bh = item % pairs;
+  return {item / pairs, bh / p.h, bh % p.h};
 }
 
-// ------------------------------------------------------------------------------------------------
+// forward: workgroup = 128 query rows of one (batch, head), loop over key tiles
+template <typename T, bool DROP>
+__global__ __launch_bounds__(NT) void fwd_kernel(Params x) {
+  const Item it = decode(x.a);
+  attn_fwd_body<T, D, NW, DROP, Cfg<T>::KT, Cfg<T>::DBUF>(x.a, it.tile, it.b, it.hd, x.dout_stride);
+}
+
 // backward: delta = rowsum(dO * O) over rows of [b * lq, h, 128] (O = out + out_lo when the forward stored the residual)
-// ------------------------------------------------------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(256) void delta_kernel(const T* __restrict__ o, const T* __restrict__ o_lo, const T* __restrict__ dout,
                                                     int64_t rows /* b * lq * h */, int64_t lq, int64_t hn, float* __restrict__ delta) {
-  constexpr int V = Store<T>::kVec, LANES = D / V;              // 16 (bf16) or 32 (fp32) lanes per row
-  const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t row = gid / LANES;
-  const int c = (int)(gid % LANES);
-  float acc = 0.f;
-  if (row < rows) {
-    float a[V], g[V];
-    Store<T>::ldv(o + row * D + c * V, a);
-    Store<T>::ldv(dout + row * D + c * V, g);
-    if (o_lo) {
-      float al[V];
-      Store<T>::ldv(o_lo + row * D + c * V, al);
-#pragma unroll
-      for (int v = 0; v < V; ++v) a[v] += al[v];
-    }
-#pragma unroll
-    for (int v = 0; v < V; ++v) acc += a[v] * g[v];
-  }
-  for (int off = LANES >> 1; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
-  if (row < rows && c == 0) {
-    const int64_t hd = row % hn, bq = row / hn, q = bq % lq, b = bq / lq;
-    delta[(b * hn + hd) * lq + q] = acc;
-  }
+  attn_delta_body<T>(o, o_lo, dout, rows, D, lq, hn, delta);     // 16 (bf16) or 32 (fp32) lanes per row
 }
 
-// ------------------------------------------------------------------------------------------------
-// backward: dQ.  workgroup = 128 queries of one (batch, head), loop over key tiles
-// ------------------------------------------------------------------------------------------------
+// backward: dQ.  workgroup = 128 queries of one (batch, head), loop over key tiles.
+// The text of attn_dq_body (attn_stream.hpp), kept as a kernel of its own: compiled through the shared body the bf16 dropout
+// instantiation takes 262 instead of 250 VGPRs, and with 68 KiB of LDS per workgroup that is one workgroup per CU instead
+// of two.  A fix to either copy belongs in both.
 template <typename T, bool DROP>
 __global__ __launch_bounds__(NT) void dq_kernel(Params x) {
   const AttnParams& p = x.a;
@@ -347,190 +191,17 @@ __global__ __launch_bounds__(NT) void dq_kernel(Params x) {
   }
 }
 
-// ------------------------------------------------------------------------------------------------
 // backward: dK, dV.  workgroup = 128 keys of one (batch, head), loop over query tiles of 32 in order
-// ------------------------------------------------------------------------------------------------
 template <typename T, bool DROP>
 __global__ __launch_bounds__(NT) void dkv_kernel(Params x) {
-  const AttnParams& p = x.a;
-  constexpr bool DBUF = Cfg<T>::DBUF;
-  constexpr int QT = Cfg<T>::QT, PITCH = D + Pad<T>::v, DB = D / 32, NBUF = DBUF ? 2 : 1;
-  __shared__ __attribute__((aligned(16))) T qs[NBUF][QT * PITCH];
-  __shared__ __attribute__((aligned(16))) T dos[NBUF][QT * PITCH];
-  __shared__ __attribute__((aligned(16))) float lse_s[NBUF][QT];
-  __shared__ __attribute__((aligned(16))) float dl_s[NBUF][QT];
-  constexpr bool FOLD = sizeof(T) == 2;
-  __shared__ __attribute__((aligned(16))) bf16_t ext_s[FOLD ? NBUF : 1][FOLD ? QT * 16 : 8];
-  __shared__ __attribute__((aligned(16))) bf16_t ext_d[FOLD ? NBUF : 1][FOLD ? QT * 16 : 8];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 31, h = lane >> 5;
-  const int64_t pairs = p.b * p.h, item = blockIdx.x;
-  const int64_t kt = item / pairs, bh = item % pairs;
-  const int64_t b = bh / p.h, hd = bh % p.h;
-  int64_t lq_, lk_, qbase, kbase, lse_base;
-  seq_view(p, b, hd, lq_, lk_, qbase, kbase, lse_base);
-  const int64_t k_tile0 = kt * BQ;
-  if (k_tile0 >= lk_) return;
-  int64_t kvlen = lk_;
-  if (p.kv_len) { kvlen = p.kv_len[b]; if (kvlen > lk_) kvlen = lk_; if (kvlen < 0) kvlen = 0; }
-  const int64_t key = k_tile0 + w * 32 + r;
-  const bool key_in = key < lk_;           // row exists in memory
-  const bool key_ok = key < kvlen;         // takes part in the softmax
-  const bool wave_live = k_tile0 + w * 32 < kvlen;   // else: staging helper only (dK = dV = 0)
-  const int64_t kr_ = key_in ? key : 0;
-  RowFrag<T, D> kf, vf;
-  kf.load(static_cast<const T*>(p.k) + (kbase + kr_) * p.k_stride + hd * D, key_in, h);
-  vf.load(static_cast<const T*>(p.v) + (kbase + kr_) * p.v_stride + hd * D, key_in, h);
-  const T* qg = static_cast<const T*>(p.q) + qbase * p.q_stride + hd * D;
-  const T* dog = static_cast<const T*>(p.dout) + qbase * x.dout_stride + hd * D;
-  const float* lse_g = p.lse + lse_base;
-  const float* dl_g = p.delta + lse_base;
-  const float sl2 = p.scale * kLog2e;
-  const uint32_t dk_u = drop_base(attn_seed(p), lse_base) + (uint32_t)(key >> 1) * kDropC2 + (uint32_t)(2 * h) * kDropC1;
-  const int k_odd = (int)(key & 1);
-  bf16x8 ones_k, ones_2;
-  if constexpr (FOLD) {
-#pragma unroll
-    for (int s_ = 0; s_ < D / 16; ++s_)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) kf.v[s_][j] = (__bf16)((float)kf.v[s_][j] * sl2);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { ones_k[j] = (__bf16)0.f; ones_2[j] = (__bf16)0.f; }
-    if (h == 0) {
-      ones_k[0] = ones_2[0] = (__bf16)1.f; ones_k[1] = ones_2[1] = (__bf16)1.f;
-      ones_k[2] = key_ok ? (__bf16)0.f : (__bf16)1.f;        // this lane's key is masked: its scores get -2^100
-    }
-  }
-  f32x16 dk[DB], dv[DB];
-#pragma unroll
-  for (int d = 0; d < DB; ++d)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) { dk[d][i] = 0.f; dv[d][i] = 0.f; }
-  if (k_tile0 < kvlen) {                                       // a workgroup wholly past kv_len has nothing to add
-    const int ntiles = (int)((lq_ + QT - 1) / QT);
-    TileRegs<T, D, QT, NT> qr, dor;
-    qr.init(p.q_stride, tid);
-    dor.init(x.dout_stride, tid);
-    float lr = 0.f, dr = 0.f;
-    auto load_tile = [&](int64_t q0) {
-      qr.load(qg, p.q_stride, q0, lq_, tid);
-      dor.load(dog, x.dout_stride, q0, lq_, tid);
-      if (tid < QT) {
-        const bool ok = q0 + tid < lq_;
-        lr = ok ? lse_g[q0 + tid] * kLog2e : INFINITY;     // +inf: probability 0 for a row past the sequence
-        dr = ok ? dl_g[q0 + tid] : 0.f;
-      }
-    };
-    auto store_tile = [&](int buf) {
-      qr.store(qs[buf], tid);
-      dor.store(dos[buf], tid);
-      if (tid < QT) {
-        lse_s[buf][tid] = lr; dl_s[buf][tid] = dr;
-        if constexpr (FOLD) {
-          const float l2 = lr < 0x1p100f ? lr : 0x1p100f;
-          const float lh = (float)(__bf16)l2, ll = (float)(__bf16)(l2 - lh);
-          const float dh = (float)(__bf16)dr, dlo = (float)(__bf16)(dr - dh);
-          bf16x8 es, ed, z;
-#pragma unroll
-          for (int j = 0; j < 8; ++j) { es[j] = (__bf16)0.f; ed[j] = (__bf16)0.f; z[j] = (__bf16)0.f; }
-          es[0] = (__bf16)(-lh); es[1] = (__bf16)(-ll); es[2] = (__bf16)(-0x1p100f);
-          ed[0] = (__bf16)(-dh); ed[1] = (__bf16)(-dlo);
-          *reinterpret_cast<bf16x8*>(&ext_s[buf][tid * 16]) = es;
-          *reinterpret_cast<bf16x8*>(&ext_s[buf][tid * 16 + 8]) = z;
-          *reinterpret_cast<bf16x8*>(&ext_d[buf][tid * 16]) = ed;
-          *reinterpret_cast<bf16x8*>(&ext_d[buf][tid * 16 + 8]) = z;
-        }
-      }
-    };
-    if (ntiles > 0) {
-      load_tile(0);
-      store_tile(0);
-    }
-    __syncthreads();
-    for (int t = 0; t < ntiles; ++t) {
-      const int64_t q0 = (int64_t)t * QT;
-      const int cur = DBUF ? (t & 1) : 0;
-      const bool more = t + 1 < ntiles;
-      if (DBUF && more) load_tile(q0 + QT);
-      if (wave_live) {
-        f32x16 s, dp;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) { s[i] = 0.f; dp[i] = 0.f; }
-        if constexpr (FOLD) {
-          const bf16x8 ea = *reinterpret_cast<const bf16x8*>(&ext_s[cur][r * 16 + 8 * h]);   // A row r = query r of the tile
-          s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ea, ones_k, s, 0, 0, 0);
-          if (!DROP) {
-            const bf16x8 da = *reinterpret_cast<const bf16x8*>(&ext_d[cur][r * 16 + 8 * h]);
-            dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(da, ones_2, dp, 0, 0, 0);
-          }
-        }
-        mma_rows<D>(qs[cur], PITCH, 0, kf, s, r, h);
-        mma_rows<D>(dos[cur], PITCH, 0, vf, dp, r, h);
-        if constexpr (FOLD && !DROP) {
-#pragma unroll
-          for (int i = 0; i < 16; ++i) {
-            const float pr = fast_exp2(s[i]);
-            s[i] = pr;
-            dp[i] = pr * dp[i];
-          }
-        } else {
-#pragma unroll
-          for (int g4 = 0; g4 < 4; ++g4) {
-            const int q4 = 8 * g4 + 4 * h;                         // registers 4*g4 .. 4*g4+3 = queries q0 + q4 .. + 3
-            const float4 l4 = *reinterpret_cast<const float4*>(&lse_s[cur][q4]);
-            const float4 d4 = *reinterpret_cast<const float4*>(&dl_s[cur][q4]);
-            const float lv[4] = {l4.x, l4.y, l4.z, l4.w}, dv4[4] = {d4.x, d4.y, d4.z, d4.w};
-#pragma unroll
-            for (int j2 = 0; j2 < 4; j2 += 2) {
-              const int i = 4 * g4 + j2;
-              const float p0 = FOLD ? fast_exp2(s[i]) : fast_exp2(key_ok ? fmaf(s[i], sl2, -lv[j2]) : -INFINITY);
-              const float p1 = FOLD ? fast_exp2(s[i + 1]) : fast_exp2(key_ok ? fmaf(s[i + 1], sl2, -lv[j2 + 1]) : -INFINITY);
-              float m0 = 1.f, m1 = 1.f;
-              if (DROP) drop_pair_k(dk_u + ((uint32_t)(q0 >> 1) + (uint32_t)((8 * g4 + j2) >> 1)) * kDropC1, k_odd, p.drop_thresh, p.keep_scale, m0, m1);
-              s[i] = p0 * m0;
-              s[i + 1] = p1 * m1;
-              dp[i] = p0 * (dp[i] * m0 - dv4[j2]);
-              dp[i + 1] = p1 * (dp[i + 1] * m1 - dv4[j2 + 1]);
-            }
-          }
-        }
-        mma_acc<D>(dos[cur], PITCH, 0, s, dv, lane);
-        mma_acc<D>(qs[cur], PITCH, 0, dp, dk, lane);
-      }
-      if (DBUF) {
-        if (more) store_tile(cur ^ 1);
-        __syncthreads();
-      } else if (more) {
-        __syncthreads();
-        load_tile(q0 + QT);
-        store_tile(0);
-        __syncthreads();
-      }
-    }
-  }
-  if (key_in) {
-    T* dkg = static_cast<T*>(p.dk) + (kbase + key) * p.dk_stride + hd * D;
-    T* dvg = static_cast<T*>(p.dv) + (kbase + key) * p.dv_stride + hd * D;
-#pragma unroll
-    for (int d = 0; d < DB; ++d) {
-      store_t<T>(dkg + d * 32, dk[d], p.scale, h);
-      store_t<T>(dvg + d * 32, dv[d], 1.f, h);
-    }
-  }
-}
-
-static inline uint32_t drop8(float pr) { long t = lroundf(pr * 256.f); return (uint32_t)(t < 0 ? 0 : (t > 255 ? 255 : t)); }
-
-static int stride_ok(const char* who, const char* what, const void* ptr, int64_t stride, int64_t min_stride, int dtype) {
-  const int v = dtype == GMLM_F32 ? 4 : 8;
-  GMLM_REQUIRE(ptr && aligned16(ptr), "%s: %s is null or not 16-byte aligned", who, what);
-  GMLM_REQUIRE(stride >= min_stride && stride % v == 0 && stride < (1 << 24),
-               "%s: %s row stride %ld must be >= %ld, < 2^24 and a multiple of %d", who, what, (long)stride, (long)min_stride, v);
-  return GMLM_OK;
+  const Item it = decode(x.a);
+  attn_dkv_body<T, D, NW, DROP, Cfg<T>::QT, Cfg<T>::DBUF>(x.a, it.tile, it.b, it.hd, x.dout_stride);
 }
 
 // host checks shared by the forward and the backward; fills the launch parameters
-static int setup(const char* who, Params& x, int64_t b, int64_t h, int64_t lq, int64_t lk, int64_t d, float dropout_p,
-                 const int32_t* kv_len, float scale, int dtype) {
+static int setup(const char* who, Params& x, const void* q, const void* k, const void* v, const int32_t* kv_len, int64_t b, int64_t h,
+                 int64_t lq, int64_t lk, int64_t d, int64_t q_stride, int64_t k_stride, int64_t v_stride, float scale, float dropout_p,
+                 uint64_t seed, const uint64_t* seed_dev, int dtype) {
   GMLM_REQUIRE(d == 128, "%s: head dim %ld not supported (this entry point takes 128)", who, (long)d);
   GMLM_REQUIRE(b >= 0 && h > 0 && lq >= 0 && lk >= 0, "%s: bad sizes", who);
   GMLM_REQUIRE(dtype == GMLM_F32 || dtype == GMLM_BF16, "%s: unsupported dtype", who);
@@ -539,10 +210,7 @@ static int setup(const char* who, Params& x, int64_t b, int64_t h, int64_t lq, i
   const int64_t rows = lq > lk ? lq : lk;
   GMLM_REQUIRE(cdiv(rows, BQ) * b * h < ((int64_t)1 << 31), "%s: too many work items", who);
   x = Params{};
-  AttnParams& p = x.a;
-  p.kv_len = kv_len;
-  p.b = b; p.h = h; p.lq = lq; p.lk = lk; p.scale = scale;
-  p.drop_thresh = drop8(dropout_p); p.keep_scale = 256.f / (256.f - (float)p.drop_thresh);
+  attn_fill(x.a, q, k, v, kv_len, b, h, lq, lk, q_stride, k_stride, v_stride, scale, dropout_p, seed, seed_dev);
   x.dout_stride = h * D;
   return GMLM_OK;
 }
@@ -571,23 +239,19 @@ extern "C" int gmlm_attention_d128_fwd(const void* q, const void* k, const void*
                                        void* out_lo, float* lse, int dtype, gmlm_stream_t stream) {
   static const char* who = "attention_d128_fwd";
   Params x;
-  int rc = setup(who, x, b, h, lq, lk, d, dropout_p, kv_len, scale, dtype);
+  int rc = setup(who, x, q, k, v, kv_len, b, h, lq, lk, d, q_stride, k_stride, v_stride, scale, dropout_p, seed, seed_dev, dtype);
   if (rc != GMLM_OK) return rc;
   GMLM_REQUIRE(!out_lo || (dtype == GMLM_BF16 && aligned16(out_lo)), "%s: out_lo is the bf16 residual of a bf16 output (16-byte aligned)", who);
   if (b == 0 || lq == 0) return GMLM_OK;
-  if ((rc = stride_ok(who, "q", q, q_stride, h * 128, dtype)) != GMLM_OK) return rc;
+  if ((rc = attn_stride_check(who, "q", q, q_stride, h * 128, dtype)) != GMLM_OK) return rc;
   if (lk > 0) {
-    if ((rc = stride_ok(who, "k", k, k_stride, h * 128, dtype)) != GMLM_OK) return rc;
-    if ((rc = stride_ok(who, "v", v, v_stride, h * 128, dtype)) != GMLM_OK) return rc;
+    if ((rc = attn_stride_check(who, "k", k, k_stride, h * 128, dtype)) != GMLM_OK) return rc;
+    if ((rc = attn_stride_check(who, "v", v, v_stride, h * 128, dtype)) != GMLM_OK) return rc;
   }
   GMLM_REQUIRE(out && aligned16(out), "%s: null or misaligned out", who);
-  AttnParams& p = x.a;
-  p.q = q; p.k = k; p.v = v; p.o_w = out; p.o_lo_w = out_lo; p.lse_w = lse;
-  p.q_stride = q_stride; p.k_stride = k_stride; p.v_stride = v_stride;
-  p.seed = seed; p.seed_dev = seed_dev;
-  x.ntiles = (uint32_t)cdiv(lq, BQ);
+  x.a.o_w = out; x.a.o_lo_w = out_lo; x.a.lse_w = lse;
   hipStream_t st = as_stream(stream);
-  const dim3 grid((unsigned)(x.ntiles * b * h));
+  const dim3 grid((unsigned)(cdiv(lq, BQ) * b * h));
   GMLM_D128_LAUNCH(fwd_kernel, grid, st, x);
   GMLM_LAUNCH_CHECK();
   return GMLM_OK;
@@ -605,29 +269,27 @@ extern "C" int gmlm_attention_d128_bwd(const void* q, const void* k, const void*
                                        void* workspace, size_t workspace_bytes, gmlm_stream_t stream) {
   static const char* who = "attention_d128_bwd";
   Params x;
-  int rc = setup(who, x, b, h, lq, lk, d, dropout_p, kv_len, scale, dtype);
+  int rc = setup(who, x, q, k, v, kv_len, b, h, lq, lk, d, q_stride, k_stride, v_stride, scale, dropout_p, seed, seed_dev, dtype);
   if (rc != GMLM_OK) return rc;
   GMLM_REQUIRE(!out_lo || (dtype == GMLM_BF16 && aligned16(out_lo)), "%s: out_lo is the bf16 residual of a bf16 output (16-byte aligned)", who);
   if (b == 0 || (lq == 0 && lk == 0)) return GMLM_OK;
   GMLM_REQUIRE(lq > 0 && lk > 0, "%s: empty query or key set with a non-empty counterpart is not supported", who);
-  if ((rc = stride_ok(who, "q", q, q_stride, h * 128, dtype)) != GMLM_OK) return rc;
-  if ((rc = stride_ok(who, "k", k, k_stride, h * 128, dtype)) != GMLM_OK) return rc;
-  if ((rc = stride_ok(who, "v", v, v_stride, h * 128, dtype)) != GMLM_OK) return rc;
-  if ((rc = stride_ok(who, "dq", dq, dq_stride, h * 128, dtype)) != GMLM_OK) return rc;
-  if ((rc = stride_ok(who, "dk", dk, dk_stride, h * 128, dtype)) != GMLM_OK) return rc;
-  if ((rc = stride_ok(who, "dv", dv, dv_stride, h * 128, dtype)) != GMLM_OK) return rc;
+  if ((rc = attn_stride_check(who, "q", q, q_stride, h * 128, dtype)) != GMLM_OK) return rc;
+  if ((rc = attn_stride_check(who, "k", k, k_stride, h * 128, dtype)) != GMLM_OK) return rc;
+  if ((rc = attn_stride_check(who, "v", v, v_stride, h * 128, dtype)) != GMLM_OK) return rc;
+  if ((rc = attn_stride_check(who, "dq", dq, dq_stride, h * 128, dtype)) != GMLM_OK) return rc;
+  if ((rc = attn_stride_check(who, "dk", dk, dk_stride, h * 128, dtype)) != GMLM_OK) return rc;
+  if ((rc = attn_stride_check(who, "dv", dv, dv_stride, h * 128, dtype)) != GMLM_OK) return rc;
   GMLM_REQUIRE(out && dout && lse && aligned16(out) && aligned16(dout), "%s: null or misaligned out/dout/lse", who);
   if (!workspace || workspace_bytes < gmlm_attention_d128_workspace_bytes(b, h, lq)) {
     set_error("%s: workspace too small", who);
     return GMLM_EWORKSPACE;
   }
   AttnParams& p = x.a;
-  p.q = q; p.k = k; p.v = v; p.out = out; p.out_lo = out_lo; p.dout = dout; p.lse = lse;
+  p.out = out; p.out_lo = out_lo; p.dout = dout; p.lse = lse;
   p.delta = static_cast<float*>(workspace);
   p.dq = dq; p.dk = dk; p.dv = dv;
-  p.q_stride = q_stride; p.k_stride = k_stride; p.v_stride = v_stride;
   p.dq_stride = dq_stride; p.dk_stride = dk_stride; p.dv_stride = dv_stride;
-  p.seed = seed; p.seed_dev = seed_dev;
   hipStream_t st = as_stream(stream);
   const int64_t rows = b * lq * h;
   if (dtype == GMLM_BF16)
@@ -635,12 +297,10 @@ extern "C" int gmlm_attention_d128_bwd(const void* q, const void* k, const void*
   else
     delta_kernel<float><<<(unsigned)cdiv(rows * 32, 256), 256, 0, st>>>((const float*)out, nullptr, (const float*)dout, rows, lq, h, p.delta);
   GMLM_LAUNCH_CHECK();
-  x.ntiles = (uint32_t)cdiv(lq, BQ);
-  const dim3 gq((unsigned)(x.ntiles * b * h));
+  const dim3 gq((unsigned)(cdiv(lq, BQ) * b * h));
   GMLM_D128_LAUNCH(dq_kernel, gq, st, x);
   GMLM_LAUNCH_CHECK();
-  x.ntiles = (uint32_t)cdiv(lk, BQ);
-  const dim3 gk((unsigned)(x.ntiles * b * h));
+  const dim3 gk((unsigned)(cdiv(lk, BQ) * b * h));
   GMLM_D128_LAUNCH(dkv_kernel, gk, st, x);
   GMLM_LAUNCH_CHECK();
   return GMLM_OK;

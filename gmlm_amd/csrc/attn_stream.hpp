@@ -1,0 +1,531 @@
+// Device bodies of the streaming attention kernels (K5/K7): forward, delta, dQ and dK/dV, written once for every head dim.
+// The __global__ entry points of attn_kernels.hip (d = 64 / 96, two-dimensional grids) and attn_d128.hip (d = 128, 1-D grids)
+// decode their grid into (tile, b, hd) and call one of these; tile sizes and the double-buffer switch are template arguments.
+//   tile     : index of the workgroup's block of NW * 32 query rows (forward, dQ) or key rows (dK/dV)
+//   b, hd    : batch (or packed sequence) and head
+//   o_stride : row stride of out / out_lo / dout in elements (h * D)
+#pragma once
+#include "attn_common.hpp"
+
+namespace gmlm {
+
+// ------------------------------------------------------------------------------------------------
+// forward
+// ------------------------------------------------------------------------------------------------
+template <typename T, int D, int NW, bool DROP, int KT, bool DBUF>
+__device__ __forceinline__ void attn_fwd_body(const AttnParams& p, int64_t tile, int64_t b, int64_t hd, int64_t o_stride) {
+  constexpr int KB = KT / 32, NT = NW * 64, PITCH = D + Pad<T>::v, DB = D / 32, NBUF = DBUF ? 2 : 1;
+  __shared__ __attribute__((aligned(16))) T ks[NBUF][KT * PITCH];
+  __shared__ __attribute__((aligned(16))) T vs[NBUF][KT * PITCH];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 31, h = lane >> 5;
+  int64_t lq_, lk_, qbase, kbase, lse_base;
+  seq_view(p, b, hd, lq_, lk_, qbase, kbase, lse_base);
+  if (tile * (NW * 32) >= (false ? lk_ : lq_)) return;   // varlen: tile past this sequence (block-uniform)
+  const int64_t q_row = tile * (NW * 32) + w * 32 + r;
+  const bool q_ok = q_row < lq_;
+  // a wave whose 32 queries all lie past the sequence (short packed sequences) only helps staging K/V
+  const bool wave_live = tile * (NW * 32) + w * 32 < lq_;
+  int64_t kvlen = lk_;
+  if (p.kv_len) { kvlen = p.kv_len[b]; if (kvlen > lk_) kvlen = lk_; if (kvlen < 0) kvlen = 0; }
+  const T* qg = static_cast<const T*>(p.q) + (qbase + (q_ok ? q_row : 0)) * p.q_stride + hd * D;
+  const T* kg = static_cast<const T*>(p.k) + kbase * p.k_stride + hd * D;
+  const T* vg = static_cast<const T*>(p.v) + kbase * p.v_stride + hd * D;
+  RowFrag<T, D> qf;
+  qf.load(qg, q_ok, h);
+  f32x16 o[DB];
+#pragma unroll
+  for (int d = 0; d < DB; ++d)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) o[d][i] = 0.f;
+  float m = -INFINITY, l = 0.f;              // running max / sum in the log2 domain (scores * scale * log2 e)
+  const float sl2 = p.scale * kLog2e;
+  // dropout hash input of this lane's query (+ 2h: the lane half's keys sit 4 further on, i.e. 2 key pairs)
+  const uint32_t dq_u = drop_base(attn_seed(p), lse_base) + (uint32_t)(q_row >> 1) * kDropC1 + (uint32_t)(2 * h) * kDropC2;
+  const int q_odd = (int)(q_row & 1);
+  const int ntiles = (int)((kvlen + KT - 1) / KT);
+  TileRegs<T, D, KT, NT> kr, vr;
+  kr.init(p.k_stride, tid);
+  vr.init(p.v_stride, tid);
+  if (ntiles > 0) {
+    kr.load(kg, p.k_stride, 0, lk_, tid);
+    vr.load(vg, p.v_stride, 0, lk_, tid);
+    kr.store(ks[0], tid);
+    vr.store(vs[0], tid);
+  }
+  __syncthreads();
+  for (int t = 0; t < ntiles; ++t) {
+    const int64_t kv0 = (int64_t)t * KT;
+    const int cur = DBUF ? (t & 1) : 0;
+    const bool more = t + 1 < ntiles;
+    if (DBUF && more) {
+      kr.load(kg, p.k_stride, kv0 + KT, lk_, tid);
+      vr.load(vg, p.v_stride, kv0 + KT, lk_, tid);
+    }
+    if (wave_live) {
+    f32x16 s[KB];
+#pragma unroll
+    for (int kb = 0; kb < KB; ++kb) {
+#pragma unroll
+      for (int i = 0; i < 16; ++i) s[kb][i] = 0.f;
+      mma_rows<D>(ks[cur], PITCH, kb * 32, qf, s[kb], r, h);
+    }
+    float rmax = -INFINITY;
+    if (kv0 + KT <= kvlen) {                        // whole tile valid (block-uniform): no per-key compare
+#pragma unroll
+      for (int kb = 0; kb < KB; ++kb)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) rmax = fmaxf(rmax, s[kb][i]);
+    } else {
+#pragma unroll
+      for (int kb = 0; kb < KB; ++kb)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          const int64_t key = kv0 + kb * 32 + acc_row(i, h);
+          const float v = key < kvlen ? s[kb][i] : -INFINITY;
+          s[kb][i] = v;
+          rmax = fmaxf(rmax, v);
+        }
+    }
+    rmax = xhalf_max(rmax);
+    // deferred rescale: keep the old reference max while the new one exceeds it by < 2^kDefer (probabilities
+    // then stay <= 2^kDefer, harmless in fp32 / bf16); the O and l rescale is skipped for the whole wave then
+    float m_new = fmaxf(m, rmax * sl2);             // finite: key kv0 is always valid
+    const bool keep = __all(m_new - m <= kDefer);   // m = -inf (first tile) -> false
+    float alpha = 1.f;
+    if (keep) m_new = m;
+    else alpha = fast_exp2(m - m_new);              // m = -inf -> 0
+    float rsum = 0.f;
+#pragma unroll
+    for (int kb = 0; kb < KB; ++kb)
+#pragma unroll
+      for (int i = 0; i < 16; i += 2) {
+        const float e0 = fast_exp2(fmaf(s[kb][i], sl2, -m_new));       // masked: exp2(-inf) = 0
+        const float e1 = fast_exp2(fmaf(s[kb][i + 1], sl2, -m_new));
+        rsum += e0 + e1;                                               // the normaliser uses the un-dropped probabilities
+        if (DROP) {
+          float m0, m1;                                // keys (k, k+1): (kv0 + kb*32 + acc_row(i, 0)) >> 1 pairs on from the tile start
+          drop_pair_q(dq_u + ((uint32_t)(t * (KT / 2)) + (uint32_t)((kb * 32 + acc_row(i, 0)) >> 1)) * kDropC2, q_odd, p.drop_thresh, p.keep_scale, m0, m1);
+          s[kb][i] = e0 * m0;
+          s[kb][i + 1] = e1 * m1;
+        } else {
+          s[kb][i] = e0;
+          s[kb][i + 1] = e1;
+        }
+      }
+    rsum = xhalf_sum(rsum);
+    l = l * alpha + rsum;
+    m = m_new;
+    if (!keep) {
+#pragma unroll
+      for (int d = 0; d < DB; ++d)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) o[d][i] *= alpha;
+    }
+#pragma unroll
+    for (int kb = 0; kb < KB; ++kb) mma_acc<D>(vs[cur], PITCH, kb * 32, s[kb], o, lane);
+    }
+    if (DBUF) {
+      if (more) {
+        kr.store(ks[cur ^ 1], tid);
+        vr.store(vs[cur ^ 1], tid);
+      }
+      __syncthreads();
+    } else if (more) {
+      __syncthreads();
+      kr.load(kg, p.k_stride, kv0 + KT, lk_, tid);
+      vr.load(vg, p.v_stride, kv0 + KT, lk_, tid);
+      kr.store(ks[0], tid);
+      vr.store(vs[0], tid);
+      __syncthreads();
+    }
+  }
+  if (q_ok) {
+    const float inv = l > 0.f ? 1.f / l : 0.f;
+    T* og = static_cast<T*>(p.o_w) + (qbase + q_row) * o_stride + hd * D;
+#pragma unroll
+    for (int d = 0; d < DB; ++d) store_t<T>(og + d * 32, o[d], inv, h);
+    if constexpr (sizeof(T) == 2) {
+      if (p.o_lo_w) {
+        T* olg = static_cast<T*>(p.o_lo_w) + (qbase + q_row) * o_stride + hd * D;
+#pragma unroll
+        for (int d = 0; d < DB; ++d) store_t_lo(olg + d * 32, o[d], inv, h);
+      }
+    }
+    if (h == 0 && p.lse_w) p.lse_w[lse_base + q_row] = l > 0.f ? (m + __log2f(l)) * kLn2 : -INFINITY;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// backward: delta[b,h,q] = sum_d dO * O   (O = o + o_lo when the forward stored the bf16 residual of its output)
+// ------------------------------------------------------------------------------------------------
+// a group of d/V lanes owns one (b, q, h) row: the wave reads 64 x 16 contiguous bytes per instruction
+template <typename T>
+__device__ __forceinline__ void attn_delta_body(const T* __restrict__ o, const T* __restrict__ o_lo, const T* __restrict__ dout,
+                                                int64_t rows /* b*lq*h */, int d, int64_t lq, int64_t hn,
+                                                float* __restrict__ delta) {
+  constexpr int V = Store<T>::kVec;
+  const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int lanes = d / V <= 8 ? 8 : (d / V <= 16 ? 16 : 32);
+  const int64_t row = gid / lanes;
+  const int c = (int)(gid % lanes);
+  float acc = 0.f;
+  if (row < rows && c < d / V) {
+    float a[V], g[V];
+    Store<T>::ldv(o + row * d + c * V, a);
+    Store<T>::ldv(dout + row * d + c * V, g);
+    if (o_lo) {
+      float al[V];
+      Store<T>::ldv(o_lo + row * d + c * V, al);
+#pragma unroll
+      for (int v = 0; v < V; ++v) a[v] += al[v];
+    }
+#pragma unroll
+    for (int v = 0; v < V; ++v) acc += a[v] * g[v];
+  }
+  for (int off = lanes >> 1; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+  if (row < rows && c == 0) {
+    const int64_t hd = row % hn, bq = row / hn, q = bq % lq, b = bq / lq;
+    delta[(b * hn + hd) * lq + q] = acc;         // packed mode passes b = 1, lq = total rows: [h, total_rows]
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// backward: dQ.  workgroup = NW*32 queries, loop over key tiles.
+//   S^T = K Q^T, P^T = exp(scale*S^T - lse[q]), dP^T = V dO^T, dS^T = P^T*(dP^T - delta[q]),
+//   dQ^T += K^T dS^T  (all with the query on the lane)
+// ------------------------------------------------------------------------------------------------
+// d128::dq_kernel (attn_d128.hip) keeps a copy of this text for its register budget: a change here belongs there too.
+template <typename T, int D, int NW, bool DROP, int KT, bool DBUF>
+__device__ __forceinline__ void attn_dq_body(const AttnParams& p, int64_t tile, int64_t b, int64_t hd, int64_t o_stride) {
+  constexpr int KB = KT / 32, NT = NW * 64, PITCH = D + Pad<T>::v, DB = D / 32, NBUF = DBUF ? 2 : 1;
+  __shared__ __attribute__((aligned(16))) T ks[NBUF][KT * PITCH];
+  __shared__ __attribute__((aligned(16))) T vs[NBUF][KT * PITCH];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 31, h = lane >> 5;
+  int64_t lq_, lk_, qbase, kbase, lse_base;
+  seq_view(p, b, hd, lq_, lk_, qbase, kbase, lse_base);
+  if (tile * (NW * 32) >= (false ? lk_ : lq_)) return;   // varlen: tile past this sequence (block-uniform)
+  const int64_t q_row = tile * (NW * 32) + w * 32 + r;
+  const bool q_ok = q_row < lq_;
+  const bool wave_live = tile * (NW * 32) + w * 32 < lq_;   // else: staging helper only
+  int64_t kvlen = lk_;
+  if (p.kv_len) { kvlen = p.kv_len[b]; if (kvlen > lk_) kvlen = lk_; if (kvlen < 0) kvlen = 0; }
+  const int64_t qr = q_ok ? q_row : 0;
+  const T* kg = static_cast<const T*>(p.k) + kbase * p.k_stride + hd * D;
+  const T* vg = static_cast<const T*>(p.v) + kbase * p.v_stride + hd * D;
+  RowFrag<T, D> qf, dof;
+  qf.load(static_cast<const T*>(p.q) + (qbase + qr) * p.q_stride + hd * D, q_ok, h);
+  dof.load(static_cast<const T*>(p.dout) + (qbase + qr) * o_stride + hd * D, q_ok, h);
+  const float sl2 = p.scale * kLog2e;
+  const float lse2 = q_ok ? p.lse[lse_base + q_row] * kLog2e : INFINITY;
+  const float dl = q_ok ? p.delta[lse_base + q_row] : 0.f;
+  const int kvl = (int)(kvlen < (1 << 30) ? kvlen : (1 << 30));
+  const uint32_t dq_u = drop_base(attn_seed(p), lse_base) + (uint32_t)(q_row >> 1) * kDropC1 + (uint32_t)(2 * h) * kDropC2;
+  const int q_odd = (int)(q_row & 1);
+  // bf16: the per-score fma / compare / select work rides in the MFMA chains (as in the pipelined forward).  Q is
+  // pre-multiplied by scale * log2 e (the SAME rounding the forward applies), and each chain starts with one extra
+  // contraction step  [1 1 m 0 ..] x [-lse_hi -lse_lo -2^100 0 ..]^T  (m = 1 for a masked key): scores leave the
+  // chain as s*scale*log2e - lse, masked keys at about -1.3e30, so P = exp2(.) with no further arithmetic; without
+  // dropout the dP chain starts from  [1 1 0 ..] x [-delta_hi -delta_lo 0 ..]^T  and dS = P * (dP - delta) is one multiply.
+  // lse / delta are split into two bf16 terms (hi + lo: relative error 2^-17).
+  constexpr bool FOLD = sizeof(T) == 2;
+  bf16x8 ones_a, ext_s, ext_dp;
+  if constexpr (FOLD) {
+#pragma unroll
+    for (int s_ = 0; s_ < D / 16; ++s_)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) qf.v[s_][j] = (__bf16)((float)qf.v[s_][j] * sl2);
+    const float l2 = q_ok ? lse2 : 0x1p100f;                 // a row past the sequence: probability 0 everywhere
+    const float lh = (float)(__bf16)l2, ll = (float)(__bf16)(l2 - lh);
+    const float dh = (float)(__bf16)dl, dlo = (float)(__bf16)(dl - dh);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { ones_a[j] = (__bf16)0.f; ext_s[j] = (__bf16)0.f; ext_dp[j] = (__bf16)0.f; }
+    if (h == 0) {
+      ones_a[0] = (__bf16)1.f; ones_a[1] = (__bf16)1.f;
+      ext_s[0] = (__bf16)(-lh); ext_s[1] = (__bf16)(-ll); ext_s[2] = (__bf16)(-0x1p100f);
+      ext_dp[0] = (__bf16)(-dh); ext_dp[1] = (__bf16)(-dlo);
+    }
+  }
+  f32x16 dq[DB];
+#pragma unroll
+  for (int d = 0; d < DB; ++d)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) dq[d][i] = 0.f;
+  const int ntiles = (int)((kvlen + KT - 1) / KT);
+  TileRegs<T, D, KT, NT> kr, vr;
+  kr.init(p.k_stride, tid);
+  vr.init(p.v_stride, tid);
+  if (ntiles > 0) {
+    kr.load(kg, p.k_stride, 0, lk_, tid);
+    vr.load(vg, p.v_stride, 0, lk_, tid);
+    kr.store(ks[0], tid);
+    vr.store(vs[0], tid);
+  }
+  __syncthreads();
+  for (int t = 0; t < ntiles; ++t) {
+    const int64_t kv0 = (int64_t)t * KT;
+    const int cur = DBUF ? (t & 1) : 0;
+    const bool more = t + 1 < ntiles;
+    if (DBUF && more) {
+      kr.load(kg, p.k_stride, kv0 + KT, lk_, tid);
+      vr.load(vg, p.v_stride, kv0 + KT, lk_, tid);
+    }
+    if (wave_live) {
+#pragma unroll
+    for (int kb = 0; kb < KB; ++kb) {
+      f32x16 s, dp;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) { s[i] = 0.f; dp[i] = 0.f; }
+      const bool full = kv0 + (kb + 1) * 32 <= kvlen;          // block-uniform
+      if constexpr (FOLD) {
+        bf16x8 oa = ones_a;
+        // only a sequence's last key block is partial.  Without the hint the fix-up is speculated and the KB key blocks fuse into
+        // one region: d = 64, 4 waves 166 -> 200 VGPRs, 3 -> 2 waves per SIMD (guard: test_streaming_dq_mfma_chains_stay_per_key_block)
+        if (__builtin_expect(!full, 0)) oa[2] = (h == 0 && (int)kv0 + kb * 32 + r >= kvl) ? (__bf16)1.f : (__bf16)0.f;   // A row r = key r of the block
+        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(oa, ext_s, s, 0, 0, 0);
+        if (!DROP) dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ones_a, ext_dp, dp, 0, 0, 0);
+      }
+      mma_rows<D>(ks[cur], PITCH, kb * 32, qf, s, r, h);
+      mma_rows<D>(vs[cur], PITCH, kb * 32, dof, dp, r, h);
+#pragma unroll
+      for (int i = 0; i < 16; i += 2) {
+        float p0, p1;
+        if constexpr (FOLD) {
+          p0 = fast_exp2(s[i]);
+          p1 = fast_exp2(s[i + 1]);
+        } else {
+          const int key = (int)kv0 + kb * 32 + acc_row(i, h);      // even; registers i, i+1 = keys key, key+1
+          // a masked key gets exponent -inf through a select (no branch around the exp); whole blocks skip the test;
+          // a query row past the sequence has lse = +inf, i.e. probability 0 everywhere
+          float a0 = fmaf(s[i], sl2, -lse2), a1 = fmaf(s[i + 1], sl2, -lse2);
+          if (!full) { a0 = key < kvl ? a0 : -INFINITY; a1 = key + 1 < kvl ? a1 : -INFINITY; }
+          p0 = fast_exp2(a0); p1 = fast_exp2(a1);
+        }
+        if (FOLD && !DROP) {
+          s[i] = p0 * dp[i];
+          s[i + 1] = p1 * dp[i + 1];
+        } else {
+          float m0 = 1.f, m1 = 1.f;
+          if (DROP) drop_pair_q(dq_u + ((uint32_t)(t * (KT / 2)) + (uint32_t)((kb * 32 + acc_row(i, 0)) >> 1)) * kDropC2, q_odd, p.drop_thresh, p.keep_scale, m0, m1);
+          s[i] = p0 * (dp[i] * m0 - dl);
+          s[i + 1] = p1 * (dp[i + 1] * m1 - dl);
+        }
+      }
+      mma_acc<D>(ks[cur], PITCH, kb * 32, s, dq, lane);
+    }
+    }
+    if (DBUF) {
+      if (more) {
+        kr.store(ks[cur ^ 1], tid);
+        vr.store(vs[cur ^ 1], tid);
+      }
+      __syncthreads();
+    } else if (more) {
+      __syncthreads();
+      kr.load(kg, p.k_stride, kv0 + KT, lk_, tid);
+      vr.load(vg, p.v_stride, kv0 + KT, lk_, tid);
+      kr.store(ks[0], tid);
+      vr.store(vs[0], tid);
+      __syncthreads();
+    }
+  }
+  if (q_ok) {
+    T* og = static_cast<T*>(p.dq) + (qbase + q_row) * p.dq_stride + hd * D;
+#pragma unroll
+    for (int d = 0; d < DB; ++d) store_t<T>(og + d * 32, dq[d], p.scale, h);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// backward: dK, dV.  workgroup = 128 keys (32 per wave), loop over query tiles of 32.
+//   S = Q K^T, P = exp(scale*S - lse[q]), dV^T += dO^T P, dP = dO V^T, dS = P*(dP - delta[q]),
+//   dK^T += Q^T dS   (all with the key on the lane, the query in the accumulator registers)
+// ------------------------------------------------------------------------------------------------
+// QT = query rows staged per barrier: 32 or 64 with two LDS buffers (long sequences: loads of tile t+1 under the MFMAs
+// of tile t), or 128 in one buffer for sequences of <= 128 tokens (the whole sequence behind ONE barrier: at
+// 16-128 tokens the per-tile barrier / LDS round trip, not the MFMA work, sets the block's lifetime).
+template <typename T, int D, int NW, bool DROP, int QT, bool DBUF>
+__device__ __forceinline__ void attn_dkv_body(const AttnParams& p, int64_t tile, int64_t b, int64_t hd, int64_t o_stride) {
+  constexpr int NT = NW * 64, PITCH = D + Pad<T>::v, DB = D / 32, NBUF = DBUF ? 2 : 1;
+  __shared__ __attribute__((aligned(16))) T qs[NBUF][QT * PITCH];
+  __shared__ __attribute__((aligned(16))) T dos[NBUF][QT * PITCH];
+  __shared__ __attribute__((aligned(16))) float lse_s[NBUF][QT];
+  __shared__ __attribute__((aligned(16))) float dl_s[NBUF][QT];
+  // bf16: per query row, the A fragments of the extra contraction steps (see attn_dq_body): 16 elements each,
+  // [-lse_hi -lse_lo -2^100 0 x 13] and [-delta_hi -delta_lo 0 x 14]; the key side holds [1 1 masked 0 ..] in registers
+  constexpr bool FOLD = sizeof(T) == 2;
+  __shared__ __attribute__((aligned(16))) bf16_t ext_s[FOLD ? NBUF : 1][FOLD ? QT * 16 : 8];
+  __shared__ __attribute__((aligned(16))) bf16_t ext_d[FOLD ? NBUF : 1][FOLD ? QT * 16 : 8];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 31, h = lane >> 5;
+  int64_t lq_, lk_, qbase, kbase, lse_base;
+  seq_view(p, b, hd, lq_, lk_, qbase, kbase, lse_base);
+  if (tile * (NW * 32) >= (true ? lk_ : lq_)) return;   // varlen: tile past this sequence (block-uniform)
+  int64_t kvlen = lk_;
+  if (p.kv_len) { kvlen = p.kv_len[b]; if (kvlen > lk_) kvlen = lk_; if (kvlen < 0) kvlen = 0; }
+  const int64_t key = tile * (NW * 32) + w * 32 + r;
+  const bool key_in = key < lk_;           // row exists in memory
+  const bool key_ok = key < kvlen;          // takes part in the softmax
+  const bool wave_live = tile * (NW * 32) + w * 32 < kvlen;   // else: staging helper only (dK = dV = 0)
+  const int64_t kr_ = key_in ? key : 0;
+  RowFrag<T, D> kf, vf;
+  kf.load(static_cast<const T*>(p.k) + (kbase + kr_) * p.k_stride + hd * D, key_in, h);
+  vf.load(static_cast<const T*>(p.v) + (kbase + kr_) * p.v_stride + hd * D, key_in, h);
+  const T* qg = static_cast<const T*>(p.q) + qbase * p.q_stride + hd * D;
+  const T* dog = static_cast<const T*>(p.dout) + qbase * o_stride + hd * D;
+  const float* lse_g = p.lse + lse_base;
+  const float* dl_g = p.delta + lse_base;
+  const float sl2 = p.scale * kLog2e;
+  const uint32_t dk_u = drop_base(attn_seed(p), lse_base) + (uint32_t)(key >> 1) * kDropC2 + (uint32_t)(2 * h) * kDropC1;   // + 2h: the lane half's queries sit 4 further on
+  const int k_odd = (int)(key & 1);
+  bf16x8 ones_k, ones_2;
+  if constexpr (FOLD) {
+    // K' = bf16(K * scale * log2 e) (one more bf16 rounding, the size of the one the forward applies to Q)
+#pragma unroll
+    for (int s_ = 0; s_ < D / 16; ++s_)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) kf.v[s_][j] = (__bf16)((float)kf.v[s_][j] * sl2);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { ones_k[j] = (__bf16)0.f; ones_2[j] = (__bf16)0.f; }
+    if (h == 0) {
+      ones_k[0] = ones_2[0] = (__bf16)1.f; ones_k[1] = ones_2[1] = (__bf16)1.f;
+      ones_k[2] = key_ok ? (__bf16)0.f : (__bf16)1.f;        // this lane's key is masked: its scores get -2^100
+    }
+  }
+  f32x16 dk[DB], dv[DB];
+#pragma unroll
+  for (int d = 0; d < DB; ++d)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) { dk[d][i] = 0.f; dv[d][i] = 0.f; }
+  // a whole workgroup past kv_len has nothing to accumulate (block-uniform condition)
+  const bool block_live = tile * (NW * 32) < kvlen;
+  if (block_live) {
+    const int ntiles = (int)((lq_ + QT - 1) / QT);
+    TileRegs<T, D, QT, NT> qr, dor;
+    qr.init(p.q_stride, tid);
+    dor.init(o_stride, tid);
+    float lr = 0.f, dr = 0.f;
+    auto load_small = [&](int64_t q0) {
+      if (tid < QT) {
+        const bool ok = q0 + tid < lq_;
+        lr = ok ? lse_g[q0 + tid] * kLog2e : INFINITY;     // +inf: probability 0 for a row past the sequence
+        dr = ok ? dl_g[q0 + tid] : 0.f;
+      }
+    };
+    auto store_small = [&](int buf) {
+      if (tid < QT) {
+        lse_s[buf][tid] = lr; dl_s[buf][tid] = dr;
+        if constexpr (FOLD) {
+          const float l2 = lr < 0x1p100f ? lr : 0x1p100f;            // +inf (row past the sequence): probability 0
+          const float lh = (float)(__bf16)l2, ll = (float)(__bf16)(l2 - lh);
+          const float dh = (float)(__bf16)dr, dlo = (float)(__bf16)(dr - dh);
+          bf16x8 es, ed, z;
+#pragma unroll
+          for (int j = 0; j < 8; ++j) { es[j] = (__bf16)0.f; ed[j] = (__bf16)0.f; z[j] = (__bf16)0.f; }
+          es[0] = (__bf16)(-lh); es[1] = (__bf16)(-ll); es[2] = (__bf16)(-0x1p100f);
+          ed[0] = (__bf16)(-dh); ed[1] = (__bf16)(-dlo);
+          *reinterpret_cast<bf16x8*>(&ext_s[buf][tid * 16]) = es;
+          *reinterpret_cast<bf16x8*>(&ext_s[buf][tid * 16 + 8]) = z;
+          *reinterpret_cast<bf16x8*>(&ext_d[buf][tid * 16]) = ed;
+          *reinterpret_cast<bf16x8*>(&ext_d[buf][tid * 16 + 8]) = z;
+        }
+      }
+    };
+    if (ntiles > 0) {
+      qr.load(qg, p.q_stride, 0, lq_, tid);
+      dor.load(dog, o_stride, 0, lq_, tid);
+      load_small(0);
+      qr.store(qs[0], tid);
+      dor.store(dos[0], tid);
+      store_small(0);
+    }
+    __syncthreads();
+    for (int t = 0; t < ntiles; ++t) {
+      const int64_t q0 = (int64_t)t * QT;
+      const int cur = DBUF ? (t & 1) : 0;
+      const bool more = t + 1 < ntiles;
+      if (DBUF && more) {
+        qr.load(qg, p.q_stride, q0 + QT, lq_, tid);
+        dor.load(dog, o_stride, q0 + QT, lq_, tid);
+        load_small(q0 + QT);
+      }
+      if (wave_live) {
+#pragma unroll
+      for (int qb = 0; qb < QT / 32; ++qb) {
+        if (QT > 32 && q0 + qb * 32 >= lq_) break;            // block-uniform
+        f32x16 s, dp;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) { s[i] = 0.f; dp[i] = 0.f; }
+        if constexpr (FOLD) {
+          const bf16x8 ea = *reinterpret_cast<const bf16x8*>(&ext_s[cur][(qb * 32 + r) * 16 + 8 * h]);   // A row r = query r of the block
+          s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ea, ones_k, s, 0, 0, 0);
+          if (!DROP) {
+            const bf16x8 da = *reinterpret_cast<const bf16x8*>(&ext_d[cur][(qb * 32 + r) * 16 + 8 * h]);
+            dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(da, ones_2, dp, 0, 0, 0);
+          }
+        }
+        mma_rows<D>(qs[cur], PITCH, qb * 32, kf, s, r, h);
+        mma_rows<D>(dos[cur], PITCH, qb * 32, vf, dp, r, h);
+        if constexpr (FOLD && !DROP) {
+#pragma unroll
+          for (int i = 0; i < 16; ++i) {
+            const float pr = fast_exp2(s[i]);
+            s[i] = pr;
+            dp[i] = pr * dp[i];
+          }
+        } else {
+#pragma unroll
+        for (int g4 = 0; g4 < 4; ++g4) {
+          const int q4 = qb * 32 + 8 * g4 + 4 * h;       // accumulator registers 4*g4 .. 4*g4+3 = queries q4 .. q4+3
+          const float4 l4 = *reinterpret_cast<const float4*>(&lse_s[cur][q4]);
+          const float4 d4 = *reinterpret_cast<const float4*>(&dl_s[cur][q4]);
+          const float lv[4] = {l4.x, l4.y, l4.z, l4.w}, dv4[4] = {d4.x, d4.y, d4.z, d4.w};
+#pragma unroll
+          for (int j = 0; j < 4; j += 2) {
+            const int i = 4 * g4 + j;                        // registers i, i+1 = queries q0 + q4 + j, + 1 (even, odd)
+            // query rows past the sequence carry lse = +inf in LDS, masked keys select the exponent -inf: both give
+            // probability exactly 0 without a branch around the exp
+            const float p0 = FOLD ? fast_exp2(s[i]) : fast_exp2(key_ok ? fmaf(s[i], sl2, -lv[j]) : -INFINITY);
+            const float p1 = FOLD ? fast_exp2(s[i + 1]) : fast_exp2(key_ok ? fmaf(s[i + 1], sl2, -lv[j + 1]) : -INFINITY);
+            float m0 = 1.f, m1 = 1.f;
+            if (DROP) drop_pair_k(dk_u + ((uint32_t)(q0 >> 1) + (uint32_t)((qb * 32 + 8 * g4 + j) >> 1)) * kDropC1, k_odd, p.drop_thresh, p.keep_scale, m0, m1);
+            s[i] = p0 * m0;
+            s[i + 1] = p1 * m1;
+            dp[i] = p0 * (dp[i] * m0 - dv4[j]);
+            dp[i + 1] = p1 * (dp[i + 1] * m1 - dv4[j + 1]);
+          }
+        }
+        }
+        mma_acc<D>(dos[cur], PITCH, qb * 32, s, dv, lane);
+        mma_acc<D>(qs[cur], PITCH, qb * 32, dp, dk, lane);
+      }
+      }
+      if (DBUF) {
+        if (more) {
+          qr.store(qs[cur ^ 1], tid);
+          dor.store(dos[cur ^ 1], tid);
+          store_small(cur ^ 1);
+        }
+        __syncthreads();
+      } else if (more) {
+        __syncthreads();
+        qr.load(qg, p.q_stride, q0 + QT, lq_, tid);
+        dor.load(dog, o_stride, q0 + QT, lq_, tid);
+        load_small(q0 + QT);
+        qr.store(qs[0], tid);
+        dor.store(dos[0], tid);
+        store_small(0);
+        __syncthreads();
+      }
+    }
+  }
+  if (key_in) {
+    T* dkg = static_cast<T*>(p.dk) + (kbase + key) * p.dk_stride + hd * D;
+    T* dvg = static_cast<T*>(p.dv) + (kbase + key) * p.dv_stride + hd * D;
+#pragma unroll
+    for (int d = 0; d < DB; ++d) {
+      store_t<T>(dkg + d * 32, dk[d], p.scale, h);
+      store_t<T>(dvg + d * 32, dv[d], 1.f, h);
+    }
+  }
+}
+
+}  // namespace gmlm

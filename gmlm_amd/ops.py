@@ -425,40 +425,6 @@ def _short_path(dtype, d: int, rows: int, pairs: int) -> bool:
     return dtype == torch.bfloat16 and d == 64 and rows <= 128 and pairs >= 512
 
 
-def _attention_d128_fwd(ctx, q, k, v, kv_len, h, scale, p, seed, qs, ks, vs):
-    """Head dim 128 (gmlm_attention_d128_fwd): q [b, lq, h*128], k / v [b, lk, h*128].  Saves what the backward needs on
-    ``ctx`` and returns the dense output [b, lq, h*128]."""
-    b, lq, _ = q.shape
-    lk = k.shape[1]
-    out = torch.empty(b, lq, h * 128, dtype=q.dtype, device=q.device)
-    lse = torch.empty(b, h, lq, dtype=torch.float32, device=q.device)
-    # bf16: keep the rounding residual of the output for the backward's delta (gmlm_hip.h, out_lo)
-    out_lo = torch.empty_like(out) if q.dtype == torch.bfloat16 and any(t.requires_grad for t in (q, k, v)) else None
-    with _span("attn_fwd_d128", flops=4.0 * b * h * lq * lk * 128):
-        sd = ctx.sd = _sd()
-        check(lib().gmlm_attention_d128_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(kv_len), b, h, lq, lk, 128, qs, ks, vs, float(scale),
-                                            float(p), seed, sd, _ptr(out), _ptr(out_lo), _ptr(lse), _dt(q), _stream()),
-              "gmlm_attention_d128_fwd")
-    ctx.save_for_backward(q, k, v, out, lse, kv_len, out_lo)
-    ctx.cfg = (h, float(scale), float(p), seed)
-    return out
-
-
-def _attention_d128_bwd(ctx, q, k, v, out, out_lo, gout, lse, kv_len, h, scale, p, seed):
-    b, lq, hd = q.shape
-    lk = k.shape[1]
-    dq = torch.empty(b, lq, hd, dtype=q.dtype, device=q.device)
-    dk = torch.empty(b, lk, hd, dtype=q.dtype, device=q.device)
-    dv = torch.empty(b, lk, hd, dtype=q.dtype, device=q.device)
-    ws = _ws(lib().gmlm_attention_d128_workspace_bytes(b, h, lq), q.device)
-    with _span("attn_bwd_d128", flops=10.0 * b * h * lq * lk * 128):
-        check(lib().gmlm_attention_d128_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(out_lo), _ptr(gout), _ptr(lse), _ptr(kv_len),
-                                            b, h, lq, lk, 128, q.stride(1), k.stride(1), v.stride(1), scale, p, seed, ctx.sd,
-                                            _ptr(dq), _ptr(dk), _ptr(dv), hd, hd, hd, _dt(q), _ptr(ws), ws.numel(), _stream()),
-              "gmlm_attention_d128_bwd")
-    return dq, dk, dv
-
-
 class Attention(torch.autograd.Function):
     """out[b, lq, h*d] = softmax(q k^T * scale + key-padding mask) v with streaming softmax.
 
@@ -473,8 +439,6 @@ class Attention(torch.autograd.Function):
         lk = k.shape[1]
         d = hd // h
         qs, ks, vs = _rows_view(q, h, d), _rows_view(k, h, d), _rows_view(v, h, d)
-        if d == 128:
-            return _attention_d128_fwd(ctx, q, k, v, kv_len, h, scale, p, seed, qs, ks, vs)
         out = torch.empty(b, lq, hd, dtype=q.dtype, device=q.device)
         lse = torch.empty(b, h, lq, dtype=torch.float32, device=q.device)
         # bf16 streaming path: keep the rounding residual of the output for the backward's delta (gmlm_hip.h, out_lo)
@@ -483,9 +447,15 @@ class Attention(torch.autograd.Function):
         out_lo = torch.empty_like(out) if want_lo else None
         with _span("attn_fwd_d%d" % d, flops=4.0 * b * h * lq * lk * d):
             sd = ctx.sd = _sd()
-            check(lib().gmlm_attention_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(kv_len), b, h, lq, lk, d, qs, ks, vs, float(scale),
-                                           float(p), seed, sd, _ptr(out), _ptr(out_lo), _ptr(lse), _dt(q), None, 0, None, 0, _stream()),
-                  "gmlm_attention_fwd")
+            if d == 128:      # its own entry point (attn_d128.hip): padded layout only, no bound on b * h
+                check(lib().gmlm_attention_d128_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(kv_len), b, h, lq, lk, d, qs, ks, vs, float(scale),
+                                                    float(p), seed, sd, _ptr(out), _ptr(out_lo), _ptr(lse), _dt(q), _stream()),
+                      "gmlm_attention_d128_fwd")
+            else:
+                check(lib().gmlm_attention_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(kv_len), b, h, lq, lk, d, qs, ks, vs, float(scale),
+                                               float(p), seed, sd, _ptr(out), _ptr(out_lo), _ptr(lse), _dt(q), None, 0, None, 0,
+                                               _stream()),
+                      "gmlm_attention_fwd")
         ctx.save_for_backward(q, k, v, out, lse, kv_len, out_lo)
         ctx.cfg = (h, float(scale), float(p), seed)
         return out
@@ -498,21 +468,26 @@ class Attention(torch.autograd.Function):
         lk = k.shape[1]
         d = hd // h
         gout = gout.contiguous().to(q.dtype)
-        if d == 128:
-            dq, dk, dv = _attention_d128_bwd(ctx, q, k, v, out, out_lo, gout, lse, kv_len, h, scale, p, seed)
-            return dq, dk, dv, None, None, None, None, None
         # one fused [.., 3*h*d] gradient buffer when q/k/v came from a fused QKV GEMM, else three
         dq = torch.empty(b, lq, hd, dtype=q.dtype, device=q.device)
         dk = torch.empty(b, lk, hd, dtype=q.dtype, device=q.device)
         dv = torch.empty(b, lk, hd, dtype=q.dtype, device=q.device)
-        ws = _ws(lib().gmlm_attention_bwd_workspace_bytes(b, h, lq, lk, d), q.device)
+        ws = _ws(lib().gmlm_attention_d128_workspace_bytes(b, h, lq) if d == 128 else
+                 lib().gmlm_attention_bwd_workspace_bytes(b, h, lq, lk, d), q.device)
         with _span("attn_bwd_d%d" % d, flops=10.0 * b * h * lq * lk * d):
             sd = ctx.sd
-            check(lib().gmlm_attention_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(gout), _ptr(lse), _ptr(kv_len), b, h,
-                                           lq, lk, d, q.stride(1), k.stride(1), v.stride(1), scale, p, seed, sd, _ptr(dq),
-                                           _ptr(dk), _ptr(dv), hd, hd, hd, _dt(q), None, 0, _ptr(ws), ws.numel(), None, None,
-                                           _ptr(out_lo), None, 0, _stream()),
-                  "gmlm_attention_bwd")
+            if d == 128:
+                check(lib().gmlm_attention_d128_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(out_lo), _ptr(gout), _ptr(lse),
+                                                    _ptr(kv_len), b, h, lq, lk, d, q.stride(1), k.stride(1), v.stride(1), scale, p,
+                                                    seed, sd, _ptr(dq), _ptr(dk), _ptr(dv), hd, hd, hd, _dt(q), _ptr(ws), ws.numel(),
+                                                    _stream()),
+                      "gmlm_attention_d128_bwd")
+            else:
+                check(lib().gmlm_attention_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(gout), _ptr(lse), _ptr(kv_len), b, h,
+                                               lq, lk, d, q.stride(1), k.stride(1), v.stride(1), scale, p, seed, sd, _ptr(dq),
+                                               _ptr(dk), _ptr(dv), hd, hd, hd, _dt(q), None, 0, _ptr(ws), ws.numel(), None, None,
+                                               _ptr(out_lo), None, 0, _stream()),
+                      "gmlm_attention_bwd")
         return dq, dk, dv, None, None, None, None, None
 
 

@@ -3,6 +3,7 @@ code objects must be exactly the kernels that tests/test_gpu_attention_matrix.py
 those it lists as unreachable (``UNREACHABLE``).  A new instantiation without a parity case, or a stale table entry, fails
 here, by name."""
 import os
+import re
 import shutil
 import subprocess
 import tempfile
@@ -70,3 +71,30 @@ def test_case_table_is_consistent():
             assert len(c.lens) == c.b and sum(c.lens) == c.lq == c.lk, c.id
         if c.layout == "fused":
             assert c.lq == c.lk and c.mode in ("pad", "kvlen"), c.id
+
+
+def test_streaming_dq_mfma_chains_stay_per_key_block():
+    """attn_dq_body (attn_stream.hpp) runs, per 32-key block of a tile, one extra contraction step for the scores, one for dP
+    (without dropout), D/16 steps each for S^T and dP^T and 2 * D/32 for dQ^T.  The bf16 d = 64 / 96 dQ kernels must hold
+    exactly that many v_mfma: one fewer means the key blocks were fused into one scheduling region (the dP start step is then
+    shared), which costs the d = 64 kernels a wave per SIMD.  (d128::dq_kernel is its own text and not counted here.)"""
+    if not os.path.exists(_lib.LIB_PATH):
+        pytest.skip("libgmlm_hip.so not built")
+    if not all(os.path.exists(os.path.join(LLVM, t)) for t in ("llvm-objdump", "llvm-objcopy")):
+        pytest.skip("ROCm llvm tools not found")
+    tmp = tempfile.mkdtemp()
+    try:
+        seen = 0
+        for co in _code_objects(_lib.LIB_PATH, tmp):
+            dis = subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", "--mcpu=gfx950", co], check=True, capture_output=True,
+                                 text=True).stdout
+            for m in re.finditer(r"^[0-9a-f]+ <_ZN4gmlm18attn_bwd_dq_kernelItLi(\d+)ELi(\d)ELb([01])EEEvNS_10AttnParamsE>:\n(.*?)(?=^[0-9a-f]+ <|\Z)",
+                                 dis, re.S | re.M):
+                d, nw, drop = int(m.group(1)), int(m.group(2)), m.group(3) == "1"
+                kb = 4 if nw == 8 else 2                                   # 128-key tiles at 8 waves, else 64
+                want = kb * ((1 if drop else 2) + 2 * (d // 16) + 2 * (d // 32))
+                assert m.group(4).count("v_mfma_") == want, (d, nw, drop, m.group(4).count("v_mfma_"), want)
+                seen += 1
+        assert seen == 12, seen                                            # {64, 96} x {2, 4, 8 waves} x {plain, dropout}
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
