@@ -57,6 +57,20 @@ SIGNATURES = {
     "gmlm_attention_d128_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "gmlm_attention_d128_bwd": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32,
                                           _f32, _u64, _p, _p, _p, _p, _i64, _i64, _i64, _i32, _p, _sz, _p]),
+    "gmlm_attention_causal_d128_fwd": (C.c_int, [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _f32,
+                                                 _p, _p, _p, _i32, _p]),
+    "gmlm_attention_causal_d128_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "gmlm_attention_causal_d128_bwd": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
+                                                 _i64, _f32, _f32, _p, _p, _p, _i64, _i64, _i64, _i32, _p, _sz, _p]),
+    "gmlm_add_rmsnorm_fwd": (C.c_int, [_p, _p, _p, _i64, _i64, _f32, _p, _p, _p, _i32, _p]),
+    "gmlm_add_rmsnorm_bwd_workspace_bytes": (_sz, [_i64, _i64]),
+    "gmlm_add_rmsnorm_bwd": (C.c_int, [_p, _p, _p, _p, _p, _i64, _i64, _p, _p, _i32, _p, _sz, _p]),
+    "gmlm_qknorm_rope_fwd": (C.c_int, [_p, _i64, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _p, _i64, _p, _i32, _p]),
+    "gmlm_qknorm_rope_bwd_workspace_bytes": (_sz, [_i64, _i64, _i64, _i32]),
+    "gmlm_qknorm_rope_bwd": (C.c_int, [_p, _i64, _p, _i64, _p, _p, _p, _i64, _p, _i64, _i64, _i64, _i64, _i64, _p, _p, _i32, _p,
+                                       _sz, _p]),
+    "gmlm_swiglu_fwd": (C.c_int, [_p, _i64, _i64, _p, _i32, _p]),
+    "gmlm_swiglu_bwd": (C.c_int, [_p, _p, _i64, _i64, _p, _i32, _p]),
     "gmlm_embed_sum_fwd": (C.c_int, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _i32, _p, _p]),
     "gmlm_meanpool_scatter_fwd": (C.c_int, [_p, _p, _p, _i64, _i64, _i64, _p, _i32, _p, _p]),
     "gmlm_meanpool_scatter_bwd": (C.c_int, [_p, _p, _p, _i64, _i64, _i64, _p, _i32, _p, _p]),

@@ -12,8 +12,14 @@ namespace gmlm {
 // ------------------------------------------------------------------------------------------------
 // forward
 // ------------------------------------------------------------------------------------------------
-template <typename T, int D, int NW, bool DROP, int KT, bool DBUF>
-__device__ __forceinline__ void attn_fwd_body(const AttnParams& p, int64_t tile, int64_t b, int64_t hd, int64_t o_stride) {
+// CAUSAL (lq == lk, padded layout): query i sees the keys <= i below kv_len; the key loop ends at the workgroup's last query,
+//   tiles wholly below the diagonal keep the compare-free path, a wave skips the arithmetic (never a barrier) of tiles past
+//   its rows.  A wave computes a tile only if the tile's first key is <= its first query (both multiples of 32), so every
+//   row of a computing wave has a valid key in every tile it computes: the running max stays finite.
+// GQA: K / V are read from head `kvh` (query head hd / group) instead of hd.
+template <typename T, int D, int NW, bool DROP, int KT, bool DBUF, bool CAUSAL = false, bool GQA = false>
+__device__ __forceinline__ void attn_fwd_body(const AttnParams& p, int64_t tile, int64_t b, int64_t hd, int64_t o_stride,
+                                              int64_t kvh = 0) {
   constexpr int KB = KT / 32, NT = NW * 64, PITCH = D + Pad<T>::v, DB = D / 32, NBUF = DBUF ? 2 : 1;
   __shared__ __attribute__((aligned(16))) T ks[NBUF][KT * PITCH];
   __shared__ __attribute__((aligned(16))) T vs[NBUF][KT * PITCH];
@@ -28,8 +34,9 @@ __device__ __forceinline__ void attn_fwd_body(const AttnParams& p, int64_t tile,
   int64_t kvlen = lk_;
   if (p.kv_len) { kvlen = p.kv_len[b]; if (kvlen > lk_) kvlen = lk_; if (kvlen < 0) kvlen = 0; }
   const T* qg = static_cast<const T*>(p.q) + (qbase + (q_ok ? q_row : 0)) * p.q_stride + hd * D;
-  const T* kg = static_cast<const T*>(p.k) + kbase * p.k_stride + hd * D;
-  const T* vg = static_cast<const T*>(p.v) + kbase * p.v_stride + hd * D;
+  const int64_t khd = GQA ? kvh : hd;
+  const T* kg = static_cast<const T*>(p.k) + kbase * p.k_stride + khd * D;
+  const T* vg = static_cast<const T*>(p.v) + kbase * p.v_stride + khd * D;
   RowFrag<T, D> qf;
   qf.load(qg, q_ok, h);
   f32x16 o[DB];
@@ -42,7 +49,9 @@ __device__ __forceinline__ void attn_fwd_body(const AttnParams& p, int64_t tile,
   // dropout hash input of this lane's query (+ 2h: the lane half's keys sit 4 further on, i.e. 2 key pairs)
   const uint32_t dq_u = drop_base(attn_seed(p), lse_base) + (uint32_t)(q_row >> 1) * kDropC1 + (uint32_t)(2 * h) * kDropC2;
   const int q_odd = (int)(q_row & 1);
-  const int ntiles = (int)((kvlen + KT - 1) / KT);
+  const int64_t q_tile0 = tile * (NW * 32), q_wave0 = q_tile0 + w * 32;
+  const int64_t kv_end = CAUSAL && q_tile0 + NW * 32 < kvlen ? q_tile0 + NW * 32 : kvlen;   // keys this workgroup can see
+  const int ntiles = (int)((kv_end + KT - 1) / KT);
   TileRegs<T, D, KT, NT> kr, vr;
   kr.init(p.k_stride, tid);
   vr.init(p.v_stride, tid);
@@ -61,7 +70,7 @@ __device__ __forceinline__ void attn_fwd_body(const AttnParams& p, int64_t tile,
       kr.load(kg, p.k_stride, kv0 + KT, lk_, tid);
       vr.load(vg, p.v_stride, kv0 + KT, lk_, tid);
     }
-    if (wave_live) {
+    if (wave_live && (!CAUSAL || kv0 <= q_wave0)) {
     f32x16 s[KB];
 #pragma unroll
     for (int kb = 0; kb < KB; ++kb) {
@@ -70,7 +79,7 @@ __device__ __forceinline__ void attn_fwd_body(const AttnParams& p, int64_t tile,
       mma_rows<D>(ks[cur], PITCH, kb * 32, qf, s[kb], r, h);
     }
     float rmax = -INFINITY;
-    if (kv0 + KT <= kvlen) {                        // whole tile valid (block-uniform): no per-key compare
+    if (kv0 + KT <= kvlen && (!CAUSAL || kv0 + KT - 1 <= q_tile0)) {   // whole tile valid (block-uniform; causal: and below the diagonal): no per-key compare
 #pragma unroll
       for (int kb = 0; kb < KB; ++kb)
 #pragma unroll
@@ -81,7 +90,7 @@ __device__ __forceinline__ void attn_fwd_body(const AttnParams& p, int64_t tile,
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
           const int64_t key = kv0 + kb * 32 + acc_row(i, h);
-          const float v = key < kvlen ? s[kb][i] : -INFINITY;
+          const float v = (key < kvlen && (!CAUSAL || key <= q_row)) ? s[kb][i] : -INFINITY;
           s[kb][i] = v;
           rmax = fmaxf(rmax, v);
         }
@@ -195,8 +204,12 @@ __device__ __forceinline__ void attn_delta_body(const T* __restrict__ o, const T
 //   dQ^T += K^T dS^T  (all with the query on the lane)
 // ------------------------------------------------------------------------------------------------
 // d128::dq_kernel (attn_d128.hip) keeps a copy of this text for its register budget: a change here belongs there too.
-template <typename T, int D, int NW, bool DROP, int KT, bool DBUF>
-__device__ __forceinline__ void attn_dq_body(const AttnParams& p, int64_t tile, int64_t b, int64_t hd, int64_t o_stride) {
+// CAUSAL / GQA as in attn_fwd_body.  The bf16 extra contraction step cannot express a causal mask (it is not rank-1): the one
+// 32-key block that crosses a wave's diagonal selects P = 0 explicitly before dS (a select, not a product: a score above
+// the diagonal is not bounded by lse and may have overflowed).
+template <typename T, int D, int NW, bool DROP, int KT, bool DBUF, bool CAUSAL = false, bool GQA = false>
+__device__ __forceinline__ void attn_dq_body(const AttnParams& p, int64_t tile, int64_t b, int64_t hd, int64_t o_stride,
+                                             int64_t kvh = 0) {
   constexpr int KB = KT / 32, NT = NW * 64, PITCH = D + Pad<T>::v, DB = D / 32, NBUF = DBUF ? 2 : 1;
   __shared__ __attribute__((aligned(16))) T ks[NBUF][KT * PITCH];
   __shared__ __attribute__((aligned(16))) T vs[NBUF][KT * PITCH];
@@ -210,8 +223,9 @@ __device__ __forceinline__ void attn_dq_body(const AttnParams& p, int64_t tile, 
   int64_t kvlen = lk_;
   if (p.kv_len) { kvlen = p.kv_len[b]; if (kvlen > lk_) kvlen = lk_; if (kvlen < 0) kvlen = 0; }
   const int64_t qr = q_ok ? q_row : 0;
-  const T* kg = static_cast<const T*>(p.k) + kbase * p.k_stride + hd * D;
-  const T* vg = static_cast<const T*>(p.v) + kbase * p.v_stride + hd * D;
+  const int64_t khd = GQA ? kvh : hd;
+  const T* kg = static_cast<const T*>(p.k) + kbase * p.k_stride + khd * D;
+  const T* vg = static_cast<const T*>(p.v) + kbase * p.v_stride + khd * D;
   RowFrag<T, D> qf, dof;
   qf.load(static_cast<const T*>(p.q) + (qbase + qr) * p.q_stride + hd * D, q_ok, h);
   dof.load(static_cast<const T*>(p.dout) + (qbase + qr) * o_stride + hd * D, q_ok, h);
@@ -250,7 +264,10 @@ __device__ __forceinline__ void attn_dq_body(const AttnParams& p, int64_t tile, 
   for (int d = 0; d < DB; ++d)
 #pragma unroll
     for (int i = 0; i < 16; ++i) dq[d][i] = 0.f;
-  const int ntiles = (int)((kvlen + KT - 1) / KT);
+  const int64_t q_tile0 = tile * (NW * 32), q_wave0 = q_tile0 + w * 32;
+  const int64_t kv_end = CAUSAL && q_tile0 + NW * 32 < kvlen ? q_tile0 + NW * 32 : kvlen;   // keys this workgroup can see
+  const int qi = (int)(q_row < (1 << 30) ? q_row : (1 << 30));
+  const int ntiles = (int)((kv_end + KT - 1) / KT);
   TileRegs<T, D, KT, NT> kr, vr;
   kr.init(p.k_stride, tid);
   vr.init(p.v_stride, tid);
@@ -272,6 +289,10 @@ __device__ __forceinline__ void attn_dq_body(const AttnParams& p, int64_t tile, 
     if (wave_live) {
 #pragma unroll
     for (int kb = 0; kb < KB; ++kb) {
+      if constexpr (CAUSAL) {
+        if (kv0 + kb * 32 > q_wave0) continue;                 // key block above this wave's rows (wave-uniform; no barrier inside)
+      }
+      const bool diag = CAUSAL && kv0 + kb * 32 == q_wave0;    // the only key block that crosses this wave's diagonal
       f32x16 s, dp;
 #pragma unroll
       for (int i = 0; i < 16; ++i) { s[i] = 0.f; dp[i] = 0.f; }
@@ -299,6 +320,13 @@ __device__ __forceinline__ void attn_dq_body(const AttnParams& p, int64_t tile, 
           float a0 = fmaf(s[i], sl2, -lse2), a1 = fmaf(s[i + 1], sl2, -lse2);
           if (!full) { a0 = key < kvl ? a0 : -INFINITY; a1 = key + 1 < kvl ? a1 : -INFINITY; }
           p0 = fast_exp2(a0); p1 = fast_exp2(a1);
+        }
+        if constexpr (CAUSAL) {
+          if (diag) {
+            const int kq = (int)kv0 + kb * 32 + acc_row(i, h);
+            p0 = kq <= qi ? p0 : 0.f;
+            p1 = kq + 1 <= qi ? p1 : 0.f;
+          }
         }
         if (FOLD && !DROP) {
           s[i] = p0 * dp[i];

@@ -20,7 +20,7 @@ import torch
 import torch.nn as nn
 from torch.utils.checkpoint import checkpoint
 
-from . import bert, ops
+from . import bert, ops, qwen3
 from .graph import GraphCache, RelCSR
 from .nn import (SPLITK_ROW_QUANTUM, CrossAttention, GraphNorm, MultiScaleFusion, RGCNConv, _linear, compute_dtype,
                  cross_attention_specs, linear_specs, shadow_params, use_shadow)
@@ -83,7 +83,21 @@ class TokenizedTexts:
 
     @classmethod
     def from_mask(cls, input_ids: torch.Tensor, attention_mask: torch.Tensor):
-        return cls(input_ids, attention_mask.sum(-1))
+        """Rows are stored left-aligned (valid ids in columns 0..len-1).  A tokenizer that pads on the LEFT (Qwen tokenizers
+        commonly do) gives rows whose mask is one contiguous run starting past column 0: their ids are shifted to column 0
+        here, on the device (no host sync), once per token set.  Positions are relative in a rotary encoder and counted from 0
+        in BERT, so the left-aligned row is what both encoder passes expect.  Right-padded rows are left as they are."""
+        mask = attention_mask != 0
+        lens = mask.sum(-1)
+        width = mask.shape[-1]
+        if width:
+            cols = torch.arange(width, device=mask.device)[None, :]
+            first = mask.int().argmax(-1)[:, None]                                        # column of each row's first valid token
+            is_run = ((cols >= first) & (cols < first + lens[:, None])) == mask
+            shift = is_run.all(-1, keepdim=True) & (first > 0)
+            moved = torch.where(cols < lens[:, None], input_ids.gather(1, (cols + first).clamp(max=width - 1)), 0)
+            input_ids = torch.where(shift, moved, input_ids)
+        return cls(input_ids, lens)
 
     def to(self, device):
         return TokenizedTexts(self.input_ids.to(device), self.lens.to(device))
@@ -120,7 +134,9 @@ class GraphTextLM(nn.Module):
             plm_encoder = AutoModel.from_pretrained(model_name, trust_remote_code=True)
             if plm_tokenizer is None:
                 plm_tokenizer = AutoTokenizer.from_pretrained(model_name, trust_remote_code=True)
-        bert.check_supported(plm_encoder)
+        # the encoder pass is picked by the PLM's model type: BERT geometry (gmlm_amd.bert) or Qwen3 (gmlm_amd.qwen3)
+        self._plm_kind = "qwen3" if getattr(plm_encoder.config, "model_type", None) == "qwen3" else "bert"
+        self._enc.check_supported(plm_encoder)
         self.plm_encoder = plm_encoder
         self.plm_tokenizer = plm_tokenizer
         self.plm_max_length = plm_max_length
@@ -158,6 +174,17 @@ class GraphTextLM(nn.Module):
     # ------------------------------------------------------------------------------------------
     def _cd(self) -> torch.dtype:
         return compute_dtype(self.compute_dtype)
+
+    @property
+    def _enc(self):
+        return qwen3 if self._plm_kind == "qwen3" else bert
+
+    def _packed_head_dim(self) -> int:
+        """Head dim of the text encoder if it has a packed (varlen) pass and the short-sequence / whole-step forms built on it,
+        else 0: BERT geometry only.  A Qwen3 encoder runs the padded pass whatever its hidden_size // heads is (64 for
+        Qwen3-0.6B, whose head dim is 128)."""
+        cfg = self.plm_encoder.config
+        return cfg.hidden_size // cfg.num_attention_heads if self._enc is bert else 0
 
     def graph(self, edge_index: torch.Tensor, num_nodes: int, edge_type=None) -> RelCSR:
         if self.dist is not None:
@@ -302,7 +329,7 @@ class GraphTextLM(nn.Module):
         lens_h = tokens.lens_host[idx_h]
         order = torch.argsort(lens_h, descending=True, stable=True)   # long sequences first: fuller attention work items
         cap = int(tokens.lens_host.max())
-        short = cd == torch.bfloat16 and p // heads == 64 and cap <= 128
+        short = cd == torch.bfloat16 and self._packed_head_dim() == 64 and cap <= 128
         lens_all, s_b, t_b, groups_h = bucketed_layout(lens_h[order].tolist(), cap, short)
         short = short and s_b * heads >= 512
         bi_h = torch.full((s_b,), n, dtype=torch.long)
@@ -344,7 +371,7 @@ class GraphTextLM(nn.Module):
         tokens.check_ids(ecfg.vocab_size, ecfg.max_position_embeddings)      # one sync per token set, not per step
         grad = self.plm_encoder.training or self.training
         heads = self.plm_encoder.config.num_attention_heads
-        packed = (p // heads) in (64, 96) and self.plm_packed
+        packed = self._packed_head_dim() in (64, 96) and self.plm_packed
         plm_batch_size = max(1, min(int(plm_batch_size), 65535 // heads))   # attention grids index (sequence, head) in 16 bits
         with torch.set_grad_enabled(grad and torch.is_grad_enabled()):
             # cast / fuse once, share across micro-batches (forward() has done it ahead of the GNN launches)
@@ -359,7 +386,7 @@ class GraphTextLM(nn.Module):
                     return g.encoder(self, key, tokens, args)
                 return self.encode_packed_static(tokens, key, *args, *(() if short else (None,)), weights)
             if weights is None:
-                weights = bert.prepare_weights(self.plm_encoder, cd)
+                weights = self._enc.prepare_weights(self.plm_encoder, cd)
             lens_h = tokens.lens_host[idx_h]
             # length-bucketed micro-batches: every active node is encoded independently and scattered by its own
             # index, so the order is free; sorting by token count keeps the padding of each micro-batch small
@@ -399,7 +426,7 @@ class GraphTextLM(nn.Module):
                     # 1,000 sequences, once per batch: all layers, forward and backward, share it)
                     groups = None
                     n_seq = bi.numel() + (1 if pad else 0)
-                    if cd == torch.bfloat16 and p // heads == 64 and lmax <= 128 and n_seq * heads >= 512:
+                    if cd == torch.bfloat16 and self._packed_head_dim() == 64 and lmax <= 128 and n_seq * heads >= 512:
                         groups = to_dev(ops.pack_sequence_groups(lh.tolist() + ([pad] if pad else [])))
                     hs = bert.bert_encode_packed(self.plm_encoder, tok, pos, cu_all, lmax, cd, self.plm_encoder.training,
                                                  self.plm_gradient_checkpointing, weights,
@@ -407,8 +434,8 @@ class GraphTextLM(nn.Module):
                     plm_embeds = ops.MeanPoolScatter.apply(plm_embeds, hs, None, bi, cu, total)
                 else:
                     ids = tokens.input_ids[bi, :lmax]
-                    hs = bert.bert_encode(self.plm_encoder, ids, lens, cd, self.plm_encoder.training,
-                                          self.plm_gradient_checkpointing, weights)
+                    encode = qwen3.qwen3_encode if self._enc is qwen3 else bert.bert_encode
+                    hs = encode(self.plm_encoder, ids, lens, cd, self.plm_encoder.training, self.plm_gradient_checkpointing, weights)
                     plm_embeds = ops.MeanPoolScatter.apply(plm_embeds, hs, lens, bi)
         return plm_embeds
 
@@ -447,7 +474,7 @@ class GraphTextLM(nn.Module):
             heads = self.plm_encoder.config.num_attention_heads
             a = seen["idx_h"].numel()
             if (0 < a <= max(1, min(int(plm_batch_size), 65535 // heads)) and self.plm_packed
-                    and (self.plm_encoder.config.hidden_size // heads) in (64, 96)):
+                    and self._packed_head_dim() in (64, 96)):
                 if seen["active_index"] is None:
                     seen["active_index"] = seen["idx_h"].pin_memory().to(gnn_input_features.device, non_blocking=True)
                 self.active_index = seen["active_index"]
@@ -467,7 +494,7 @@ class GraphTextLM(nn.Module):
             gnn_embeds = self.get_graph_embeddings(gnn_input_features, edge_index, edge_type)
             tokens = self.tokenize(all_node_texts)
             with torch.cuda.stream(side):
-                weights = bert.prepare_weights(self.plm_encoder, self._cd())
+                weights = self._enc.prepare_weights(self.plm_encoder, self._cd())
                 plm_embeds = self.encode_texts(tokens, text_processing_node_mask, plm_batch_size, mask_copy, weights)
             cur.wait_stream(side)                                     # join
             plm_embeds.record_stream(cur)                             # allocated on `side`, read (and saved for backward) on `cur`
@@ -491,7 +518,7 @@ class GraphTextLM(nn.Module):
                 self.active_index.record_stream(cur)
             return g.head(gnn_embeds, plm_embeds)
         # (a recorded encoder casts the weights inside its own graph)
-        weights = None if (replay and g.encoder_enabled) else bert.prepare_weights(self.plm_encoder, self._cd())
+        weights = None if (replay and g.encoder_enabled) else self._enc.prepare_weights(self.plm_encoder, self._cd())
         gnn_embeds = g.gnn(gnn_input_features) if replay else \
             self.get_graph_embeddings(gnn_input_features, edge_index, edge_type)               # fp32 [N, P]
         tokens = self.tokenize(all_node_texts)
@@ -509,6 +536,9 @@ class GraphTextLM(nn.Module):
         for THIS input shape and ``edge_index`` tensor; ``forward`` then replays them (training mode, same shape, same
         edge tensor) and runs eagerly otherwise.  For the launch-bound small configurations (gmlm_amd/graphs.py)."""
         from . import graphs
+        if self._enc is not bert and encoder:
+            raise NotImplementedError("hipGraph capture of the text encoder covers BERT-geometry encoders only; pass encoder=False "
+                                      "to record the GNN and head regions around an eager Qwen3 encoder")
         return graphs.capture(self, gnn_input_sample, edge_index, encoder=encoder, whole_step=whole_step, concurrent=concurrent)
 
     def release_hip_graphs(self):

@@ -845,3 +845,242 @@ class BiasGelu(torch.autograd.Function):
 def bias_gelu(x, bias, p=0.0, training=False):
     p = float(p) if training else 0.0
     return BiasGelu.apply(x, bias, p, draw_seed() if p > 0 else 0)
+
+
+# ---------------------------------------------------------------------------------------------
+# Pre-norm decoder-style encoder (Qwen3 geometry): add + RMSNorm, Q/K head norm + RoPE, SwiGLU, causal GQA attention
+# ---------------------------------------------------------------------------------------------
+class AddRMSNorm(torch.autograd.Function):
+    """(s, y) with s = a + b in the compute dtype (``b`` None: s is ``a``) and y = s * rsqrt(mean(s^2) + eps) * w.
+    ``s`` is the residual stream handed to the next add; its gradient and y's meet in ONE backward kernel."""
+
+    @staticmethod
+    def forward(ctx, a, b, w, eps):
+        _cuda(a)
+        shape = a.shape
+        f = shape[-1]
+        a2 = a.contiguous().view(-1, f)
+        b2 = None if b is None else b.to(a.dtype).contiguous().view(-1, f)
+        rows = a2.shape[0]
+        wf = _f32c(w)
+        s2 = torch.empty_like(a2) if b2 is not None else None
+        y = torch.empty_like(a2)
+        rstd = torch.empty(rows, dtype=torch.float32, device=a.device)
+        check(lib().gmlm_add_rmsnorm_fwd(_ptr(a2), _ptr(b2), _ptr(wf), rows, f, float(eps), _ptr(s2), _ptr(y), _ptr(rstd),
+                                         _dt(a2), _stream()), "gmlm_add_rmsnorm_fwd")
+        if s2 is None:
+            s2 = a2
+        ctx.save_for_backward(s2, wf, rstd)
+        ctx.cfg = (shape, b is not None)
+        return (s2.view(shape) if b is not None else a.view_as(a)), y.view(shape)
+
+    @staticmethod
+    def backward(ctx, gs, gy):
+        s2, wf, rstd = ctx.saved_tensors
+        shape, has_b = ctx.cfg
+        rows, f = s2.shape
+        if gy is None:
+            gy = torch.zeros_like(s2)
+        gy2 = gy.contiguous().view(rows, f).to(s2.dtype)
+        gs2 = None if gs is None else gs.contiguous().view(rows, f).to(s2.dtype)
+        ds = torch.empty_like(s2)
+        dw = torch.empty(f, dtype=torch.float32, device=s2.device)
+        ws = _ws(lib().gmlm_add_rmsnorm_bwd_workspace_bytes(rows, f), s2.device)
+        check(lib().gmlm_add_rmsnorm_bwd(_ptr(gy2), _ptr(gs2), _ptr(s2), _ptr(wf), _ptr(rstd), rows, f, _ptr(ds), _ptr(dw),
+                                         _dt(s2), _ptr(ws), ws.numel(), _stream()), "gmlm_add_rmsnorm_bwd")
+        ds = ds.view(shape)
+        return ds, (ds if has_b else None), dw, None
+
+
+def add_rmsnorm(a, b, w, eps=1e-6):
+    """-> (a + b, RMSNorm(a + b) * w); ``b`` may be None."""
+    return AddRMSNorm.apply(a, b, w, eps)
+
+
+def _qkv_rows(qkv: torch.Tensor, width: int):
+    """[..., >= width] rows with a contiguous last dim and one row stride -> (tokens, row stride in elements)."""
+    if qkv.stride(-1) != 1 or qkv.shape[-1] < width:
+        raise ValueError(f"fused projection rows must be contiguous and at least {width} wide")
+    tokens = qkv.numel() // qkv.shape[-1]
+    stride = qkv.stride(-2)
+    if qkv.dim() == 3 and qkv.shape[0] > 1 and qkv.stride(0) != qkv.shape[1] * stride:
+        raise ValueError("fused projection rows must have batch stride = l * row stride")
+    return tokens, stride
+
+
+def _rope_fwd(qkv, qw, kw, cs, seq_len, hq, hkv, eps):
+    tokens, stride = _qkv_rows(qkv, (hq + 2 * hkv) * 128)
+    qk = torch.empty(*qkv.shape[:-1], (hq + hkv) * 128, dtype=qkv.dtype, device=qkv.device)
+    rstd = torch.empty(tokens, hq + hkv, dtype=torch.float32, device=qkv.device)
+    check(lib().gmlm_qknorm_rope_fwd(_ptr(qkv), stride, _ptr(qw), _ptr(kw), _ptr(cs), cs.shape[0], tokens, seq_len, hq, hkv, 128,
+                                     float(eps), _ptr(qk), (hq + hkv) * 128, _ptr(rstd), _dt(qkv), _stream()),
+          "gmlm_qknorm_rope_fwd")
+    return qk, rstd
+
+
+def _rope_bwd_(dqkv, qkv, qw, kw, cs, rstd, seq_len, hq, hkv):
+    """In place on the Q | K columns of ``dqkv``; returns the fp32 [2, 128] weight gradients."""
+    tokens, stride = _qkv_rows(qkv, (hq + 2 * hkv) * 128)
+    _, dstride = _qkv_rows(dqkv, (hq + hkv) * 128)
+    dwt = torch.empty(2, 128, dtype=torch.float32, device=qkv.device)
+    ws = _ws(lib().gmlm_qknorm_rope_bwd_workspace_bytes(tokens, hq, hkv, _dt(qkv)), qkv.device)
+    check(lib().gmlm_qknorm_rope_bwd(_ptr(dqkv), dstride, _ptr(qkv), stride, _ptr(qw), _ptr(kw), _ptr(cs), cs.shape[0], _ptr(rstd),
+                                     tokens, seq_len, hq, hkv, 128, _ptr(dwt), _ptr(dwt[1]), _dt(qkv), _ptr(ws), ws.numel(),
+                                     _stream()), "gmlm_qknorm_rope_bwd")
+    return dwt
+
+
+def _rope_args(qkv, qw, kw, cs):
+    if qkv.dim() != 3:
+        raise ValueError("fused projection output must be [b, l, (hq + 2 hkv) * 128]")
+    if cs.dtype != torch.float32 or cs.dim() != 3 or tuple(cs.shape[1:]) != (2, 64) or not cs.is_contiguous():
+        raise ValueError("cos / sin table must be a contiguous fp32 [max_len, 2, 64] tensor")
+    return _f32c(qw), _f32c(kw)
+
+
+class QKNormRope(torch.autograd.Function):
+    """Rotated, head-normalised [q | k] of a fused [b, l, (hq + 2 hkv) * 128] projection output (positions 0..l-1)."""
+
+    @staticmethod
+    def forward(ctx, qkv, qw, kw, cs, hq, hkv, eps):
+        _cuda(qkv)
+        qwf, kwf = _rope_args(qkv, qw, kw, cs)
+        qk, rstd = _rope_fwd(qkv, qwf, kwf, cs, qkv.shape[1], hq, hkv, eps)
+        ctx.save_for_backward(qkv, qwf, kwf, cs, rstd)
+        ctx.cfg = (hq, hkv)
+        return qk
+
+    @staticmethod
+    def backward(ctx, g):
+        qkv, qwf, kwf, cs, rstd = ctx.saved_tensors
+        hq, hkv = ctx.cfg
+        n = (hq + hkv) * 128
+        dqkv = torch.zeros(*qkv.shape[:-1], (hq + 2 * hkv) * 128, dtype=qkv.dtype, device=qkv.device)   # V columns: no gradient from here
+        dqkv[..., :n].copy_(g)
+        dwt = _rope_bwd_(dqkv, qkv, qwf, kwf, cs, rstd, qkv.shape[1], hq, hkv)
+        if dqkv.shape[-1] != qkv.shape[-1]:
+            dqkv = torch.nn.functional.pad(dqkv, (0, qkv.shape[-1] - dqkv.shape[-1]))
+        return dqkv, dwt[0], dwt[1], None, None, None, None
+
+
+def qknorm_rope(qkv, q_weight, k_weight, cos_sin, hq, hkv, eps=1e-6):
+    return QKNormRope.apply(qkv, q_weight, k_weight, cos_sin, hq, hkv, eps)
+
+
+def _causal_fwd(q, k, v, kv_len, hq, hkv, scale, want_lo):
+    b, l = q.shape[0], q.shape[1]
+    qs, ks, vs = _rows_view(q, hq, 128), _rows_view(k, hkv, 128), _rows_view(v, hkv, 128)
+    out = torch.empty(b, l, hq * 128, dtype=q.dtype, device=q.device)
+    lse = torch.empty(b, hq, l, dtype=torch.float32, device=q.device)
+    out_lo = torch.empty_like(out) if want_lo else None
+    with _span("attn_causal_fwd_d128", flops=2.0 * b * hq * l * l * 128):
+        check(lib().gmlm_attention_causal_d128_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(kv_len), b, hq, hkv, l, k.shape[1], 128, qs, ks, vs,
+                                                   float(scale), 0.0, _ptr(out), _ptr(out_lo), _ptr(lse), _dt(q), _stream()),
+              "gmlm_attention_causal_d128_fwd")
+    return out, out_lo, lse
+
+
+def _causal_bwd(q, k, v, out, out_lo, gout, lse, kv_len, hq, hkv, scale, dq, dk, dv):
+    b, l = q.shape[0], q.shape[1]
+    gout = gout.contiguous().to(q.dtype)
+    ws = _ws(lib().gmlm_attention_causal_d128_workspace_bytes(b, hq, l), q.device)
+    with _span("attn_causal_bwd_d128", flops=5.0 * b * hq * l * l * 128):
+        check(lib().gmlm_attention_causal_d128_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(out_lo), _ptr(gout), _ptr(lse),
+                                                   _ptr(kv_len), b, hq, hkv, l, k.shape[1], 128, q.stride(1), k.stride(1), v.stride(1),
+                                                   float(scale), 0.0, _ptr(dq), _ptr(dk), _ptr(dv), dq.stride(1), dk.stride(1),
+                                                   dv.stride(1), _dt(q), _ptr(ws), ws.numel(), _stream()),
+              "gmlm_attention_causal_d128_bwd")
+
+
+class CausalAttention(torch.autograd.Function):
+    """out[b, l, hq*128] = softmax(causal + key-padding mask(q k^T * scale)) v with hq query heads sharing hkv KV heads.
+    q [b, l, hq*128], k / v [b, l, hkv*128] (strided slices of a fused buffer are fine); kv_len int32 [b] or None.
+    The three gradients are views of ONE fused [b, l, (hq + 2 hkv) * 128] buffer."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, kv_len, hq, hkv, scale):
+        _cuda(q, k, v)
+        want_lo = q.dtype == torch.bfloat16 and any(t.requires_grad for t in (q, k, v))
+        out, out_lo, lse = _causal_fwd(q, k, v, kv_len, hq, hkv, scale, want_lo)
+        ctx.save_for_backward(q, k, v, out, lse, kv_len, out_lo)
+        ctx.cfg = (hq, hkv, float(scale))
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        q, k, v, out, lse, kv_len, out_lo = ctx.saved_tensors
+        hq, hkv, scale = ctx.cfg
+        b, l = q.shape[0], q.shape[1]
+        nq, nk = hq * 128, hkv * 128
+        dqkv = torch.empty(b, l, nq + 2 * nk, dtype=q.dtype, device=q.device)
+        dq, dk, dv = dqkv[..., :nq], dqkv[..., nq:nq + nk], dqkv[..., nq + nk:]
+        _causal_bwd(q, k, v, out, out_lo, gout, lse, kv_len, hq, hkv, scale, dq, dk, dv)
+        return dq, dk, dv, None, None, None, None
+
+
+def causal_attention(q, k, v, kv_len, hq, hkv, scale):
+    return CausalAttention.apply(q, k, v, kv_len, hq, hkv, scale)
+
+
+class RopeCausalAttention(torch.autograd.Function):
+    """Head norm + RoPE + causal GQA attention of a fused [b, l, (hq + 2 hkv) * 128] projection output in one autograd node:
+    V is read from the fused rows in place, and the backward lets the attention kernels write dq | dk | dv into ONE fused
+    buffer that the head-norm backward then finishes in place, so a single data-gradient GEMM follows."""
+
+    @staticmethod
+    def forward(ctx, qkv, qw, kw, cs, kv_len, hq, hkv, scale, eps):
+        _cuda(qkv)
+        qwf, kwf = _rope_args(qkv, qw, kw, cs)
+        if qkv.shape[-1] != (hq + 2 * hkv) * 128:
+            raise ValueError("fused projection output must be [b, l, (hq + 2 hkv) * 128]")
+        nq, nk = hq * 128, hkv * 128
+        qk, rstd = _rope_fwd(qkv, qwf, kwf, cs, qkv.shape[1], hq, hkv, eps)
+        want_lo = qkv.dtype == torch.bfloat16 and (qkv.requires_grad or qw.requires_grad or kw.requires_grad)
+        out, out_lo, lse = _causal_fwd(qk[..., :nq], qk[..., nq:], qkv[..., nq + nk:], kv_len, hq, hkv, scale, want_lo)
+        ctx.save_for_backward(qkv, qk, qwf, kwf, cs, rstd, out, lse, kv_len, out_lo)
+        ctx.cfg = (hq, hkv, float(scale))
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        qkv, qk, qwf, kwf, cs, rstd, out, lse, kv_len, out_lo = ctx.saved_tensors
+        hq, hkv, scale = ctx.cfg
+        nq, nk = hq * 128, hkv * 128
+        dqkv = torch.empty_like(qkv, memory_format=torch.contiguous_format)
+        _causal_bwd(qk[..., :nq], qk[..., nq:], qkv[..., nq + nk:], out, out_lo, gout, lse, kv_len, hq, hkv, scale,
+                    dqkv[..., :nq], dqkv[..., nq:nq + nk], dqkv[..., nq + nk:])
+        dwt = _rope_bwd_(dqkv, qkv, qwf, kwf, cs, rstd, qkv.shape[1], hq, hkv)
+        return dqkv, dwt[0], dwt[1], None, None, None, None, None, None
+
+
+def rope_causal_attention(qkv, q_weight, k_weight, cos_sin, kv_len, hq, hkv, scale, eps=1e-6):
+    return RopeCausalAttention.apply(qkv, q_weight, k_weight, cos_sin, kv_len, hq, hkv, scale, eps)
+
+
+class SwiGLU(torch.autograd.Function):
+    """[..., 2 I] = [gate | up] -> silu(gate) * up [..., I]."""
+
+    @staticmethod
+    def forward(ctx, gu):
+        _cuda(gu)
+        shape = gu.shape
+        inter = shape[-1] // 2
+        g2 = gu.contiguous().view(-1, 2 * inter)
+        y = torch.empty(g2.shape[0], inter, dtype=gu.dtype, device=gu.device)
+        check(lib().gmlm_swiglu_fwd(_ptr(g2), g2.shape[0], inter, _ptr(y), _dt(g2), _stream()), "gmlm_swiglu_fwd")
+        ctx.save_for_backward(g2)
+        ctx.shape = shape
+        return y.view(*shape[:-1], inter)
+
+    @staticmethod
+    def backward(ctx, gy):
+        (g2,) = ctx.saved_tensors
+        rows, inter = g2.shape[0], g2.shape[1] // 2
+        gy2 = gy.contiguous().view(rows, inter).to(g2.dtype)
+        dgu = torch.empty_like(g2)
+        check(lib().gmlm_swiglu_bwd(_ptr(gy2), _ptr(g2), rows, inter, _ptr(dgu), _dt(g2), _stream()), "gmlm_swiglu_bwd")
+        return dgu.view(ctx.shape)
+
+
+def swiglu(gate_up):
+    return SwiGLU.apply(gate_up)

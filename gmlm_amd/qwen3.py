@@ -1,0 +1,188 @@
+"""Qwen3-geometry text encoder forward on the gfx950 kernels.
+
+Replaces the forward of HuggingFace ``Qwen3Model`` (hf:modeling_qwen3.py: Qwen3RMSNorm, Qwen3RotaryEmbedding,
+Qwen3Attention, Qwen3MLP, Qwen3DecoderLayer) as the reference runs it on ``Qwen/Qwen3-Embedding-0.6B`` (main.py:1007, 349),
+while keeping the HF module as the *parameter container*: state-dict keys stay ``plm_encoder.layers.N.*`` etc.
+
+Per layer:  add + RMSNorm (one kernel, also yields the residual stream) -> fused Q|K|V GEMM (hipBLASLt)
+            -> per-head RMSNorm of Q / K + rotary embedding -> causal attention, grouped KV heads (MFMA, per-sequence length)
+            -> O GEMM -> add + RMSNorm -> fused gate|up GEMM -> SwiGLU -> down GEMM.
+Padded layout only ([B, L, .] with ``lens``); there is no packed / varlen, hipGraph, bucketed or ring form of this encoder
+(DESIGN.md section 4 "Qwen3 encoder").
+"""
+from __future__ import annotations
+
+import torch
+from torch.utils.checkpoint import checkpoint
+
+from . import ops
+from .nn import _mm
+
+
+def _sliding_window_in_use(cfg) -> bool:
+    if getattr(cfg, "use_sliding_window", False) and getattr(cfg, "sliding_window", None):
+        return True
+    return any(t != "full_attention" for t in (getattr(cfg, "layer_types", None) or ()))
+
+
+def _rope_type(cfg) -> str:
+    for name in ("rope_parameters", "rope_scaling"):
+        rp = getattr(cfg, name, None)
+        if isinstance(rp, dict):
+            t = rp.get("rope_type", rp.get("type"))
+            if t is not None:
+                return t
+    return "default"
+
+
+def rope_theta(cfg) -> float:
+    rp = getattr(cfg, "rope_parameters", None)
+    if isinstance(rp, dict) and rp.get("rope_theta") is not None:
+        return float(rp["rope_theta"])
+    return float(getattr(cfg, "rope_theta", 10000.0))
+
+
+def head_dim(cfg) -> int:
+    """``config.head_dim`` where the config has one (Qwen3: 128 with hidden 1024 and 16 heads), else hidden_size // heads."""
+    hd = getattr(cfg, "head_dim", None)
+    return int(hd) if hd else cfg.hidden_size // cfg.num_attention_heads
+
+
+def check_supported(plm) -> None:
+    cfg = plm.config
+    problems = []
+    if getattr(cfg, "model_type", None) != "qwen3":
+        problems.append(f"model_type={getattr(cfg, 'model_type', None)!r} (this module takes Qwen3 encoders)")
+    if getattr(cfg, "hidden_act", "silu") != "silu":
+        problems.append(f"hidden_act={cfg.hidden_act!r}")
+    if head_dim(cfg) != 128:
+        problems.append(f"head_dim={head_dim(cfg)} (the causal attention kernels take 128)")
+    if getattr(cfg, "attention_bias", False):
+        problems.append("attention_bias")
+    if _sliding_window_in_use(cfg):
+        problems.append("sliding-window attention")
+    if _rope_type(cfg) != "default":
+        problems.append(f"rope type {_rope_type(cfg)!r} (default rotary embedding only)")
+    if float(getattr(cfg, "attention_dropout", 0.0) or 0.0) != 0.0:
+        problems.append(f"attention_dropout={cfg.attention_dropout} (no probability dropout in the causal kernels)")
+    for name in ("hidden_dropout", "hidden_dropout_prob", "resid_pdrop"):
+        if float(getattr(cfg, name, 0.0) or 0.0) != 0.0:
+            problems.append(f"{name}={getattr(cfg, name)}")
+    heads, kv = getattr(cfg, "num_attention_heads", 0), getattr(cfg, "num_key_value_heads", 0)
+    if not heads or not kv or heads % kv:
+        problems.append(f"{heads} query heads / {kv} KV heads")
+    if problems:
+        raise NotImplementedError("gmlm_amd text-encoder kernels do not cover this PLM: " + "; ".join(problems))
+
+
+_ROPE_TABLES = {}
+
+
+def rope_table(cfg, max_len: int, device) -> torch.Tensor:
+    """fp32 [>= max_len, 2, 64]: cos and sin of position * inv_freq, computed as Qwen3RotaryEmbedding does (default rope type:
+    inv_freq = theta^(-2i/d) in fp32, the products and cos / sin in fp32).  Built ONCE per (device, theta, head dim) for
+    ``max_position_embeddings`` rows (a row depends on its position only, so every shorter sequence reads a prefix) and kept:
+    no host work and no host-to-device copy per encoder call."""
+    d, theta = head_dim(cfg), rope_theta(cfg)
+    device = torch.device(device)
+    rows = max(int(max_len), int(getattr(cfg, "max_position_embeddings", 0) or 0))
+    key = (device.type, device.index, theta, d)
+    hit = _ROPE_TABLES.get(key)
+    if hit is None or hit.shape[0] < rows:
+        inv_freq = 1.0 / (theta ** (torch.arange(0, d, 2, dtype=torch.int64).to(dtype=torch.float) / d))
+        freqs = torch.arange(rows, dtype=torch.float32)[:, None] * inv_freq[None, :]
+        hit = _ROPE_TABLES[key] = torch.stack([freqs.cos(), freqs.sin()], 1).contiguous().to(device)
+    return hit
+
+
+class LayerWeights:
+    """Per-forward view of one Qwen3DecoderLayer: the GEMM operands in the compute dtype (fused ``wqkv`` [q|k|v] and ``wgu``
+    [gate|up], ``wo``, ``wdown``; no autograd history) next to the fp32 masters their gradients go to (``nn._mm``)."""
+    __slots__ = ("wqkv", "wo", "wgu", "wdown", "m_qkv", "m_wo", "m_gu", "m_down", "ln1", "ln2", "qn", "kn")
+
+
+def _layer_masters(layer):
+    sa, mlp = layer.self_attn, layer.mlp
+    return ([sa.q_proj.weight, sa.k_proj.weight, sa.v_proj.weight], sa.o_proj.weight, [mlp.gate_proj.weight, mlp.up_proj.weight],
+            mlp.down_proj.weight)
+
+
+def prepare_weights(plm, cd):
+    """One flat buffer in the compute dtype for all layers' GEMM weights, filled by ONE multi-tensor copy (Q/K/V rows land
+    directly in the fused [(hq + 2 hkv) * 128, P] operand, gate / up rows in the fused [2 I, P] one)."""
+    layers = list(plm.layers)
+    out, srcs, dsts = [], [], []
+    padded = lambda n: (n + 127) // 128 * 128                 # keep every operand 256-byte aligned
+    with torch.no_grad():
+        dev = layers[0].self_attn.q_proj.weight.device if layers else None
+        total = 0
+        for layer in layers:
+            wq, wo, wgu, wd = _layer_masters(layer)
+            total += padded(sum(t.numel() for t in wq)) + padded(wo.numel()) + padded(sum(t.numel() for t in wgu)) + padded(wd.numel())
+        flat = torch.empty(total, dtype=cd, device=dev)
+        off = 0
+
+        def take(rows, cols):
+            nonlocal off
+            v = flat[off:off + rows * cols].view(rows, cols)
+            off += padded(rows * cols)
+            return v
+
+        for layer in layers:
+            wq, wo, wgu, wd = _layer_masters(layer)
+            lw = LayerWeights()
+            lw.wqkv = take(sum(t.shape[0] for t in wq), wq[0].shape[1])
+            lw.wo = take(*wo.shape)
+            lw.wgu = take(sum(t.shape[0] for t in wgu), wgu[0].shape[1])
+            lw.wdown = take(*wd.shape)
+            for fused, parts in ((lw.wqkv, wq), (lw.wgu, wgu)):
+                r = 0
+                for w_ in parts:
+                    dsts.append(fused[r:r + w_.shape[0]])
+                    srcs.append(w_.detach())
+                    r += w_.shape[0]
+            dsts += [lw.wo, lw.wdown]
+            srcs += [wo.detach(), wd.detach()]
+            lw.m_qkv, lw.m_wo, lw.m_gu, lw.m_down = tuple(wq), (wo,), tuple(wgu), (wd,)
+            lw.ln1, lw.ln2 = layer.input_layernorm.weight, layer.post_attention_layernorm.weight
+            lw.qn, lw.kn = layer.self_attn.q_norm.weight, layer.self_attn.k_norm.weight
+            out.append(lw)
+        if dsts:
+            torch._foreach_copy_(dsts, srcs)
+    return out
+
+
+def _layer(lw, stream, branch, lens, cs, hq, hkv, scale, eps):
+    """(residual stream, last branch output) of the previous layer -> the same pair after this layer; the add that joins them
+    is fused into the next RMSNorm."""
+    s1, y1 = ops.add_rmsnorm(stream, branch, lw.ln1, eps)
+    qkv = _mm(y1, lw.wqkv, None, lw.m_qkv)
+    ctx = ops.rope_causal_attention(qkv, lw.qn, lw.kn, cs, lens, hq, hkv, scale, eps)
+    s2, y2 = ops.add_rmsnorm(s1, _mm(ctx, lw.wo, None, lw.m_wo), lw.ln2, eps)
+    m = ops.swiglu(_mm(y2, lw.wgu, None, lw.m_gu))
+    return s2, _mm(m, lw.wdown, None, lw.m_down)
+
+
+def qwen3_encode(plm, input_ids: torch.Tensor, lens: torch.Tensor, cd: torch.dtype, training: bool = False,
+                 gradient_checkpointing: bool = False, weights=None) -> torch.Tensor:
+    """input_ids int [B, L] (left-aligned: padding anywhere past ``lens[b]`` is ignored), lens int32 [B] -> [B, L, P] in ``cd``.
+
+    Positions are 0..L-1 per row; a query sees the keys at or before it that lie below ``lens[b]``.  Rows at or past
+    ``lens[b]`` are computed but never read by the pooling.  ``weights``: optional ``prepare_weights(plm, cd)`` result."""
+    cfg = plm.config
+    b, l = input_ids.shape
+    if l > cfg.max_position_embeddings:
+        raise ValueError(f"sequence length {l} exceeds max_position_embeddings {cfg.max_position_embeddings}")
+    hq, hkv = cfg.num_attention_heads, cfg.num_key_value_heads
+    eps, scale = cfg.rms_norm_eps, head_dim(cfg) ** -0.5
+    x = torch.nn.functional.embedding(input_ids.long(), plm.embed_tokens.weight).to(cd)   # bit-exact row gather
+    cs = rope_table(cfg, l, x.device)
+    if weights is None:
+        weights = prepare_weights(plm, cd)
+    stream, branch = x, None
+    for lw in weights:
+        if gradient_checkpointing and training and torch.is_grad_enabled():
+            stream, branch = checkpoint(_layer, lw, stream, branch, lens, cs, hq, hkv, scale, eps, use_reentrant=False)
+        else:
+            stream, branch = _layer(lw, stream, branch, lens, cs, hq, hkv, scale, eps)
+    return ops.add_rmsnorm(stream, branch, plm.norm.weight, eps)[1]

@@ -316,6 +316,68 @@ size_t gmlm_wgrad_workspace_bytes(int64_t t, int64_t n, int64_t k, int splits);
 int gmlm_wgrad_bf16(const void* dy, int64_t ld_dy, const void* x, int64_t ld_x, int64_t t, int64_t n, int64_t k, int splits,
                     float* out, int64_t ld_out, int flags, void* workspace, size_t workspace_bytes, gmlm_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Row kernels of the pre-norm decoder-style text encoders (Qwen3 geometry).  bf16 or fp32 storage (`dtype`), fp32
+ * arithmetic, one rounding on store; every pointer 16-byte aligned; sums over rows run in a fixed order (no atomics).
+ * ------------------------------------------------------------------------------------------- */
+/* Residual add + RMSNorm over rows of width f (a multiple of 8 (bf16) / 4 (fp32), at most 4096):
+ *   sum = a + b, stored to s in `dtype` (b and s are given together or both NULL: sum = a, nothing stored);
+ *   y = sum * rstd * w with rstd[r] = rsqrt(mean(sum^2) + eps) (fp32 [rows], taken over the STORED sum); w fp32 [f]. */
+int gmlm_add_rmsnorm_fwd(const void* a, const void* b, const float* w, int64_t rows, int64_t f, float eps, void* s, void* y,
+                         float* rstd, int dtype, gmlm_stream_t stream);
+/* s = the sum the forward normalised (its s, or its a when b was NULL); dres (nullable) = the gradient arriving on the
+ * residual stream.  ds = dres + d(sum) is the gradient of a and of b; dw fp32 [f].
+ * workspace: gmlm_add_rmsnorm_bwd_workspace_bytes(rows, f). */
+size_t gmlm_add_rmsnorm_bwd_workspace_bytes(int64_t rows, int64_t f);
+int gmlm_add_rmsnorm_bwd(const void* dy, const void* dres, const void* s, const float* w, const float* rstd, int64_t rows,
+                         int64_t f, void* ds, float* dw, int dtype, void* workspace, size_t workspace_bytes,
+                         gmlm_stream_t stream);
+/* Per-head RMSNorm of Q and K + rotary position embedding (d must be 128).  qkv: `tokens` rows [q (hq heads) | k (hkv) |
+ * v (hkv)] x 128 at row stride qkv_stride; token t sits at position t % seq_len (padded [b, seq_len] layout).
+ * For every Q and K head row x: n = x * rsqrt(mean(x^2) + eps) * weight (q_weight / k_weight, fp32 [128]), then
+ * out[i] = n[i] cos[i] - n[i+64] sin[i], out[i+64] = n[i+64] cos[i] + n[i] sin[i]  (i < 64), written to out
+ * [tokens, (hq + hkv) * 128] at row stride out_stride; V is not touched.  cos_sin: fp32 [max_len, 2, 64] (the cos row,
+ * then the sin row of each position; seq_len <= max_len).  rstd: fp32 [tokens, hq + hkv]. */
+int gmlm_qknorm_rope_fwd(const void* qkv, int64_t qkv_stride, const float* q_weight, const float* k_weight,
+                         const float* cos_sin, int64_t max_len, int64_t tokens, int64_t seq_len, int64_t hq, int64_t hkv,
+                         int64_t d, float eps, void* out, int64_t out_stride, float* rstd, int dtype, gmlm_stream_t stream);
+/* IN PLACE on the first (hq + hkv) * 128 columns of dqkv (row stride dqkv_stride): on entry the gradient of the rotated
+ * Q | K, on return the gradient of the projection output (inverse rotation, then the RMSNorm backward); the V columns
+ * are left alone.  dq_weight / dk_weight: one fp32 [2, 128] buffer (dk_weight == dq_weight + 128).
+ * workspace: gmlm_qknorm_rope_bwd_workspace_bytes(tokens, hq, hkv, dtype). */
+size_t gmlm_qknorm_rope_bwd_workspace_bytes(int64_t tokens, int64_t hq, int64_t hkv, int dtype);
+int gmlm_qknorm_rope_bwd(void* dqkv, int64_t dqkv_stride, const void* qkv, int64_t qkv_stride, const float* q_weight,
+                         const float* k_weight, const float* cos_sin, int64_t max_len, const float* rstd, int64_t tokens,
+                         int64_t seq_len, int64_t hq, int64_t hkv, int64_t d, float* dq_weight, float* dk_weight, int dtype,
+                         void* workspace, size_t workspace_bytes, gmlm_stream_t stream);
+/* SwiGLU: gate_up [rows, 2 * inter] = [gate | up] -> y [rows, inter] = silu(gate) * up; the backward returns the fused
+ * [rows, 2 * inter] gradient.  inter: a multiple of 8 (bf16) / 4 (fp32). */
+int gmlm_swiglu_fwd(const void* gate_up, int64_t rows, int64_t inter, void* y, int dtype, gmlm_stream_t stream);
+int gmlm_swiglu_bwd(const void* dy, const void* gate_up, int64_t rows, int64_t inter, void* dgate_up, int dtype,
+                    gmlm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Causal self-attention with grouped KV heads at head dim 128 (d must be 128, lq == lk, hq % hkv == 0).
+ * q / dq [b, l, hq, 128] and k / v / dk / dv [b, l, hkv, 128], each at its own row stride (a fused [q | k | v] row works
+ * without copies); out / out_lo / dout [b, l, hq, 128] dense; lse / delta [b, hq, l] fp32.  Query head j reads KV head
+ * j / (hq / hkv).  Query i sees the keys <= i that lie below kv_len[b] (int32 [b] or NULL = l); a sequence with
+ * kv_len = 0 has zero output, lse = -inf and zero gradients.  dropout_p must be 0 (no probability dropout here).
+ * out_lo (bf16 only, optional): residual of the output for an exact delta, as in gmlm_attention_d128_*.
+ * dK / dV are summed over the query heads of a group and the query tiles in a fixed order (no atomics, no expanded
+ * K / V): identical calls give identical bits.  Backward workspace: gmlm_attention_causal_d128_workspace_bytes(b, hq, lq).
+ * ------------------------------------------------------------------------------------------- */
+int gmlm_attention_causal_d128_fwd(const void* q, const void* k, const void* v, const int32_t* kv_len, int64_t b, int64_t hq,
+                                   int64_t hkv, int64_t lq, int64_t lk, int64_t d, int64_t q_stride, int64_t k_stride,
+                                   int64_t v_stride, float scale, float dropout_p, void* out, void* out_lo, float* lse,
+                                   int dtype, gmlm_stream_t stream);
+size_t gmlm_attention_causal_d128_workspace_bytes(int64_t b, int64_t hq, int64_t lq);
+int gmlm_attention_causal_d128_bwd(const void* q, const void* k, const void* v, const void* out, const void* out_lo,
+                                   const void* dout, const float* lse, const int32_t* kv_len, int64_t b, int64_t hq,
+                                   int64_t hkv, int64_t lq, int64_t lk, int64_t d, int64_t q_stride, int64_t k_stride,
+                                   int64_t v_stride, float scale, float dropout_p, void* dq, void* dk, void* dv,
+                                   int64_t dq_stride, int64_t dk_stride, int64_t dv_stride, int dtype, void* workspace,
+                                   size_t workspace_bytes, gmlm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

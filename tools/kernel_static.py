@@ -1,0 +1,106 @@
+"""Static comparison of the gfx950 kernels of two builds of libgmlm_hip.so (no GPU needed): per kernel the symbol, the
+VGPR count (AGPRs included), LDS bytes, scratch bytes, and the number of v_mfma / scratch_ / packed-fp32 instructions, from
+the code objects' metadata and disassembly.
+
+    python tools/kernel_static.py --parent PARENT/libgmlm_hip.so --new gmlm_amd/libgmlm_hip.so \
+        --match 'attn_|d128::' --added 'causal128::|rmsnorm_|qknorm_rope_|swiglu_' --out profiles/attn_causal_static.json
+
+``--match``: kernels (demangled name, regex) that must be the same in both builds; ``--added``: kernels only the new build
+has, listed with their figures.  Exit status 1 when a matched kernel differs or is missing.
+"""
+import argparse
+import json
+import os
+import re
+import struct
+import subprocess
+import sys
+import tempfile
+
+LLVM = os.environ.get("ROCM_LLVM", "/opt/rocm/llvm/bin")
+
+
+def code_objects(so, into):
+    """The gfx950 ELF code objects embedded in the .so's offload bundles, one file each."""
+    fat = os.path.join(into, "fatbin")
+    subprocess.run([os.path.join(LLVM, "llvm-objcopy"), "--dump-section", ".hip_fatbin=" + fat, so, os.path.join(into, "so")],
+                   check=True, capture_output=True)
+    blob = open(fat, "rb").read()
+    files, i = [], 0
+    while True:
+        i = blob.find(b"\x7fELF", i)
+        if i < 0:
+            return files
+        shoff, = struct.unpack_from("<Q", blob, i + 0x28)
+        shentsize, shnum = struct.unpack_from("<HH", blob, i + 0x3A)
+        path = os.path.join(into, "co%d.o" % len(files))
+        with open(path, "wb") as f:
+            f.write(blob[i:i + shoff + shentsize * shnum])
+        files.append(path)
+        i += shoff + shentsize * shnum
+
+
+def demangle(names):
+    import torch                                               # the ROCm llvm tools ship no c++filt; torch carries a demangler
+    return {n: torch._C._demangle(n) for n in names}
+
+
+def kernels(so):
+    res = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        for co in code_objects(so, tmp):
+            notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], check=True, capture_output=True, text=True).stdout
+            meta = {}
+            for blk in re.split(r"\n\s*- \.agpr_count:", notes)[1:]:
+                g = lambda key: re.search(r"\." + key + r":\s*(\S+)", blk)
+                if g("name") and g("vgpr_count"):
+                    meta[g("name").group(1)] = dict(vgpr=int(g("vgpr_count").group(1)), lds_bytes=int(g("group_segment_fixed_size").group(1)),
+                                                    scratch_bytes=int(g("private_segment_fixed_size").group(1)))
+            dis = subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", "--mcpu=gfx950", co], check=True, capture_output=True,
+                                 text=True).stdout
+            for m in re.finditer(r"^[0-9a-f]+ <(\w+)>:\n(.*?)(?=^[0-9a-f]+ <|\Z)", dis, re.S | re.M):
+                sym, body = m.group(1), m.group(2)
+                if sym not in meta:
+                    continue
+                ops = re.findall(r"^\s*(\S+)", re.sub(r"//.*", "", body), re.M)
+                d = dict(meta[sym])
+                d.update(v_mfma=sum(o.startswith("v_mfma") for o in ops), scratch_instr=sum(o.startswith("scratch_") for o in ops),
+                         packed_f32=sum(bool(re.match(r"v_pk_\w+_f32", o)) for o in ops), instructions=len(ops),
+                         waves_per_simd=min(8, 512 // ((meta[sym]["vgpr"] + 7) // 8 * 8)) if meta[sym]["vgpr"] else 8)
+                res[sym] = d
+    names = demangle(list(res))
+    return {re.sub(r"^void ", "", names[s]): dict(symbol=s, **d) for s, d in res.items()}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--parent", required=True)
+    ap.add_argument("--new", required=True)
+    ap.add_argument("--match", required=True)
+    ap.add_argument("--added", default=None)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    old, new = kernels(a.parent), kernels(a.new)
+    keys = ("symbol", "vgpr", "lds_bytes", "scratch_bytes", "v_mfma", "scratch_instr", "packed_f32", "instructions")
+    rows, bad = [], 0
+    for name in sorted(k for k in old if re.search(a.match, k)):
+        o, n = old[name], new.get(name)
+        same = n is not None and all(o[k] == n[k] for k in keys)
+        bad += not same
+        rows.append(dict(kernel=name, parent={k: o[k] for k in keys[1:]}, new=None if n is None else {k: n[k] for k in keys[1:]},
+                         unchanged=same))
+    added = [dict(kernel=k, **{x: v for x, v in d.items() if x != "symbol"}) for k, d in sorted(new.items())
+             if a.added and re.search(a.added, k) and k not in old]
+    res = dict(what="per-kernel static figures of two builds of libgmlm_hip.so (same flags): vgpr = .vgpr_count + AGPRs as the code "
+                    "object metadata reports it, instructions / v_mfma / scratch_instr / packed_f32 counted in the disassembly",
+               match=a.match, compared=len(rows), unchanged=len(rows) - bad, existing=rows, added=added)
+    text = json.dumps(res, indent=1)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(text + "\n")
+    print(f"{len(rows)} kernels compared, {len(rows) - bad} unchanged, {len(added)} added")
+    sys.exit(1 if bad else 0)
+
+
+if __name__ == "__main__":
+    main()
