@@ -80,6 +80,71 @@ def test_wgrad_strided_column_slice(dev):
     assert torch.equal(out, ops.wgrad_bf16(dy.contiguous(), x.contiguous()))
 
 
+# Small plans (stages = T // 32 token stages of the main kernel, the rest of T is the combine kernel's token tail): slices
+# shorter than the 4-deep stage ring (1, 2, 3 stages: the prologue issues fewer than 3 stages and the vmcnt selection takes
+# its short branches), the first ring wrap (4, 5) and a second one (9), uneven slices, splits clamped to the stage count,
+# the default plan at a small T (one tile: 256 splits clamped to 40 one-stage slices), and non-square tile grids with
+# tiles * splits below 8, a multiple of 8 and not a multiple of 8 (the XCD remap's q / r split).
+_SMALL_PLANS = [(32 * s, 256, 256, 1) for s in (1, 2, 3, 4, 5, 9)] + [
+    (33, 256, 256, 1), (63, 256, 256, 1), (32 * 5 + 31, 256, 256, 1),               # token tail of 1, 31 and 31 rows
+    (32 * 7, 256, 256, 3),                                                           # slices of 2, 2, 3 stages
+    (32 * 5, 256, 256, 4),                                                           # 1, 1, 1, 2
+    (32 * 9 + 17, 256, 256, 2),                                                      # 4, 5 and a 17-row tail
+    (32 * 3, 256, 256, 8),                                                           # splits clamped to 3
+    (32 * 40 + 5, 256, 256, 0),                                                      # default plan
+    (32 * 7 + 5, 256, 512, 3), (32 * 7 + 5, 512, 256, 4),                            # 2 tiles: 6 and 8 workgroups
+    (32 * 7 + 5, 768, 512, 1), (32 * 7 + 5, 768, 512, 4), (32 * 7 + 5, 768, 512, 3),  # 6 tiles: 6, 24 and 18 workgroups
+]
+
+
+def _int_operands(dev, t, n, k, seed):
+    """Integer-valued bf16 operands, dy in [-3, 3] and x in [-4, 4]: every partial sum is an integer of magnitude at most
+    12 t < 2^24, exact in fp32 whatever the order."""
+    g = torch.Generator(device=dev).manual_seed(seed)
+    dy = torch.randint(-3, 4, (t, n), device=dev, generator=g).bfloat16()
+    x = torch.randint(-4, 5, (t, k), device=dev, generator=g).bfloat16()
+    assert 12 * t < 2 ** 24
+    return dy, x
+
+
+@pytest.mark.parametrize("t,n,k,splits", _SMALL_PLANS, ids=[f"t{t}_n{n}_k{k}_s{s}" for t, n, k, s in _SMALL_PLANS])
+def test_wgrad_small_plans_exact(dev, t, n, k, splits):
+    dy, x = _int_operands(dev, t, n, k, 1000 * t + n + k + splits)
+    exact = (dy.double().t() @ x.double()).float()
+    out = ops.wgrad_bf16(dy, x, splits)
+    assert out.dtype == torch.float32 and torch.equal(out, exact), int((out != exact).sum())
+    plain = ops.wgrad_bf16(dy, x, splits, ops.WGRAD_NO_REMAP)
+    assert torch.equal(plain, exact)
+    # Gaussian data: a mistake that integer data happens to mask; the plain order adds the same partials in the same order
+    dy, x = _operands(dev, t, n, k, 7 * t + n + k + splits)
+    out = ops.wgrad_bf16(dy, x, splits)
+    _check(out, dy, x)
+    assert torch.equal(ops.wgrad_bf16(dy, x, splits, ops.WGRAD_NO_REMAP), out)
+
+
+def test_wgrad_small_plan_strided_and_poisoned(dev):
+    """Column slices of wider tensors at 16-byte-aligned nonzero offsets, a workspace full of NaN (the header: 'no
+    initialisation needed'), output rows padded by four columns that must stay as they were; two slices of 2 and 3 stages,
+    then the default plan (2 tiles -> 128 splits, clamped to 5 one-stage slices), each with a 7-row token tail."""
+    from gmlm_amd._lib import check, lib
+    t, n, k = 32 * 5 + 7, 512, 256
+    wide, xw = _int_operands(dev, t, n + 72, k + 24, 11)
+    dy, x = wide[:, 40:40 + n], xw[:, 8:8 + k]
+    assert dy.stride(0) == n + 72 and x.stride(0) == k + 24 and dy.data_ptr() % 16 == 0 and x.data_ptr() % 16 == 0
+    exact = (dy.double().t() @ x.double()).float()
+    sentinel = -12345.0
+    for splits, flags in ((2, 0), (2, ops.WGRAD_NO_REMAP), (0, 0)):
+        ld_out = k + 4
+        out = torch.full((n, ld_out), sentinel, dtype=torch.float32, device=dev)
+        nbytes = lib().gmlm_wgrad_workspace_bytes(t, n, k, splits)
+        assert nbytes == (splits or 5) * n * k * 4
+        ws = torch.full((nbytes // 4,), float("nan"), dtype=torch.float32, device=dev)
+        check(lib().gmlm_wgrad_bf16(dy.data_ptr(), dy.stride(0), x.data_ptr(), x.stride(0), t, n, k, splits, out.data_ptr(), ld_out,
+                                    flags, ws.data_ptr(), nbytes, torch.cuda.current_stream().cuda_stream), "gmlm_wgrad_bf16")
+        assert torch.equal(out[:, :k], exact), (splits, flags, int((out[:, :k] != exact).sum()))
+        assert bool((out[:, k:] == sentinel).all()), "the padding columns of the output rows were written"
+
+
 @pytest.mark.parametrize("case", ["ragged_n", "short_t", "fp32", "bf16_result", "one_tile"])
 def test_wgrad_unsupported_falls_back(dev, case):
     t, n, k = (4096 + 5, 768, 768) if case == "short_t" else (16384 + 3, 96 if case == "ragged_n" else 768, 768)
