@@ -8,7 +8,7 @@
 // Main kernel, one 256 x 256 tile per workgroup, 8 waves as 2 (n) x 4 (k), each wave 128 x 64 = 8 x 4 accumulators of
 // v_mfma_f32_16x16x32_bf16.  A stage is 32 token rows of dy[:, n0 .. n0 + 256) and of x[:, k0 .. k0 + 256): two 16 KiB images
 // of 512-byte rows, filled by LDS-DMA (global_load_lds_dwordx4, 1 KiB of contiguous LDS per wave-instruction, per-lane
-// source address).  A four-deep ring keeps up to three stages in flight across the one barrier of a stage (counted
+// source address).  A four-deep ring keeps up to three stages in flight across the barriers of a stage (counted
 // vmcnt, raw s_barrier; guide "Pipelining across barriers").  Both MFMA operands want 8 consecutive TOKENS per lane, i.e.
 // a column of the staged rows: they are read with ds_read_b64_tr_b16 (4 rows x 16 columns per 16-lane group).
 //   Swizzle: 16-byte slot s of row r holds chunk s ^ 2 h(r), h(r) = (r & 3) | ((r >> 3) & 1) << 2.  A half-wave's
@@ -16,6 +16,33 @@
 //   i.e. 8 distinct 32-byte bank windows of the 256-byte bank row -> conflict free.  The XOR keeps 32-byte pairs together
 //   (even mask), so a lane's 8 bytes never straddle two slots.  Applied on the DMA SOURCE address (the LDS side of an
 //   LDS-DMA is lane-linear) and again on the read.
+//
+// Schedules (template parameter; both give every accumulator the stages of its slice in order, one MFMA per stage, so
+// the partial tiles are bit-identical):
+//   ONE_PHASE (flag GMLM_WGRAD_ONE_PHASE): one barrier per stage; all 8 waves wait, read and multiply in lock-step.
+//   TWO_PHASE (default): a stage is a READ phase (the 24 transposed reads, closed by lgkmcnt(0)) and an MMA phase (the 32
+//   MFMAs), each opened by a workgroup barrier: A_s opens READ(s), B_s opens MMA(s).  Group 0 = waves 0-3, group 1 = waves
+//   4-7; the two waves of a SIMD are w and w + 4, one of each group.  Group 1 executes one extra barrier before its loop and
+//   group 0 one after, so group 1 runs exactly one phase behind: on every SIMD one wave issues MFMAs while the other
+//   reads LDS and waits.  With the barriers of the workgroup numbered #0, #1, ...:
+//                  READ(s) is after      MMA(s) is after
+//       group 0        #2s                   #2s+1
+//       group 1        #2s+1                 #2s+2
+//   Rules the loop keeps (correctness is argued from these, not from clean runs):
+//   RAW   stage s is first read after #2s (by group 0), so EVERY wave retires its own DMA pieces of stage s with a counted
+//         vmcnt before it arrives at #2s: group 0 in front of its A_s (= #2s); group 1 in front of its B_(s-1) (= #2s), or
+//         of its extra barrier #0 when s = 0 - one barrier earlier than its own A_s = #2s+1, which would be too late.
+//   WAR   stage s+3 lands in the slot of stage s-1.  Group 1 reads stage s-1 in the phase that #2s ends (group 0 one phase
+//         earlier), and every READ phase ends with lgkmcnt(0) in front of its barrier: a wave past #2s knows those reads
+//         are done.  A wave issues stage s+3 at the start of its own READ(s): after #2s (group 0), after #2s+1 (group 1).
+//   vmcnt immediates are 4 x (issued - s - 1) from `issued` at the point of the wait (group 1 waits for s+1 at the end of
+//         READ(s), i.e. after the issue of that phase: one more stage issued than group 0 had at its wait for s in the same
+//         iteration): 8 in the steady state, 4 / 0 only while the slice drains or is shorter than the ring (ns = 1, 2, 3:
+//         the prologue issues ns stages and the short branches are taken).
+//   Barrier count: 2 ns + 1 for both groups and every ns >= 1 (#0 .. #2ns; the last one is group 0's extra barrier and
+//         group 1's B_(ns-1)).
+//   The reads stay in READ and the MFMAs in MMA: sched_barrier(0) on both sides of the MFMA block, and the lgkmcnt(0) asm
+//   is a memory clobber (the compiler's own progressive lgkmcnt waits inside the MMA block are then no-ops).
 #include "attn_common.hpp"
 
 namespace gmlm {
@@ -56,6 +83,7 @@ __device__ __forceinline__ void wg_dma(const bf16_t* base, uint32_t off, uint32_
                : "=&s"(keep) : "v"(off), "s"(base), "s"(dst) : "memory");
 }
 
+template <bool TWO_PHASE>
 __global__ __launch_bounds__(wg::NW * 64, 1) void wgrad_bf16_kernel(WgradParams p) {
   using namespace wg;
   extern __shared__ __attribute__((aligned(1024))) unsigned char smem_dyn[];
@@ -108,22 +136,17 @@ __global__ __launch_bounds__(wg::NW * 64, 1) void wgrad_bf16_kernel(WgradParams 
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[m][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  const int pre = ns < NBUF - 1 ? ns : NBUF - 1;
-  for (int s = 0; s < pre; ++s) issue(s);
-  int issued = pre;
-  for (int s = 0; s < ns; ++s) {
-    // stage s has landed once at most (issued - s - 1) younger stages are outstanding (vmcnt counts in issue order)
+  // stage s has landed once at most (issued - s - 1) younger stages are outstanding (vmcnt counts in issue order)
+  auto wait_stage = [&](int s, int issued) {
     const int younger = issued - s - 1;
     if (younger >= 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
     else if (younger == 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     static_assert(VM_PER_STAGE == 4 && NBUF == 4, "vmcnt immediates above assume 4 per stage and 2 younger stages");
-    // every wave's DMA of stage s has landed, and every wave has finished computing stage s - 1 (its slot is free)
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    if (issued < ns) { issue(issued); ++issued; }
+  };
+  bf16x8 a[8], b[4];
+  auto read_stage = [&](int s) {
     const unsigned char* img = smem_dyn + (s % NBUF) * STAGE;
-    bf16x8 a[8], b[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(GMLM_LDS3(bf16x4, img + boff[j]));
@@ -136,10 +159,48 @@ __global__ __launch_bounds__(wg::NW * 64, 1) void wgrad_bf16_kernel(WgradParams 
       const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(GMLM_LDS3(bf16x4, img + aoff[m] + 4 * TILE * 2));
       a[m] = bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
     }
+  };
+  auto mma_stage = [&] {
 #pragma unroll
     for (int m = 0; m < 8; ++m)
 #pragma unroll
       for (int j = 0; j < 4; ++j) acc[m][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[m], b[j], acc[m][j], 0, 0, 0);
+  };
+
+  const int pre = ns < NBUF - 1 ? ns : NBUF - 1;
+  for (int s = 0; s < pre; ++s) issue(s);
+  int issued = pre;
+  if constexpr (!TWO_PHASE) {
+    for (int s = 0; s < ns; ++s) {
+      wait_stage(s, issued);
+      // every wave's DMA of stage s has landed, and every wave has finished computing stage s - 1 (its slot is free)
+      __builtin_amdgcn_s_barrier();
+      asm volatile("" ::: "memory");
+      if (issued < ns) { issue(issued); ++issued; }
+      read_stage(s);
+      mma_stage();
+    }
+  } else {
+    const int grp = w >> 2;                  // wave-uniform (w is an SGPR): the branches below are scalar
+    if (grp == 1) {
+      wait_stage(0, issued);                 // RAW for stage 0: in front of #0
+      __builtin_amdgcn_s_barrier();          // #0
+    }
+    for (int s = 0; s < ns; ++s) {
+      if (grp == 0) wait_stage(s, issued);   // RAW for stage s: in front of #2s
+      __builtin_amdgcn_s_barrier();          // A_s: #2s (group 0), #2s+1 (group 1)
+      asm volatile("" ::: "memory");
+      if (issued < ns) { issue(issued); ++issued; }   // stage s+3 into the slot of s-1 (WAR: past #2s)
+      read_stage(s);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      if (grp == 1 && s + 1 < ns) wait_stage(s + 1, issued);   // RAW for stage s+1: in front of #2(s+1)
+      __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_s_barrier();          // B_s: #2s+1 (group 0), #2s+2 (group 1)
+      __builtin_amdgcn_sched_barrier(0);
+      mma_stage();
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    if (grp == 0) __builtin_amdgcn_s_barrier();       // #2ns
   }
 
   // C/D map of 16x16x32: column (k) = lane & 15, row (n) = 4 (lane >> 4) + register
@@ -211,7 +272,7 @@ extern "C" int gmlm_wgrad_bf16(const void* dy, int64_t ld_dy, const void* x, int
   GMLM_REQUIRE(ld_dy % 8 == 0 && ld_x % 8 == 0 && ld_out % 4 == 0, "wgrad_bf16: row strides must keep rows 16-byte aligned");
   GMLM_REQUIRE(((uintptr_t)dy | (uintptr_t)x | (uintptr_t)out | (uintptr_t)workspace) % 16 == 0,
                "wgrad_bf16: pointers must be 16-byte aligned");
-  GMLM_REQUIRE(splits >= 0 && (flags & ~GMLM_WGRAD_NO_REMAP) == 0, "wgrad_bf16: bad splits / flags");
+  GMLM_REQUIRE(splits >= 0 && (flags & ~(GMLM_WGRAD_NO_REMAP | GMLM_WGRAD_ONE_PHASE)) == 0, "wgrad_bf16: bad splits / flags");
   // the LDS-DMA source offset of a lane is 32-bit: 16 rows of either operand must stay below 4 GiB
   GMLM_REQUIRE(ld_dy < (1ll << 26) && ld_x < (1ll << 26), "wgrad_bf16: row stride too large");
   const int s = wgrad_splits(t, n, k, splits);
@@ -225,13 +286,18 @@ extern "C" int gmlm_wgrad_bf16(const void* dy, int64_t ld_dy, const void* x, int
   static std::once_flag once;
   static hipError_t attr = hipSuccess;
   std::call_once(once, [] {
-    attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_bf16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, wg::LDS);
+    attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_bf16_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               wg::LDS);
+    if (attr == hipSuccess)
+      attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_bf16_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 wg::LDS);
   });
   GMLM_HIP(attr);
   hipStream_t st = as_stream(stream);
   WgradParams p{(const bf16_t*)dy, (const bf16_t*)x, (float*)workspace, ld_dy, ld_x, n, k, (int32_t)stages, s, (int32_t)tiles_k,
                 (int32_t)tiles, (flags & GMLM_WGRAD_NO_REMAP) ? 0 : 1};
-  wgrad_bf16_kernel<<<(unsigned)(tiles * s), wg::NW * 64, wg::LDS, st>>>(p);
+  if (flags & GMLM_WGRAD_ONE_PHASE) wgrad_bf16_kernel<false><<<(unsigned)(tiles * s), wg::NW * 64, wg::LDS, st>>>(p);
+  else wgrad_bf16_kernel<true><<<(unsigned)(tiles * s), wg::NW * 64, wg::LDS, st>>>(p);
   GMLM_LAUNCH_CHECK();
   const int64_t items = n * (k / 4);
   wgrad_combine_kernel<<<(unsigned)((items + 255) / 256), 256, 0, st>>>((const float*)workspace, s, n, k, (const bf16_t*)dy, ld_dy,

@@ -187,6 +187,7 @@ def column_sum(x: torch.Tensor) -> torch.Tensor:
 
 WGRAD_TILE = 256           # N and K granularity of gmlm_wgrad_bf16
 WGRAD_NO_REMAP = 1         # gmlm_wgrad_bf16 flag: plain workgroup order
+WGRAD_ONE_PHASE = 2        # gmlm_wgrad_bf16 flag: the one-barrier main loop (default: two wave groups a phase apart)
 
 
 def wgrad_bf16(dy: torch.Tensor, x: torch.Tensor, splits: int = 0, flags: int = 0) -> torch.Tensor:

@@ -308,10 +308,12 @@ int gmlm_bias_gelu_bwd(const void* dy, const void* x, const float* bias, int64_t
  * N and K multiples of 256, T >= 32, row strides multiples of 8 elements (4 for out), pointers 16-byte aligned.
  * T is cut into `splits` contiguous slices (0 = the default plan: about 256 workgroups); each slice of each 256 x 256
  * tile goes to a fp32 partial in the workspace, which a second launch adds in slice order: deterministic.
- * flags: GMLM_WGRAD_NO_REMAP = plain workgroup order (no XCD grouping of the slices).
+ * flags: GMLM_WGRAD_NO_REMAP = plain workgroup order (no XCD grouping of the slices); GMLM_WGRAD_ONE_PHASE = the one-barrier
+ * main loop (all waves read, then multiply, in lock-step) instead of the default two wave groups a phase apart; same bits.
  * workspace: gmlm_wgrad_workspace_bytes(T, N, K, splits), no initialisation needed.
  * ------------------------------------------------------------------------------------------- */
 #define GMLM_WGRAD_NO_REMAP 1
+#define GMLM_WGRAD_ONE_PHASE 2
 size_t gmlm_wgrad_workspace_bytes(int64_t t, int64_t n, int64_t k, int splits);
 int gmlm_wgrad_bf16(const void* dy, int64_t ld_dy, const void* x, int64_t ld_x, int64_t t, int64_t n, int64_t k, int splits,
                     float* out, int64_t ld_out, int flags, void* workspace, size_t workspace_bytes, gmlm_stream_t stream);

@@ -1,7 +1,10 @@
 """Weight-gradient GEMM of the BERT shapes: the native split-K kernel (ops.wgrad_bf16, nn.NATIVE_WGRAD = True) against the
 library path (batched hipBLASLt GEMM with fp32 output + slice sum, nn.NATIVE_WGRAD = False), random bf16 operands, through
-nn._splitk_wgrad.  usage: [T=tokens] [GEOMETRY=base|mini] [SPLITS=s,s,...] [NO_REMAP=1] python tools/ubench/wgrad_native.py
-SPLITS / NO_REMAP time the native kernel alone at other slice counts / without the XCD grouping (ops.wgrad_bf16 direct)."""
+nn._splitk_wgrad.  usage: [T=tokens] [GEOMETRY=base|mini] [SPLITS=s,s,...] [NO_REMAP=1] [ONE_PHASE=1] [AB=rounds]
+python tools/ubench/wgrad_native.py
+SPLITS / NO_REMAP / ONE_PHASE time the native kernel alone at other slice counts / without the XCD grouping / with the
+one-barrier main loop (ops.wgrad_bf16 direct).  AB=r skips the library comparison and alternates the two main-loop schedules
+instead, r rounds of ONE_PHASE / default per shape in this one process at the default plan, every run printed."""
 import os
 import sys
 
@@ -13,7 +16,8 @@ from gmlm_amd import nn, ops  # noqa: E402
 dev = torch.device("cuda")
 T = int(os.environ.get("T", "91712"))
 SPLITS = [int(v) for v in os.environ.get("SPLITS", "").split(",") if v]
-FLAGS = ops.WGRAD_NO_REMAP if os.environ.get("NO_REMAP") else 0
+FLAGS = (ops.WGRAD_NO_REMAP if os.environ.get("NO_REMAP") else 0) | (ops.WGRAD_ONE_PHASE if os.environ.get("ONE_PHASE") else 0)
+AB = int(os.environ.get("AB", "0"))
 SHAPES = {"base": (("qkv", 2304, 768), ("o", 768, 768), ("ffn1", 3072, 768), ("ffn2", 768, 3072)),
           "mini": (("qkv", 768, 256), ("o", 256, 256), ("ffn1", 1024, 256), ("ffn2", 256, 1024))}[os.environ.get("GEOMETRY", "base")]
 
@@ -41,6 +45,19 @@ for name, n, k in SHAPES:
     dy = torch.randn(T, n, device=dev, generator=g).bfloat16()
     x = torch.randn(T, k, device=dev, generator=g).bfloat16()
     fl = 2.0 * T * n * k
+    if AB:
+        base = FLAGS & ~ops.WGRAD_ONE_PHASE
+        assert torch.equal(ops.wgrad_bf16(dy, x, flags=base), ops.wgrad_bf16(dy, x, flags=base | ops.WGRAD_ONE_PHASE))
+        one, two = [], []
+        timeit(lambda: ops.wgrad_bf16(dy, x, flags=base | ops.WGRAD_ONE_PHASE), 100)    # untimed: clocks and caches settle
+        timeit(lambda: ops.wgrad_bf16(dy, x, flags=base), 100)
+        for _ in range(AB):
+            one.append(timeit(lambda: ops.wgrad_bf16(dy, x, flags=base | ops.WGRAD_ONE_PHASE), 100))
+            two.append(timeit(lambda: ops.wgrad_bf16(dy, x, flags=base), 100))
+        print(f"{name:5s} {n:5d}x{k:<5d} T={T} flags={base}  one-phase " + " ".join(f"{v:6.1f}" for v in one) + "   default "
+              + " ".join(f"{v:6.1f}" for v in two) + f" us   means {sum(one) / AB:6.1f} / {sum(two) / AB:6.1f}"
+              f"  x{sum(one) / sum(two):4.2f}  every default run faster: {max(two) < min(one)}", flush=True)
+        continue
     nn.NATIVE_WGRAD = True
     out = nn._splitk_wgrad(dy, x, keep_fp32=True)
     exact = dy.double().t() @ x.double()
