@@ -62,6 +62,11 @@ SIGNATURES = {
     "gmlm_attention_causal_d128_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "gmlm_attention_causal_d128_bwd": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
                                                  _i64, _f32, _f32, _p, _p, _p, _i64, _i64, _i64, _i32, _p, _sz, _p]),
+    "gmlm_attention_causal_d128_varlen_fwd": (C.c_int, [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32,
+                                                        _f32, _p, _p, _p, _i32, _p]),
+    "gmlm_attention_causal_d128_varlen_workspace_bytes": (_sz, [_i64, _i64]),
+    "gmlm_attention_causal_d128_varlen_bwd": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
+                                                        _i64, _i64, _f32, _f32, _p, _p, _p, _i64, _i64, _i64, _i32, _p, _sz, _p]),
     "gmlm_add_rmsnorm_fwd": (C.c_int, [_p, _p, _p, _i64, _i64, _f32, _p, _p, _p, _i32, _p]),
     "gmlm_add_rmsnorm_bwd_workspace_bytes": (_sz, [_i64, _i64]),
     "gmlm_add_rmsnorm_bwd": (C.c_int, [_p, _p, _p, _p, _p, _i64, _i64, _p, _p, _i32, _p, _sz, _p]),
@@ -69,6 +74,9 @@ SIGNATURES = {
     "gmlm_qknorm_rope_bwd_workspace_bytes": (_sz, [_i64, _i64, _i64, _i32]),
     "gmlm_qknorm_rope_bwd": (C.c_int, [_p, _i64, _p, _i64, _p, _p, _p, _i64, _p, _i64, _i64, _i64, _i64, _i64, _p, _p, _i32, _p,
                                        _sz, _p]),
+    "gmlm_qknorm_rope_pos_fwd": (C.c_int, [_p, _i64, _p, _p, _p, _i64, _i64, _p, _i64, _i64, _i64, _f32, _p, _i64, _p, _i32, _p]),
+    "gmlm_qknorm_rope_pos_bwd": (C.c_int, [_p, _i64, _p, _i64, _p, _p, _p, _i64, _p, _i64, _p, _i64, _i64, _i64, _p, _p, _i32, _p,
+                                           _sz, _p]),
     "gmlm_swiglu_fwd": (C.c_int, [_p, _i64, _i64, _p, _i32, _p]),
     "gmlm_swiglu_bwd": (C.c_int, [_p, _p, _i64, _i64, _p, _i32, _p]),
     "gmlm_embed_sum_fwd": (C.c_int, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _i32, _p, _p]),

@@ -1,7 +1,8 @@
 // Causal attention with grouped KV heads at head dim 128, forward + backward, gfx950 MFMA (gmlm_attention_causal_d128_*):
 // the self-attention of a Qwen3-geometry text encoder (hq query heads share hkv KV heads, query i sees keys 0..i of its own
 // sequence and, of those, the ones below kv_len).  Padded layout [b, l, heads, 128] with per-operand row strides, so the
-// fused [q | k | v] projection output is read (and its gradient written) without copies.
+// fused [q | k | v] projection output is read (and its gradient written) without copies; or packed layout [T, heads, 128]
+// (gmlm_attention_causal_d128_varlen_*): the same kernels with AttnParams::cu set, sequence i = rows [cu[i], cu[i + 1]).
 // Forward and dQ ARE the streaming bodies of attn_stream.hpp, instantiated with their CAUSAL and GQA template flags (defaults
 // false: the existing kernels' code objects are unchanged, profiles/attn_causal_static.json) at the tiling of attn_d128.hip
 // (4 waves, 128 query rows per workgroup, bf16: 64-row K / V tiles double-buffered, fp32: 32-row tiles in one buffer); delta is
@@ -33,9 +34,9 @@ template <typename T> struct Cfg;
 template <> struct Cfg<bf16_t> { static constexpr int KT = 64, QT = 32; static constexpr bool DBUF = true; };
 template <> struct Cfg<float> { static constexpr int KT = 32, QT = 32; static constexpr bool DBUF = false; };
 
-__device__ __forceinline__ int64_t clamp_kvlen(const AttnParams& p, int64_t b) {
-  int64_t kvlen = p.lk;
-  if (p.kv_len) { kvlen = p.kv_len[b]; if (kvlen > p.lk) kvlen = p.lk; if (kvlen < 0) kvlen = 0; }
+__device__ __forceinline__ int64_t clamp_kvlen(const AttnParams& p, int64_t b, int64_t lk_) {
+  int64_t kvlen = lk_;
+  if (p.kv_len) { kvlen = p.kv_len[b]; if (kvlen > lk_) kvlen = lk_; if (kvlen < 0) kvlen = 0; }
   return kvlen;
 }
 
@@ -88,10 +89,12 @@ __global__ __launch_bounds__(NT) void dkv_kernel(Params x) {
   const int64_t hkv = p.h / x.group, pairs = p.b * hkv, item = blockIdx.x;
   const int64_t kt = item / pairs, bh = item % pairs;
   const int64_t b = bh / hkv, kvh = bh % hkv;
-  const int64_t l_ = p.lq, base = b * p.lq;
+  // padded: sequence b owns rows [b * lq, (b + 1) * lq); packed: rows [cu[b], cu[b + 1]) of lq = T rows in all (block-uniform)
+  int64_t l_ = p.lq, base = b * p.lq;
+  if (p.cu) { base = p.cu[b]; l_ = p.cu[b + 1] - base; }
   const int64_t k_tile0 = kt * BQ;
-  if (k_tile0 >= l_) return;
-  const int64_t kvlen = clamp_kvlen(p, b);
+  if (k_tile0 >= l_) return;                // also a packed sequence of length 0: before any operand load
+  const int64_t kvlen = clamp_kvlen(p, b, l_);
   const int64_t k_wave0 = k_tile0 + w * 32, key = k_wave0 + r;
   const bool key_in = key < l_;            // row exists in memory
   const bool key_ok = key < kvlen;         // takes part in the softmax
@@ -126,7 +129,8 @@ __global__ __launch_bounds__(NT) void dkv_kernel(Params x) {
     qr.init(p.q_stride, tid);
     dor.init(x.dout_stride, tid);
     for (int g = 0; g < x.group; ++g) {
-      const int64_t hd = kvh * x.group + g, lse_base = (b * p.h + hd) * p.lq;
+      const int64_t hd = kvh * x.group + g;
+      const int64_t lse_base = p.cu ? hd * p.lq + base : (b * p.h + hd) * p.lq;   // [hq, T] or [b, hq, l], as seq_view()
       const T* qg = static_cast<const T*>(p.q) + base * p.q_stride + hd * D;
       const T* dog = static_cast<const T*>(p.dout) + base * x.dout_stride + hd * D;
       const float* lse_g = p.lse + lse_base;
@@ -267,6 +271,23 @@ static int setup(const char* who, Params& x, const void* q, const void* k, const
   return GMLM_OK;
 }
 
+// packed (varlen) layout: `seqs` sequences, sequence i = rows [cu[i], cu[i + 1]) of `rows` packed rows, none longer than
+// max_len.  Same kernels with AttnParams::cu set: b = seqs, lq = lk = rows (lse / delta [hq, rows]); a tile past its
+// sequence returns block-uniformly.
+static int setup_varlen(const char* who, Params& x, const void* q, const void* k, const void* v, const int32_t* cu, int64_t seqs,
+                        int64_t max_len, int64_t rows, int64_t hq, int64_t hkv, int64_t d, int64_t q_stride, int64_t k_stride,
+                        int64_t v_stride, float scale, float dropout_p, int dtype) {
+  GMLM_REQUIRE(cu, "%s: null cu_seqlens", who);
+  GMLM_REQUIRE(max_len > 0, "%s: max_len %ld must be positive", who, (long)max_len);
+  GMLM_REQUIRE(seqs >= 0 && rows >= 0 && rows < ((int64_t)1 << 30), "%s: %ld packed rows (must be >= 0 and < 2^30)", who, (long)rows);
+  GMLM_REQUIRE(max_len < ((int64_t)1 << 30) && seqs < ((int64_t)1 << 30), "%s: bad sizes", who);
+  int rc = setup(who, x, q, k, v, nullptr, 0, hq, hkv, 0, 0, d, q_stride, k_stride, v_stride, scale, dropout_p, dtype);
+  if (rc != GMLM_OK) return rc;
+  GMLM_REQUIRE(cdiv(max_len, BQ) * seqs * hq < ((int64_t)1 << 31), "%s: too many work items", who);
+  x.a.b = seqs; x.a.lq = x.a.lk = rows; x.a.cu = cu;
+  return GMLM_OK;
+}
+
 }  // namespace causal128
 }  // namespace gmlm
 
@@ -344,6 +365,80 @@ extern "C" int gmlm_attention_causal_d128_bwd(const void* q, const void* k, cons
   GMLM_CAUSAL_LAUNCH(dq_kernel, gq, st, x);
   GMLM_LAUNCH_CHECK();
   const dim3 gk((unsigned)(cdiv(lk, BQ) * b * hkv));
+  GMLM_CAUSAL_LAUNCH(dkv_kernel, gk, st, x);
+  GMLM_LAUNCH_CHECK();
+  return GMLM_OK;
+}
+
+extern "C" int gmlm_attention_causal_d128_varlen_fwd(const void* q, const void* k, const void* v, const int32_t* cu_seqlens,
+                                                     int64_t num_seqs, int64_t max_len, int64_t total_rows, int64_t hq,
+                                                     int64_t hkv, int64_t d, int64_t q_stride, int64_t k_stride, int64_t v_stride,
+                                                     float scale, float dropout_p, void* out, void* out_lo, float* lse, int dtype,
+                                                     gmlm_stream_t stream) {
+  static const char* who = "attention_causal_d128_varlen_fwd";
+  Params x;
+  int rc = setup_varlen(who, x, q, k, v, cu_seqlens, num_seqs, max_len, total_rows, hq, hkv, d, q_stride, k_stride, v_stride, scale,
+                        dropout_p, dtype);
+  if (rc != GMLM_OK) return rc;
+  GMLM_REQUIRE(!out_lo || (dtype == GMLM_BF16 && aligned16(out_lo)), "%s: out_lo is the bf16 residual of a bf16 output (16-byte aligned)", who);
+  if (num_seqs == 0 || total_rows == 0) return GMLM_OK;
+  if ((rc = attn_stride_check(who, "q", q, q_stride, hq * 128, dtype)) != GMLM_OK) return rc;
+  if ((rc = attn_stride_check(who, "k", k, k_stride, hkv * 128, dtype)) != GMLM_OK) return rc;
+  if ((rc = attn_stride_check(who, "v", v, v_stride, hkv * 128, dtype)) != GMLM_OK) return rc;
+  GMLM_REQUIRE(out && aligned16(out), "%s: null or misaligned out", who);
+  x.a.o_w = out; x.a.o_lo_w = out_lo; x.a.lse_w = lse;
+  hipStream_t st = as_stream(stream);
+  const dim3 grid((unsigned)(cdiv(max_len, BQ) * num_seqs * hq));
+  GMLM_CAUSAL_LAUNCH(fwd_kernel, grid, st, x);
+  GMLM_LAUNCH_CHECK();
+  return GMLM_OK;
+}
+
+extern "C" size_t gmlm_attention_causal_d128_varlen_workspace_bytes(int64_t total_rows, int64_t hq) {
+  return (size_t)(total_rows * hq > 0 ? total_rows * hq : 1) * sizeof(float);   // delta [hq, total_rows]
+}
+
+extern "C" int gmlm_attention_causal_d128_varlen_bwd(const void* q, const void* k, const void* v, const void* out,
+                                                     const void* out_lo, const void* dout, const float* lse,
+                                                     const int32_t* cu_seqlens, int64_t num_seqs, int64_t max_len,
+                                                     int64_t total_rows, int64_t hq, int64_t hkv, int64_t d, int64_t q_stride,
+                                                     int64_t k_stride, int64_t v_stride, float scale, float dropout_p, void* dq,
+                                                     void* dk, void* dv, int64_t dq_stride, int64_t dk_stride, int64_t dv_stride,
+                                                     int dtype, void* workspace, size_t workspace_bytes, gmlm_stream_t stream) {
+  static const char* who = "attention_causal_d128_varlen_bwd";
+  Params x;
+  int rc = setup_varlen(who, x, q, k, v, cu_seqlens, num_seqs, max_len, total_rows, hq, hkv, d, q_stride, k_stride, v_stride, scale,
+                        dropout_p, dtype);
+  if (rc != GMLM_OK) return rc;
+  GMLM_REQUIRE(!out_lo || (dtype == GMLM_BF16 && aligned16(out_lo)), "%s: out_lo is the bf16 residual of a bf16 output (16-byte aligned)", who);
+  if (num_seqs == 0 || total_rows == 0) return GMLM_OK;
+  if ((rc = attn_stride_check(who, "q", q, q_stride, hq * 128, dtype)) != GMLM_OK) return rc;
+  if ((rc = attn_stride_check(who, "k", k, k_stride, hkv * 128, dtype)) != GMLM_OK) return rc;
+  if ((rc = attn_stride_check(who, "v", v, v_stride, hkv * 128, dtype)) != GMLM_OK) return rc;
+  if ((rc = attn_stride_check(who, "dq", dq, dq_stride, hq * 128, dtype)) != GMLM_OK) return rc;
+  if ((rc = attn_stride_check(who, "dk", dk, dk_stride, hkv * 128, dtype)) != GMLM_OK) return rc;
+  if ((rc = attn_stride_check(who, "dv", dv, dv_stride, hkv * 128, dtype)) != GMLM_OK) return rc;
+  GMLM_REQUIRE(out && dout && lse && aligned16(out) && aligned16(dout), "%s: null or misaligned out/dout/lse", who);
+  if (!workspace || workspace_bytes < gmlm_attention_causal_d128_varlen_workspace_bytes(total_rows, hq)) {
+    set_error("%s: workspace too small", who);
+    return GMLM_EWORKSPACE;
+  }
+  AttnParams& p = x.a;
+  p.out = out; p.out_lo = out_lo; p.dout = dout; p.lse = lse;
+  p.delta = static_cast<float*>(workspace);
+  p.dq = dq; p.dk = dk; p.dv = dv;
+  p.dq_stride = dq_stride; p.dk_stride = dk_stride; p.dv_stride = dv_stride;
+  hipStream_t st = as_stream(stream);
+  const int64_t rows = total_rows * hq;                         // delta as one sequence of total_rows: [hq, total_rows]
+  if (dtype == GMLM_BF16)
+    delta_kernel<bf16_t><<<(unsigned)cdiv(rows * 16, 256), 256, 0, st>>>((const bf16_t*)out, (const bf16_t*)out_lo, (const bf16_t*)dout, rows, total_rows, hq, p.delta);
+  else
+    delta_kernel<float><<<(unsigned)cdiv(rows * 32, 256), 256, 0, st>>>((const float*)out, nullptr, (const float*)dout, rows, total_rows, hq, p.delta);
+  GMLM_LAUNCH_CHECK();
+  const dim3 gq((unsigned)(cdiv(max_len, BQ) * num_seqs * hq));
+  GMLM_CAUSAL_LAUNCH(dq_kernel, gq, st, x);
+  GMLM_LAUNCH_CHECK();
+  const dim3 gk((unsigned)(cdiv(max_len, BQ) * num_seqs * hkv));
   GMLM_CAUSAL_LAUNCH(dkv_kernel, gk, st, x);
   GMLM_LAUNCH_CHECK();
   return GMLM_OK;

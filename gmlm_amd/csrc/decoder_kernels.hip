@@ -141,16 +141,29 @@ struct RmsDwFn {
 // Q / K head norm + rotary embedding.  A head row of 128 elements = LPR lanes x 16 bytes (16 lanes bf16, 32 lanes fp32);
 // element i pairs with i + 64, i.e. lane j with lane j ^ (LPR / 2): one cross-lane exchange, no LDS.
 //   n = x * rsqrt(mean(x^2) + eps) * w;   out[i] = n[i] cos[i] - n[i + 64] sin[i],  out[i + 64] = n[i + 64] cos[i] + n[i] sin[i]
-// cs: fp32 [max_len, 2, 64] (cos row, then sin row) of the token's position  row % seq_len.
+// cs: fp32 [max_len, 2, 64] (cos row, then sin row) of the token's position: row % seq_len (padded [b, seq_len] layout), or,
+// when pos_ids is given (packed rows), pos_ids[row] clamped into [0, max_len) so that no position reads outside the table.
 // ------------------------------------------------------------------------------------------------
 constexpr int kHeadDim = 128;
+
+// pos_ids is a kernel argument: the branch is uniform over the grid
+__device__ __forceinline__ const float* rope_row(const float* __restrict__ cs, int64_t t, int64_t seq_len,
+                                                 const int32_t* __restrict__ pos_ids, int64_t max_len) {
+  if (pos_ids) {
+    int64_t pos = pos_ids[t];
+    pos = pos < 0 ? 0 : (pos >= max_len ? max_len - 1 : pos);
+    return cs + pos * 128;
+  }
+  return cs + (t % seq_len) * 128;
+}
 
 template <typename T>
 __global__ __launch_bounds__(256) void qknorm_rope_fwd_kernel(const T* __restrict__ qkv, int64_t in_stride,
                                                                const float* __restrict__ qw, const float* __restrict__ kw,
                                                                const float* __restrict__ cs, int64_t tokens, int64_t seq_len,
                                                                int hq, int hkv, float eps, T* __restrict__ out,
-                                                               int64_t out_stride, float* __restrict__ rstd_o) {
+                                                               int64_t out_stride, float* __restrict__ rstd_o,
+                                                               const int32_t* __restrict__ pos_ids, int64_t max_len) {
   constexpr int V = Store<T>::kVec, LPR = kHeadDim / V;
   const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int lr = (int)(gid % LPR), nh = hq + hkv;
@@ -162,7 +175,7 @@ __global__ __launch_bounds__(256) void qknorm_rope_fwd_kernel(const T* __restric
   Store<T>::ldv(qkv + t * in_stride + (int64_t)hd * kHeadDim + lr * V, x);
   load_f32<V>((hd < hq ? qw : kw) + lr * V, wv);
   const int col = (lr * V) & 63;
-  const float* csr = cs + (t % seq_len) * 128;
+  const float* csr = rope_row(cs, t, seq_len, pos_ids, max_len);
   load_f32<V>(csr + col, c);
   load_f32<V>(csr + 64 + col, sn);
   float sq = 0.f;
@@ -192,7 +205,8 @@ __global__ __launch_bounds__(256) void qknorm_rope_bwd_kernel(T* __restrict__ dq
                                                                int64_t in_stride, const float* __restrict__ qw,
                                                                const float* __restrict__ kw, const float* __restrict__ cs,
                                                                const float* __restrict__ rstd, int64_t tokens, int64_t seq_len,
-                                                               int hq, int hkv, float* __restrict__ partial) {
+                                                               int hq, int hkv, float* __restrict__ partial,
+                                                               const int32_t* __restrict__ pos_ids, int64_t max_len) {
   constexpr int V = Store<T>::kVec, LPR = kHeadDim / V, RPB = 256 / LPR;
   __shared__ float red[RPB][2][kHeadDim];
   const int lr = threadIdx.x % LPR, grp = threadIdx.x / LPR, nh = hq + hkv;
@@ -217,7 +231,7 @@ __global__ __launch_bounds__(256) void qknorm_rope_bwd_kernel(T* __restrict__ dq
     T* dptr = dqkv + t * d_stride + (int64_t)hd * kHeadDim + lr * V;
     Store<T>::ldv(dptr, g);
     Store<T>::ldv(qkv + t * in_stride + (int64_t)hd * kHeadDim + lr * V, x);
-    const float* csr = cs + (t % seq_len) * 128;
+    const float* csr = rope_row(cs, t, seq_len, pos_ids, max_len);
     load_f32<V>(csr + col, c);
     load_f32<V>(csr + 64 + col, sn);
     const float rs = rstd[live ? item : 0];
@@ -328,6 +342,7 @@ static int rope_check(const char* who, const void* qkv, int64_t stride, const vo
   GMLM_REQUIRE(dtype == GMLM_F32 || dtype == GMLM_BF16, "%s: unsupported dtype", who);
   GMLM_REQUIRE(d == 128, "%s: head dim %ld not supported (this entry point takes 128)", who, (long)d);
   GMLM_REQUIRE(tokens >= 0 && hq > 0 && hkv > 0 && hq + hkv < 4096, "%s: bad sizes", who);
+  GMLM_REQUIRE(max_len > 0, "%s: empty cos / sin table", who);
   GMLM_REQUIRE(seq_len > 0 && seq_len <= max_len, "%s: sequence length %ld exceeds the %ld rows of the cos / sin table", who,
                (long)seq_len, (long)max_len);
   const int v = dtype == GMLM_F32 ? 4 : 8;
@@ -391,11 +406,11 @@ extern "C" int gmlm_add_rmsnorm_bwd(const void* dy, const void* dres, const void
   return col_reduce<1>(rows, f, RmsDwFn<float>{(const float*)dy, (const float*)s, rstd, f}, dw, workspace, workspace_bytes, st);
 }
 
-extern "C" int gmlm_qknorm_rope_fwd(const void* qkv, int64_t qkv_stride, const float* q_weight, const float* k_weight,
-                                    const float* cos_sin, int64_t max_len, int64_t tokens, int64_t seq_len, int64_t hq,
-                                    int64_t hkv, int64_t d, float eps, void* out, int64_t out_stride, float* rstd, int dtype,
-                                    gmlm_stream_t stream) {
-  static const char* who = "qknorm_rope_fwd";
+// pos_ids NULL: position = row % seq_len; else position = pos_ids[row] (seq_len unused)
+static int rope_fwd(const char* who, const void* qkv, int64_t qkv_stride, const float* q_weight, const float* k_weight,
+                    const float* cos_sin, int64_t max_len, int64_t tokens, int64_t seq_len, const int32_t* pos_ids, int64_t hq,
+                    int64_t hkv, int64_t d, float eps, void* out, int64_t out_stride, float* rstd, int dtype,
+                    gmlm_stream_t stream) {
   int rc = rope_check(who, qkv, qkv_stride, out, out_stride, (hq + hkv) * 128, q_weight, k_weight, cos_sin, tokens, seq_len, max_len,
                       hq, hkv, d, dtype);
   if (rc != GMLM_OK) return rc;
@@ -405,23 +420,40 @@ extern "C" int gmlm_qknorm_rope_fwd(const void* qkv, int64_t qkv_stride, const f
   const int64_t items = tokens * (hq + hkv);
   if (dtype == GMLM_BF16)
     qknorm_rope_fwd_kernel<bf16_t><<<(unsigned)cdiv(items * 16, 256), 256, 0, st>>>((const bf16_t*)qkv, qkv_stride, q_weight, k_weight,
-        cos_sin, tokens, seq_len, (int)hq, (int)hkv, eps, (bf16_t*)out, out_stride, rstd);
+        cos_sin, tokens, seq_len, (int)hq, (int)hkv, eps, (bf16_t*)out, out_stride, rstd, pos_ids, max_len);
   else
     qknorm_rope_fwd_kernel<float><<<(unsigned)cdiv(items * 32, 256), 256, 0, st>>>((const float*)qkv, qkv_stride, q_weight, k_weight,
-        cos_sin, tokens, seq_len, (int)hq, (int)hkv, eps, (float*)out, out_stride, rstd);
+        cos_sin, tokens, seq_len, (int)hq, (int)hkv, eps, (float*)out, out_stride, rstd, pos_ids, max_len);
   GMLM_LAUNCH_CHECK();
   return GMLM_OK;
+}
+
+extern "C" int gmlm_qknorm_rope_fwd(const void* qkv, int64_t qkv_stride, const float* q_weight, const float* k_weight,
+                                    const float* cos_sin, int64_t max_len, int64_t tokens, int64_t seq_len, int64_t hq,
+                                    int64_t hkv, int64_t d, float eps, void* out, int64_t out_stride, float* rstd, int dtype,
+                                    gmlm_stream_t stream) {
+  return rope_fwd("qknorm_rope_fwd", qkv, qkv_stride, q_weight, k_weight, cos_sin, max_len, tokens, seq_len, nullptr, hq, hkv, d, eps,
+                  out, out_stride, rstd, dtype, stream);
+}
+
+extern "C" int gmlm_qknorm_rope_pos_fwd(const void* qkv, int64_t qkv_stride, const float* q_weight, const float* k_weight,
+                                        const float* cos_sin, int64_t max_len, int64_t tokens, const int32_t* pos_ids, int64_t hq,
+                                        int64_t hkv, int64_t d, float eps, void* out, int64_t out_stride, float* rstd, int dtype,
+                                        gmlm_stream_t stream) {
+  static const char* who = "qknorm_rope_pos_fwd";
+  GMLM_REQUIRE(pos_ids, "%s: null pos_ids", who);
+  return rope_fwd(who, qkv, qkv_stride, q_weight, k_weight, cos_sin, max_len, tokens, 1, pos_ids, hq, hkv, d, eps, out, out_stride,
+                  rstd, dtype, stream);
 }
 
 extern "C" size_t gmlm_qknorm_rope_bwd_workspace_bytes(int64_t tokens, int64_t hq, int64_t hkv, int dtype) {
   return (size_t)rope_bwd_blocks(tokens * (hq + hkv), dtype) * 256 * sizeof(float);
 }
 
-extern "C" int gmlm_qknorm_rope_bwd(void* dqkv, int64_t dqkv_stride, const void* qkv, int64_t qkv_stride, const float* q_weight,
-                                    const float* k_weight, const float* cos_sin, int64_t max_len, const float* rstd,
-                                    int64_t tokens, int64_t seq_len, int64_t hq, int64_t hkv, int64_t d, float* dq_weight,
-                                    float* dk_weight, int dtype, void* workspace, size_t workspace_bytes, gmlm_stream_t stream) {
-  static const char* who = "qknorm_rope_bwd";
+static int rope_bwd(const char* who, void* dqkv, int64_t dqkv_stride, const void* qkv, int64_t qkv_stride, const float* q_weight,
+                    const float* k_weight, const float* cos_sin, int64_t max_len, const float* rstd, int64_t tokens,
+                    int64_t seq_len, const int32_t* pos_ids, int64_t hq, int64_t hkv, int64_t d, float* dq_weight,
+                    float* dk_weight, int dtype, void* workspace, size_t workspace_bytes, gmlm_stream_t stream) {
   int rc = rope_check(who, qkv, qkv_stride, dqkv, dqkv_stride, (hq + hkv) * 128, q_weight, k_weight, cos_sin, tokens, seq_len,
                       max_len, hq, hkv, d, dtype);
   if (rc != GMLM_OK) return rc;
@@ -440,14 +472,33 @@ extern "C" int gmlm_qknorm_rope_bwd(void* dqkv, int64_t dqkv_stride, const void*
   float* partial = static_cast<float*>(workspace);
   if (dtype == GMLM_BF16)
     qknorm_rope_bwd_kernel<bf16_t><<<nb, 256, 0, st>>>((bf16_t*)dqkv, dqkv_stride, (const bf16_t*)qkv, qkv_stride, q_weight, k_weight,
-        cos_sin, rstd, tokens, seq_len, (int)hq, (int)hkv, partial);
+        cos_sin, rstd, tokens, seq_len, (int)hq, (int)hkv, partial, pos_ids, max_len);
   else
     qknorm_rope_bwd_kernel<float><<<nb, 256, 0, st>>>((float*)dqkv, dqkv_stride, (const float*)qkv, qkv_stride, q_weight, k_weight,
-        cos_sin, rstd, tokens, seq_len, (int)hq, (int)hkv, partial);
+        cos_sin, rstd, tokens, seq_len, (int)hq, (int)hkv, partial, pos_ids, max_len);
   GMLM_LAUNCH_CHECK();
   rows_sum_kernel<<<8, 256, 0, st>>>(partial, nb, 256, dq_weight);
   GMLM_LAUNCH_CHECK();
   return GMLM_OK;
+}
+
+extern "C" int gmlm_qknorm_rope_bwd(void* dqkv, int64_t dqkv_stride, const void* qkv, int64_t qkv_stride, const float* q_weight,
+                                    const float* k_weight, const float* cos_sin, int64_t max_len, const float* rstd,
+                                    int64_t tokens, int64_t seq_len, int64_t hq, int64_t hkv, int64_t d, float* dq_weight,
+                                    float* dk_weight, int dtype, void* workspace, size_t workspace_bytes, gmlm_stream_t stream) {
+  return rope_bwd("qknorm_rope_bwd", dqkv, dqkv_stride, qkv, qkv_stride, q_weight, k_weight, cos_sin, max_len, rstd, tokens, seq_len,
+                  nullptr, hq, hkv, d, dq_weight, dk_weight, dtype, workspace, workspace_bytes, stream);
+}
+
+extern "C" int gmlm_qknorm_rope_pos_bwd(void* dqkv, int64_t dqkv_stride, const void* qkv, int64_t qkv_stride,
+                                        const float* q_weight, const float* k_weight, const float* cos_sin, int64_t max_len,
+                                        const float* rstd, int64_t tokens, const int32_t* pos_ids, int64_t hq, int64_t hkv,
+                                        int64_t d, float* dq_weight, float* dk_weight, int dtype, void* workspace,
+                                        size_t workspace_bytes, gmlm_stream_t stream) {
+  static const char* who = "qknorm_rope_pos_bwd";
+  GMLM_REQUIRE(pos_ids, "%s: null pos_ids", who);
+  return rope_bwd(who, dqkv, dqkv_stride, qkv, qkv_stride, q_weight, k_weight, cos_sin, max_len, rstd, tokens, 1, pos_ids, hq, hkv, d,
+                  dq_weight, dk_weight, dtype, workspace, workspace_bytes, stream);
 }
 
 static int swiglu_check(const char* who, int64_t rows, int64_t inter, int dtype) {

@@ -180,11 +180,16 @@ class GraphTextLM(nn.Module):
         return qwen3 if self._plm_kind == "qwen3" else bert
 
     def _packed_head_dim(self) -> int:
-        """Head dim of the text encoder if it has a packed (varlen) pass and the short-sequence / whole-step forms built on it,
-        else 0: BERT geometry only.  A Qwen3 encoder runs the padded pass whatever its hidden_size // heads is (64 for
-        Qwen3-0.6B, whose head dim is 128)."""
+        """Head dim of the text encoder if it has the forms built on the BERT packed pass (short-sequence groups, bucketed
+        layout, hipGraph capture of the encoder), else 0: BERT geometry only.  A Qwen3 encoder has none of them whatever its
+        hidden_size // heads is (64 for Qwen3-0.6B, whose head dim is 128); its plain packed pass is ``_has_packed_pass``."""
         cfg = self.plm_encoder.config
         return cfg.hidden_size // cfg.num_attention_heads if self._enc is bert else 0
+
+    def _has_packed_pass(self) -> bool:
+        """The encoder can run all active nodes as one variable-length packed batch: BERT geometry at head dim 64 / 96
+        (``bert.bert_encode_packed``) and Qwen3 (``qwen3.qwen3_encode_packed``, head dim 128)."""
+        return self._enc is qwen3 or self._packed_head_dim() in (64, 96)
 
     def graph(self, edge_index: torch.Tensor, num_nodes: int, edge_type=None) -> RelCSR:
         if self.dist is not None:
@@ -371,7 +376,8 @@ class GraphTextLM(nn.Module):
         tokens.check_ids(ecfg.vocab_size, ecfg.max_position_embeddings)      # one sync per token set, not per step
         grad = self.plm_encoder.training or self.training
         heads = self.plm_encoder.config.num_attention_heads
-        packed = self._packed_head_dim() in (64, 96) and self.plm_packed
+        packed = self._has_packed_pass() and self.plm_packed
+        static_ok = self._packed_head_dim() in (64, 96)                      # bucketed layout / recorded encoder: BERT geometry only
         plm_batch_size = max(1, min(int(plm_batch_size), 65535 // heads))   # attention grids index (sequence, head) in 16 bits
         with torch.set_grad_enabled(grad and torch.is_grad_enabled()):
             # cast / fuse once, share across micro-batches (forward() has done it ahead of the GNN launches)
@@ -379,7 +385,7 @@ class GraphTextLM(nn.Module):
             g = self._graphed if (grad and torch.is_grad_enabled() and self.training and self.dist is None) else None
             if g is not None and not g.encoder_enabled:
                 g = None
-            if packed and a <= plm_batch_size and (self.plm_bucketed or g is not None):
+            if packed and static_ok and a <= plm_batch_size and (self.plm_bucketed or g is not None):
                 # ONE micro-batch padded to bucket sizes: static shapes, replayable (graphs.py); the same function runs eagerly
                 key, args, short = self._bucket_tables(tokens, seen, cd)
                 if g is not None:
@@ -424,6 +430,11 @@ class GraphTextLM(nn.Module):
                     # short sequences (the reference tokenises to <= 128 tokens, main.py:340): consecutive sequences are packed
                     # into attention work items of <= 128 rows (host arithmetic on the host copy of the lengths, ~0.2 ms per
                     # 1,000 sequences, once per batch: all layers, forward and backward, share it)
+                    if self._enc is qwen3:
+                        hs = qwen3.qwen3_encode_packed(self.plm_encoder, tok, pos, cu_all, lmax, cd, self.plm_encoder.training,
+                                                       self.plm_gradient_checkpointing, weights)
+                        plm_embeds = ops.MeanPoolScatter.apply(plm_embeds, hs, None, bi, cu, total)
+                        continue
                     groups = None
                     n_seq = bi.numel() + (1 if pad else 0)
                     if cd == torch.bfloat16 and self._packed_head_dim() == 64 and lmax <= 128 and n_seq * heads >= 512:

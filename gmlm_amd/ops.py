@@ -909,30 +909,51 @@ def _qkv_rows(qkv: torch.Tensor, width: int):
     return tokens, stride
 
 
-def _rope_fwd(qkv, qw, kw, cs, seq_len, hq, hkv, eps):
+def _rope_fwd(qkv, qw, kw, cs, seq_len, hq, hkv, eps, pos_ids=None):
+    """``pos_ids`` (int32 [tokens]) given: the position of row t is pos_ids[t] and ``seq_len`` is not used."""
     tokens, stride = _qkv_rows(qkv, (hq + 2 * hkv) * 128)
     qk = torch.empty(*qkv.shape[:-1], (hq + hkv) * 128, dtype=qkv.dtype, device=qkv.device)
     rstd = torch.empty(tokens, hq + hkv, dtype=torch.float32, device=qkv.device)
+    if pos_ids is not None:
+        check(lib().gmlm_qknorm_rope_pos_fwd(_ptr(qkv), stride, _ptr(qw), _ptr(kw), _ptr(cs), cs.shape[0], tokens, _ptr(pos_ids), hq,
+                                             hkv, 128, float(eps), _ptr(qk), (hq + hkv) * 128, _ptr(rstd), _dt(qkv), _stream()),
+              "gmlm_qknorm_rope_pos_fwd")
+        return qk, rstd
     check(lib().gmlm_qknorm_rope_fwd(_ptr(qkv), stride, _ptr(qw), _ptr(kw), _ptr(cs), cs.shape[0], tokens, seq_len, hq, hkv, 128,
                                      float(eps), _ptr(qk), (hq + hkv) * 128, _ptr(rstd), _dt(qkv), _stream()),
           "gmlm_qknorm_rope_fwd")
     return qk, rstd
 
 
-def _rope_bwd_(dqkv, qkv, qw, kw, cs, rstd, seq_len, hq, hkv):
+def _rope_bwd_(dqkv, qkv, qw, kw, cs, rstd, seq_len, hq, hkv, pos_ids=None):
     """In place on the Q | K columns of ``dqkv``; returns the fp32 [2, 128] weight gradients."""
     tokens, stride = _qkv_rows(qkv, (hq + 2 * hkv) * 128)
     _, dstride = _qkv_rows(dqkv, (hq + hkv) * 128)
     dwt = torch.empty(2, 128, dtype=torch.float32, device=qkv.device)
     ws = _ws(lib().gmlm_qknorm_rope_bwd_workspace_bytes(tokens, hq, hkv, _dt(qkv)), qkv.device)
+    if pos_ids is not None:
+        check(lib().gmlm_qknorm_rope_pos_bwd(_ptr(dqkv), dstride, _ptr(qkv), stride, _ptr(qw), _ptr(kw), _ptr(cs), cs.shape[0],
+                                             _ptr(rstd), tokens, _ptr(pos_ids), hq, hkv, 128, _ptr(dwt), _ptr(dwt[1]), _dt(qkv),
+                                             _ptr(ws), ws.numel(), _stream()), "gmlm_qknorm_rope_pos_bwd")
+        return dwt
     check(lib().gmlm_qknorm_rope_bwd(_ptr(dqkv), dstride, _ptr(qkv), stride, _ptr(qw), _ptr(kw), _ptr(cs), cs.shape[0], _ptr(rstd),
                                      tokens, seq_len, hq, hkv, 128, _ptr(dwt), _ptr(dwt[1]), _dt(qkv), _ptr(ws), ws.numel(),
                                      _stream()), "gmlm_qknorm_rope_bwd")
     return dwt
 
 
-def _rope_args(qkv, qw, kw, cs):
-    if qkv.dim() != 3:
+def _pos_arg(qkv, pos_ids):
+    """Positions of packed rows: int32 [tokens] on the rows' device."""
+    if qkv.dim() != 2:
+        raise ValueError("packed fused projection output must be [tokens, (hq + 2 hkv) * 128]")
+    if pos_ids.dim() != 1 or pos_ids.numel() != qkv.shape[0] or pos_ids.device != qkv.device or pos_ids.is_floating_point() \
+            or pos_ids.dtype == torch.bool:
+        raise ValueError("pos_ids must be an integer [tokens] tensor on the device of the rows")
+    return pos_ids.to(torch.int32).contiguous()
+
+
+def _rope_args(qkv, qw, kw, cs, packed=False):
+    if not packed and qkv.dim() != 3:
         raise ValueError("fused projection output must be [b, l, (hq + 2 hkv) * 128]")
     if cs.dtype != torch.float32 or cs.dim() != 3 or tuple(cs.shape[1:]) != (2, 64) or not cs.is_contiguous():
         raise ValueError("cos / sin table must be a contiguous fp32 [max_len, 2, 64] tensor")
@@ -940,32 +961,34 @@ def _rope_args(qkv, qw, kw, cs):
 
 
 class QKNormRope(torch.autograd.Function):
-    """Rotated, head-normalised [q | k] of a fused [b, l, (hq + 2 hkv) * 128] projection output (positions 0..l-1)."""
+    """Rotated, head-normalised [q | k] of a fused [b, l, (hq + 2 hkv) * 128] projection output (positions 0..l-1), or, with
+    ``pos_ids`` (integer [tokens]), of packed [tokens, (hq + 2 hkv) * 128] rows at the positions given."""
 
     @staticmethod
-    def forward(ctx, qkv, qw, kw, cs, hq, hkv, eps):
+    def forward(ctx, qkv, qw, kw, cs, hq, hkv, eps, pos_ids=None):
         _cuda(qkv)
-        qwf, kwf = _rope_args(qkv, qw, kw, cs)
-        qk, rstd = _rope_fwd(qkv, qwf, kwf, cs, qkv.shape[1], hq, hkv, eps)
-        ctx.save_for_backward(qkv, qwf, kwf, cs, rstd)
+        qwf, kwf = _rope_args(qkv, qw, kw, cs, pos_ids is not None)
+        pos = None if pos_ids is None else _pos_arg(qkv, pos_ids)
+        qk, rstd = _rope_fwd(qkv, qwf, kwf, cs, qkv.shape[-2], hq, hkv, eps, pos)
+        ctx.save_for_backward(qkv, qwf, kwf, cs, rstd, pos)
         ctx.cfg = (hq, hkv)
         return qk
 
     @staticmethod
     def backward(ctx, g):
-        qkv, qwf, kwf, cs, rstd = ctx.saved_tensors
+        qkv, qwf, kwf, cs, rstd, pos = ctx.saved_tensors
         hq, hkv = ctx.cfg
         n = (hq + hkv) * 128
         dqkv = torch.zeros(*qkv.shape[:-1], (hq + 2 * hkv) * 128, dtype=qkv.dtype, device=qkv.device)   # V columns: no gradient from here
         dqkv[..., :n].copy_(g)
-        dwt = _rope_bwd_(dqkv, qkv, qwf, kwf, cs, rstd, qkv.shape[1], hq, hkv)
+        dwt = _rope_bwd_(dqkv, qkv, qwf, kwf, cs, rstd, qkv.shape[-2], hq, hkv, pos)
         if dqkv.shape[-1] != qkv.shape[-1]:
             dqkv = torch.nn.functional.pad(dqkv, (0, qkv.shape[-1] - dqkv.shape[-1]))
-        return dqkv, dwt[0], dwt[1], None, None, None, None
+        return dqkv, dwt[0], dwt[1], None, None, None, None, None
 
 
-def qknorm_rope(qkv, q_weight, k_weight, cos_sin, hq, hkv, eps=1e-6):
-    return QKNormRope.apply(qkv, q_weight, k_weight, cos_sin, hq, hkv, eps)
+def qknorm_rope(qkv, q_weight, k_weight, cos_sin, hq, hkv, eps=1e-6, pos_ids=None):
+    return QKNormRope.apply(qkv, q_weight, k_weight, cos_sin, hq, hkv, eps, pos_ids)
 
 
 def _causal_fwd(q, k, v, kv_len, hq, hkv, scale, want_lo):
@@ -1056,6 +1079,117 @@ class RopeCausalAttention(torch.autograd.Function):
 
 def rope_causal_attention(qkv, q_weight, k_weight, cos_sin, kv_len, hq, hkv, scale, eps=1e-6):
     return RopeCausalAttention.apply(qkv, q_weight, k_weight, cos_sin, kv_len, hq, hkv, scale, eps)
+
+
+def _varlen_args(rows, cu_seqlens, max_len):
+    """cu_seqlens int32 [S + 1] on the rows' device; -> (S, max_len)."""
+    if cu_seqlens is None or cu_seqlens.dtype != torch.int32 or cu_seqlens.dim() != 1 or cu_seqlens.numel() < 1 \
+            or not cu_seqlens.is_contiguous() or cu_seqlens.device != rows.device:
+        raise ValueError("cu_seqlens must be a contiguous int32 [sequences + 1] tensor on the device of the rows")
+    if int(max_len) <= 0:
+        raise ValueError(f"max_len must be positive, got {max_len}")
+    return cu_seqlens.numel() - 1, int(max_len)
+
+
+def _packed_stride(t: torch.Tensor, h: int):
+    if t.dim() != 2 or t.stride(-1) != 1 or t.shape[-1] != h * 128:
+        raise ValueError("packed attention operands must be [tokens, heads * 128] with a contiguous last dim")
+    return t.stride(0)
+
+
+def _causal_varlen_fwd(q, k, v, cu, s, max_len, hq, hkv, scale, want_lo):
+    t = q.shape[0]
+    qs, ks, vs = _packed_stride(q, hq), _packed_stride(k, hkv), _packed_stride(v, hkv)
+    if k.shape[0] != t or v.shape[0] != t:
+        raise ValueError("packed q, k and v must have the same number of rows")
+    out = torch.empty(t, hq * 128, dtype=q.dtype, device=q.device)
+    lse = torch.empty(hq, t, dtype=torch.float32, device=q.device)
+    out_lo = torch.empty_like(out) if want_lo else None
+    with _span("attn_causal_varlen_fwd_d128", flops=2.0 * s * hq * max_len * max_len * 128):
+        check(lib().gmlm_attention_causal_d128_varlen_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(cu), s, max_len, t, hq, hkv, 128, qs, ks, vs,
+                                                          float(scale), 0.0, _ptr(out), _ptr(out_lo), _ptr(lse), _dt(q), _stream()),
+              "gmlm_attention_causal_d128_varlen_fwd")
+    return out, out_lo, lse
+
+
+def _causal_varlen_bwd(q, k, v, out, out_lo, gout, lse, cu, s, max_len, hq, hkv, scale, dq, dk, dv):
+    t = q.shape[0]
+    gout = gout.contiguous().to(q.dtype)
+    ws = _ws(lib().gmlm_attention_causal_d128_varlen_workspace_bytes(t, hq), q.device)
+    with _span("attn_causal_varlen_bwd_d128", flops=5.0 * s * hq * max_len * max_len * 128):
+        check(lib().gmlm_attention_causal_d128_varlen_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(out_lo), _ptr(gout), _ptr(lse),
+                                                          _ptr(cu), s, max_len, t, hq, hkv, 128, q.stride(0), k.stride(0),
+                                                          v.stride(0), float(scale), 0.0, _ptr(dq), _ptr(dk), _ptr(dv),
+                                                          dq.stride(0), dk.stride(0), dv.stride(0), _dt(q), _ptr(ws), ws.numel(),
+                                                          _stream()), "gmlm_attention_causal_d128_varlen_bwd")
+
+
+class CausalAttentionVarlen(torch.autograd.Function):
+    """``CausalAttention`` on a packed batch: q [T, hq*128], k / v [T, hkv*128] (strided slices of a fused buffer are fine),
+    sequence i = rows [cu_seqlens[i], cu_seqlens[i+1]) (int32 [S + 1]; a sequence may be empty, none is longer than
+    ``max_len``), query i of a sequence sees its keys 0..i.  The sequences cover all T rows: a row that belongs to none is
+    neither read nor written, so its output and gradient rows would be uninitialised.  The three gradients are views of ONE fused [T, (hq + 2 hkv) * 128] buffer."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, cu_seqlens, max_len, hq, hkv, scale):
+        _cuda(q, k, v)
+        s, max_len = _varlen_args(q, cu_seqlens, max_len)
+        want_lo = q.dtype == torch.bfloat16 and any(t.requires_grad for t in (q, k, v))
+        out, out_lo, lse = _causal_varlen_fwd(q, k, v, cu_seqlens, s, max_len, hq, hkv, scale, want_lo)
+        ctx.save_for_backward(q, k, v, out, lse, cu_seqlens, out_lo)
+        ctx.cfg = (s, max_len, hq, hkv, float(scale))
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        q, k, v, out, lse, cu, out_lo = ctx.saved_tensors
+        s, max_len, hq, hkv, scale = ctx.cfg
+        nq, nk = hq * 128, hkv * 128
+        dqkv = torch.empty(q.shape[0], nq + 2 * nk, dtype=q.dtype, device=q.device)
+        dq, dk, dv = dqkv[:, :nq], dqkv[:, nq:nq + nk], dqkv[:, nq + nk:]
+        _causal_varlen_bwd(q, k, v, out, out_lo, gout, lse, cu, s, max_len, hq, hkv, scale, dq, dk, dv)
+        return dq, dk, dv, None, None, None, None, None
+
+
+def causal_attention_varlen(q, k, v, cu_seqlens, max_len, hq, hkv, scale):
+    return CausalAttentionVarlen.apply(q, k, v, cu_seqlens, max_len, hq, hkv, scale)
+
+
+class RopeCausalAttentionVarlen(torch.autograd.Function):
+    """``RopeCausalAttention`` on packed [T, (hq + 2 hkv) * 128] rows: head norm + RoPE at ``pos_ids`` (integer [T]) + causal GQA
+    attention per sequence of ``cu_seqlens`` in one autograd node.  V is read from the fused rows in place; the backward
+    writes dq | dk | dv into ONE fused buffer that the head-norm backward finishes in place."""
+
+    @staticmethod
+    def forward(ctx, qkv, qw, kw, cs, pos_ids, cu_seqlens, max_len, hq, hkv, scale, eps):
+        _cuda(qkv)
+        qwf, kwf = _rope_args(qkv, qw, kw, cs, True)
+        pos = _pos_arg(qkv, pos_ids)
+        if qkv.shape[-1] != (hq + 2 * hkv) * 128:
+            raise ValueError("fused projection output must be [tokens, (hq + 2 hkv) * 128]")
+        s, max_len = _varlen_args(qkv, cu_seqlens, max_len)
+        nq, nk = hq * 128, hkv * 128
+        qk, rstd = _rope_fwd(qkv, qwf, kwf, cs, 0, hq, hkv, eps, pos)
+        want_lo = qkv.dtype == torch.bfloat16 and (qkv.requires_grad or qw.requires_grad or kw.requires_grad)
+        out, out_lo, lse = _causal_varlen_fwd(qk[:, :nq], qk[:, nq:], qkv[:, nq + nk:], cu_seqlens, s, max_len, hq, hkv, scale, want_lo)
+        ctx.save_for_backward(qkv, qk, qwf, kwf, cs, rstd, out, lse, cu_seqlens, pos, out_lo)
+        ctx.cfg = (s, max_len, hq, hkv, float(scale))
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        qkv, qk, qwf, kwf, cs, rstd, out, lse, cu, pos, out_lo = ctx.saved_tensors
+        s, max_len, hq, hkv, scale = ctx.cfg
+        nq, nk = hq * 128, hkv * 128
+        dqkv = torch.empty_like(qkv, memory_format=torch.contiguous_format)
+        _causal_varlen_bwd(qk[:, :nq], qk[:, nq:], qkv[:, nq + nk:], out, out_lo, gout, lse, cu, s, max_len, hq, hkv, scale,
+                           dqkv[:, :nq], dqkv[:, nq:nq + nk], dqkv[:, nq + nk:])
+        dwt = _rope_bwd_(dqkv, qkv, qwf, kwf, cs, rstd, 0, hq, hkv, pos)
+        return dqkv, dwt[0], dwt[1], None, None, None, None, None, None, None, None
+
+
+def rope_causal_attention_varlen(qkv, q_weight, k_weight, cos_sin, pos_ids, cu_seqlens, max_len, hq, hkv, scale, eps=1e-6):
+    return RopeCausalAttentionVarlen.apply(qkv, q_weight, k_weight, cos_sin, pos_ids, cu_seqlens, max_len, hq, hkv, scale, eps)
 
 
 class SwiGLU(torch.autograd.Function):

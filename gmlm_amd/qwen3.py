@@ -7,8 +7,9 @@ while keeping the HF module as the *parameter container*: state-dict keys stay `
 Per layer:  add + RMSNorm (one kernel, also yields the residual stream) -> fused Q|K|V GEMM (hipBLASLt)
             -> per-head RMSNorm of Q / K + rotary embedding -> causal attention, grouped KV heads (MFMA, per-sequence length)
             -> O GEMM -> add + RMSNorm -> fused gate|up GEMM -> SwiGLU -> down GEMM.
-Padded layout only ([B, L, .] with ``lens``); there is no packed / varlen, hipGraph, bucketed or ring form of this encoder
-(DESIGN.md section 4 "Qwen3 encoder").
+Two layouts: padded ([B, L, .] with ``lens``, ``qwen3_encode``) and packed / varlen ([T, .] rows of the sequences back to back
+with ``cu_seqlens`` and per-row positions, ``qwen3_encode_packed``: no padded token is computed).  There is no hipGraph,
+bucketed, short-sequence or ring form of this encoder (DESIGN.md section 4 "Qwen3 encoder").
 """
 from __future__ import annotations
 
@@ -152,12 +153,15 @@ def prepare_weights(plm, cd):
     return out
 
 
-def _layer(lw, stream, branch, lens, cs, hq, hkv, scale, eps):
+def _layer(lw, stream, branch, lens, cs, hq, hkv, scale, eps, packed=None):
     """(residual stream, last branch output) of the previous layer -> the same pair after this layer; the add that joins them
-    is fused into the next RMSNorm."""
+    is fused into the next RMSNorm.  ``packed`` = (pos_ids, cu_seqlens, max_len): the rows are [T, .] packed sequences."""
     s1, y1 = ops.add_rmsnorm(stream, branch, lw.ln1, eps)
     qkv = _mm(y1, lw.wqkv, None, lw.m_qkv)
-    ctx = ops.rope_causal_attention(qkv, lw.qn, lw.kn, cs, lens, hq, hkv, scale, eps)
+    if packed is not None:
+        ctx = ops.rope_causal_attention_varlen(qkv, lw.qn, lw.kn, cs, *packed, hq, hkv, scale, eps)
+    else:
+        ctx = ops.rope_causal_attention(qkv, lw.qn, lw.kn, cs, lens, hq, hkv, scale, eps)
     s2, y2 = ops.add_rmsnorm(s1, _mm(ctx, lw.wo, None, lw.m_wo), lw.ln2, eps)
     m = ops.swiglu(_mm(y2, lw.wgu, None, lw.m_gu))
     return s2, _mm(m, lw.wdown, None, lw.m_down)
@@ -185,4 +189,33 @@ def qwen3_encode(plm, input_ids: torch.Tensor, lens: torch.Tensor, cd: torch.dty
             stream, branch = checkpoint(_layer, lw, stream, branch, lens, cs, hq, hkv, scale, eps, use_reentrant=False)
         else:
             stream, branch = _layer(lw, stream, branch, lens, cs, hq, hkv, scale, eps)
+    return ops.add_rmsnorm(stream, branch, plm.norm.weight, eps)[1]
+
+
+def qwen3_encode_packed(plm, tok: torch.Tensor, pos: torch.Tensor, cu_seqlens: torch.Tensor, max_len: int, cd: torch.dtype,
+                        training: bool = False, gradient_checkpointing: bool = False, weights=None) -> torch.Tensor:
+    """Packed (varlen) pass: tok / pos int [T] (token id and position of every row, the sequences back to back), cu_seqlens
+    int32 [S + 1] (sequence i = rows [cu[i], cu[i+1]), covering all T rows), max_len >= the longest sequence -> [T, P] in ``cd``.
+
+    The same layer chain as ``qwen3_encode`` on [T, .] rows: the norms, SwiGLU and the GEMMs are row-wise, the rotary
+    embedding reads its table row by ``pos`` and the attention resolves its rows through ``cu_seqlens``."""
+    cfg = plm.config
+    max_len = int(max_len)
+    if max_len > cfg.max_position_embeddings:
+        raise ValueError(f"sequence length {max_len} exceeds max_position_embeddings {cfg.max_position_embeddings}")
+    if tok.dim() != 1 or pos.shape != tok.shape:
+        raise ValueError("packed token ids and positions must be [T] tensors of one size")
+    hq, hkv = cfg.num_attention_heads, cfg.num_key_value_heads
+    eps, scale = cfg.rms_norm_eps, head_dim(cfg) ** -0.5
+    x = torch.nn.functional.embedding(tok.long(), plm.embed_tokens.weight).to(cd)   # bit-exact row gather
+    cs = rope_table(cfg, max_len, x.device)
+    packed = (pos.to(torch.int32), cu_seqlens, max_len)
+    if weights is None:
+        weights = prepare_weights(plm, cd)
+    stream, branch = x, None
+    for lw in weights:
+        if gradient_checkpointing and training and torch.is_grad_enabled():
+            stream, branch = checkpoint(_layer, lw, stream, branch, None, cs, hq, hkv, scale, eps, packed, use_reentrant=False)
+        else:
+            stream, branch = _layer(lw, stream, branch, None, cs, hq, hkv, scale, eps, packed)
     return ops.add_rmsnorm(stream, branch, plm.norm.weight, eps)[1]

@@ -352,6 +352,18 @@ int gmlm_qknorm_rope_bwd(void* dqkv, int64_t dqkv_stride, const void* qkv, int64
                          const float* k_weight, const float* cos_sin, int64_t max_len, const float* rstd, int64_t tokens,
                          int64_t seq_len, int64_t hq, int64_t hkv, int64_t d, float* dq_weight, float* dk_weight, int dtype,
                          void* workspace, size_t workspace_bytes, gmlm_stream_t stream);
+/* The same two operations for packed rows: token t sits at position pos_ids[t] (int32 [tokens], required) instead of
+ * t % seq_len; an index outside [0, max_len) is clamped into the table, never read past it.  Same kernels, same
+ * arithmetic: with pos_ids[t] = t % seq_len the results are bit for bit those of the entry points above.  The backward's
+ * workspace is gmlm_qknorm_rope_bwd_workspace_bytes(tokens, hq, hkv, dtype). */
+int gmlm_qknorm_rope_pos_fwd(const void* qkv, int64_t qkv_stride, const float* q_weight, const float* k_weight,
+                             const float* cos_sin, int64_t max_len, int64_t tokens, const int32_t* pos_ids, int64_t hq,
+                             int64_t hkv, int64_t d, float eps, void* out, int64_t out_stride, float* rstd, int dtype,
+                             gmlm_stream_t stream);
+int gmlm_qknorm_rope_pos_bwd(void* dqkv, int64_t dqkv_stride, const void* qkv, int64_t qkv_stride, const float* q_weight,
+                             const float* k_weight, const float* cos_sin, int64_t max_len, const float* rstd, int64_t tokens,
+                             const int32_t* pos_ids, int64_t hq, int64_t hkv, int64_t d, float* dq_weight, float* dk_weight,
+                             int dtype, void* workspace, size_t workspace_bytes, gmlm_stream_t stream);
 /* SwiGLU: gate_up [rows, 2 * inter] = [gate | up] -> y [rows, inter] = silu(gate) * up; the backward returns the fused
  * [rows, 2 * inter] gradient.  inter: a multiple of 8 (bf16) / 4 (fp32). */
 int gmlm_swiglu_fwd(const void* gate_up, int64_t rows, int64_t inter, void* y, int dtype, gmlm_stream_t stream);
@@ -379,6 +391,23 @@ int gmlm_attention_causal_d128_bwd(const void* q, const void* k, const void* v, 
                                    int64_t v_stride, float scale, float dropout_p, void* dq, void* dk, void* dv,
                                    int64_t dq_stride, int64_t dk_stride, int64_t dv_stride, int dtype, void* workspace,
                                    size_t workspace_bytes, gmlm_stream_t stream);
+/* The same attention on a packed (variable-length) batch: q / dq [total_rows, hq, 128], k / v / dk / dv [total_rows, hkv, 128]
+ * at their own row strides, out / out_lo / dout [total_rows, hq, 128] dense, lse / delta [hq, total_rows] fp32.  Sequence i
+ * owns rows [cu_seqlens[i], cu_seqlens[i + 1]) (int32 [num_seqs + 1], required, non-decreasing, last entry <= total_rows);
+ * its length is its row count (there is no kv_len), it may be 0, and none may exceed max_len (> 0), which only sizes the
+ * grid.  total_rows < 2^30.  Rows owned by no sequence are neither read nor written.  Same kernels, same summation order
+ * as the padded entry points.  Backward workspace: gmlm_attention_causal_d128_varlen_workspace_bytes(total_rows, hq). */
+int gmlm_attention_causal_d128_varlen_fwd(const void* q, const void* k, const void* v, const int32_t* cu_seqlens,
+                                          int64_t num_seqs, int64_t max_len, int64_t total_rows, int64_t hq, int64_t hkv,
+                                          int64_t d, int64_t q_stride, int64_t k_stride, int64_t v_stride, float scale,
+                                          float dropout_p, void* out, void* out_lo, float* lse, int dtype, gmlm_stream_t stream);
+size_t gmlm_attention_causal_d128_varlen_workspace_bytes(int64_t total_rows, int64_t hq);
+int gmlm_attention_causal_d128_varlen_bwd(const void* q, const void* k, const void* v, const void* out, const void* out_lo,
+                                          const void* dout, const float* lse, const int32_t* cu_seqlens, int64_t num_seqs,
+                                          int64_t max_len, int64_t total_rows, int64_t hq, int64_t hkv, int64_t d,
+                                          int64_t q_stride, int64_t k_stride, int64_t v_stride, float scale, float dropout_p,
+                                          void* dq, void* dk, void* dv, int64_t dq_stride, int64_t dk_stride, int64_t dv_stride,
+                                          int dtype, void* workspace, size_t workspace_bytes, gmlm_stream_t stream);
 
 #ifdef __cplusplus
 }

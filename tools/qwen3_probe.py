@@ -11,6 +11,13 @@ not a rocprofv3 trace.
 Writes one JSON file (``--out``) and prints it.  Needs a GPU: there is no CPU fallback.
 
     python tools/qwen3_probe.py --out profiles/qwen3_probe.json
+
+``--packed``: this project's two passes against each other instead of against HF, alternating in the same way: the padded
+pass (``qwen3_encode``, every micro-batch padded to its longest sequence) and the packed / varlen pass
+(``qwen3_encode_packed``, the same micro-batches as [T, .] rows with no padded token).  The result also says whether the
+packed pass reached the split-K weight-gradient kernel (``wgrad_bf16_kernel``, T >= 16,384 rows in one micro-batch).
+
+    python tools/qwen3_probe.py --packed --batch 1257 --out profiles/qwen3_packed_probe.json
 """
 import argparse
 import json
@@ -59,6 +66,29 @@ def step_ours(plm, data, weights_fn, encode):
         ((hs * m).sum(1).float() / lens[:, None].float()).sum().backward()
 
 
+def pack(data):
+    """The padded micro-batches as packed ones: (token ids [T], positions [T], cu_seqlens [S + 1], longest, sequence of row, lens)."""
+    out = []
+    for ids, am, lens in data:
+        keep = am.bool()
+        s, width = ids.shape
+        pos = torch.arange(width, device=ids.device).expand(s, width)[keep]
+        seq = torch.arange(s, device=ids.device)[:, None].expand(s, width)[keep]
+        cu = torch.zeros(s + 1, dtype=torch.int32, device=ids.device)
+        cu[1:] = lens.cumsum(0)
+        out.append((ids[keep], pos, cu, width, seq, lens))
+    return out
+
+
+def step_packed(plm, data, weights_fn, encode):
+    plm.zero_grad(set_to_none=True)
+    weights = weights_fn(plm, torch.bfloat16)
+    for tok, pos, cu, width, seq, lens in data:
+        hs = encode(plm, tok, pos, cu, width, torch.bfloat16, True, False, weights)
+        pooled = torch.zeros(lens.numel(), hs.shape[1], dtype=hs.dtype, device=hs.device).index_add_(0, seq, hs)
+        (pooled.float() / lens[:, None].float()).sum().backward()
+
+
 def step_hf(plm, data):
     plm.zero_grad(set_to_none=True)
     for ids, am, lens in data:
@@ -105,6 +135,7 @@ def main():
     ap.add_argument("--max-len", type=int, default=128)
     ap.add_argument("--batch", type=int, default=128)
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--packed", action="store_true", help="padded pass against packed pass of this project (no HF run)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -115,6 +146,8 @@ def main():
     qwen3.check_supported(plm)
     data, tokens = batches(a.sequences, a.min_len, a.max_len, a.vocab, a.batch, dev)
     ours = lambda: step_ours(plm, data, qwen3.prepare_weights, qwen3.qwen3_encode)
+    if a.packed:
+        return packed_main(a, plm, data, tokens, ours)
     hf = lambda: step_hf(plm, data)
     # same weights, same batches: the two losses' gradients agree to bf16 accuracy (printed, not a test: tests/test_gpu_qwen3.py)
     ours()
@@ -137,11 +170,47 @@ def main():
                speedup_median=med(t_hf) / med(t_ours), grad_rel_diff_layer0_down_proj=agree,
                kernel_table_source="torch.profiler device events, one pass per path after the timed rounds",
                ours_kernels=kernel_table(ours), hf_kernels=kernel_table(hf))
+    emit(res, a.out)
+
+
+def packed_main(a, plm, data, tokens, padded):
+    from gmlm_amd import qwen3
+    pdata = pack(data)
+    packed = lambda: step_packed(plm, pdata, qwen3.prepare_weights, qwen3.qwen3_encode_packed)
+    padded()
+    g_pad = plm.layers[0].mlp.down_proj.weight.grad.double().clone()
+    packed()
+    g_pack = plm.layers[0].mlp.down_proj.weight.grad.double()
+    agree = float((g_pack - g_pad).norm() / g_pad.norm())
+    padded()                                                    # second warm-up round of each path
+    packed()
+    t_pad, t_pack = [], []
+    for _ in range(a.rounds):
+        t_pad.append(timed(padded))
+        t_pack.append(timed(packed))
+    med = lambda v: sorted(v)[len(v) // 2]
+    padded_tokens = int(sum(i.numel() for i, _, _ in data))
+    k_pad, k_pack = kernel_table(padded, top=10 ** 6), kernel_table(packed, top=10 ** 6)
+    wgrad = lambda tab: any("wgrad_bf16_kernel" in k["name"] for k in tab["kernels"])
+    res = dict(what="Qwen3-0.6B geometry text encoder, bf16 forward + backward, padded pass vs packed (varlen) pass of this project, alternating",
+               device=torch.cuda.get_device_name(0), layers=a.layers, sequences=a.sequences, tokens=tokens,
+               padded_tokens=padded_tokens, real_to_padded_rows=tokens / padded_tokens, micro_batch=a.batch,
+               micro_batches=len(data), largest_packed_micro_batch_rows=max(int(t[0].numel()) for t in pdata), rounds=a.rounds,
+               padded_ms=t_pad, packed_ms=t_pack, padded_median_ms=med(t_pad), packed_median_ms=med(t_pack),
+               padded_range_ms=[min(t_pad), max(t_pad)], packed_range_ms=[min(t_pack), max(t_pack)],
+               speedup_median=med(t_pad) / med(t_pack), grad_rel_diff_layer0_down_proj=agree,
+               native_splitk_wgrad_reached=dict(padded=wgrad(k_pad), packed=wgrad(k_pack)),
+               kernel_table_source="torch.profiler device events, one pass per path after the timed rounds",
+               padded_kernels=dict(k_pad, kernels=k_pad["kernels"][:14]), packed_kernels=dict(k_pack, kernels=k_pack["kernels"][:14]))
+    emit(res, a.out)
+
+
+def emit(res, out):
     text = json.dumps(res, indent=1)
     print(text)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
             f.write(text + "\n")
 
 
