@@ -22,6 +22,7 @@ inline ColReducePlan col_reduce_plan(int64_t n, int64_t f) {
   if (chunks > max_chunks) chunks = max_chunks;
   if (chunks < 1) chunks = 1;
   p.rows_per_chunk = cdiv(n, chunks);
+  if (p.rows_per_chunk < 1) p.rows_per_chunk = 1;   // n = 0: the workspace query of a call with no row must not divide by 0
   p.chunks = (int)cdiv(n, p.rows_per_chunk);
   if (p.chunks < 1) p.chunks = 1;
   return p;

@@ -336,23 +336,32 @@ static int64_t rope_bwd_blocks(int64_t items, int dtype) {
   return nb < 1 ? 1 : (nb > kRopeBwdMaxBlocks ? kRopeBwdMaxBlocks : nb);
 }
 
-static int rope_check(const char* who, const void* qkv, int64_t stride, const void* other, int64_t other_stride, int64_t min_other,
-                      const float* qw, const float* kw, const float* cs, int64_t tokens, int64_t seq_len, int64_t max_len,
-                      int64_t hq, int64_t hkv, int64_t d, int dtype) {
+// Sizes first, pointers second (rope_ptrs): a call with no token returns GMLM_OK in between, as the other row kernels do for
+// zero rows.  seq_len = 0 is the padded layout [b, 0]: it has no token, and only then is it accepted.
+static int rope_sizes(const char* who, int64_t stride, int64_t other_stride, int64_t min_other, int64_t tokens, int64_t seq_len,
+                      int64_t max_len, int64_t hq, int64_t hkv, int64_t d, int dtype) {
   GMLM_REQUIRE(dtype == GMLM_F32 || dtype == GMLM_BF16, "%s: unsupported dtype", who);
   GMLM_REQUIRE(d == 128, "%s: head dim %ld not supported (this entry point takes 128)", who, (long)d);
   GMLM_REQUIRE(tokens >= 0 && hq > 0 && hkv > 0 && hq + hkv < 4096, "%s: bad sizes", who);
   GMLM_REQUIRE(max_len > 0, "%s: empty cos / sin table", who);
-  GMLM_REQUIRE(seq_len > 0 && seq_len <= max_len, "%s: sequence length %ld exceeds the %ld rows of the cos / sin table", who,
+  GMLM_REQUIRE(seq_len >= 0 && seq_len <= max_len, "%s: sequence length %ld exceeds the %ld rows of the cos / sin table", who,
                (long)seq_len, (long)max_len);
+  GMLM_REQUIRE(seq_len > 0 || tokens == 0, "%s: %ld tokens in sequences of length 0", who, (long)tokens);
   const int v = dtype == GMLM_F32 ? 4 : 8;
-  GMLM_REQUIRE(qkv && other && aligned16(qkv) && aligned16(other), "%s: null or not 16-byte aligned pointer", who);
   GMLM_REQUIRE(stride >= (hq + 2 * hkv) * 128 && stride % v == 0, "%s: qkv row stride %ld must be >= %ld and a multiple of %d", who,
                (long)stride, (long)((hq + 2 * hkv) * 128), v);
   GMLM_REQUIRE(other_stride >= min_other && other_stride % v == 0, "%s: row stride %ld must be >= %ld and a multiple of %d", who,
                (long)other_stride, (long)min_other, v);
-  GMLM_REQUIRE(qw && kw && cs && aligned16(qw) && aligned16(kw) && aligned16(cs), "%s: null or misaligned weight / table", who);
   GMLM_REQUIRE(tokens * (hq + hkv) < ((int64_t)1 << 34), "%s: too many head rows", who);
+  return GMLM_OK;
+}
+
+static int rope_ptrs(const char* who, const void* qkv, const void* other, const float* qw, const float* kw, const float* cs,
+                     const float* rstd, bool by_pos, const int32_t* pos_ids) {
+  GMLM_REQUIRE(qkv && other && aligned16(qkv) && aligned16(other), "%s: null or not 16-byte aligned pointer", who);
+  GMLM_REQUIRE(qw && kw && cs && aligned16(qw) && aligned16(kw) && aligned16(cs), "%s: null or misaligned weight / table", who);
+  GMLM_REQUIRE(rstd, "%s: null rstd", who);
+  GMLM_REQUIRE(!by_pos || pos_ids, "%s: null pos_ids", who);
   return GMLM_OK;
 }
 
@@ -406,16 +415,15 @@ extern "C" int gmlm_add_rmsnorm_bwd(const void* dy, const void* dres, const void
   return col_reduce<1>(rows, f, RmsDwFn<float>{(const float*)dy, (const float*)s, rstd, f}, dw, workspace, workspace_bytes, st);
 }
 
-// pos_ids NULL: position = row % seq_len; else position = pos_ids[row] (seq_len unused)
+// by_pos: position = pos_ids[row] (seq_len unused, passed as 1); else pos_ids is NULL and position = row % seq_len
 static int rope_fwd(const char* who, const void* qkv, int64_t qkv_stride, const float* q_weight, const float* k_weight,
-                    const float* cos_sin, int64_t max_len, int64_t tokens, int64_t seq_len, const int32_t* pos_ids, int64_t hq,
-                    int64_t hkv, int64_t d, float eps, void* out, int64_t out_stride, float* rstd, int dtype,
+                    const float* cos_sin, int64_t max_len, int64_t tokens, int64_t seq_len, bool by_pos, const int32_t* pos_ids,
+                    int64_t hq, int64_t hkv, int64_t d, float eps, void* out, int64_t out_stride, float* rstd, int dtype,
                     gmlm_stream_t stream) {
-  int rc = rope_check(who, qkv, qkv_stride, out, out_stride, (hq + hkv) * 128, q_weight, k_weight, cos_sin, tokens, seq_len, max_len,
-                      hq, hkv, d, dtype);
+  int rc = rope_sizes(who, qkv_stride, out_stride, (hq + hkv) * 128, tokens, seq_len, max_len, hq, hkv, d, dtype);
   if (rc != GMLM_OK) return rc;
-  GMLM_REQUIRE(rstd, "%s: null rstd", who);
   if (tokens == 0) return GMLM_OK;
+  if ((rc = rope_ptrs(who, qkv, out, q_weight, k_weight, cos_sin, rstd, by_pos, pos_ids)) != GMLM_OK) return rc;
   hipStream_t st = as_stream(stream);
   const int64_t items = tokens * (hq + hkv);
   if (dtype == GMLM_BF16)
@@ -432,18 +440,16 @@ extern "C" int gmlm_qknorm_rope_fwd(const void* qkv, int64_t qkv_stride, const f
                                     const float* cos_sin, int64_t max_len, int64_t tokens, int64_t seq_len, int64_t hq,
                                     int64_t hkv, int64_t d, float eps, void* out, int64_t out_stride, float* rstd, int dtype,
                                     gmlm_stream_t stream) {
-  return rope_fwd("qknorm_rope_fwd", qkv, qkv_stride, q_weight, k_weight, cos_sin, max_len, tokens, seq_len, nullptr, hq, hkv, d, eps,
-                  out, out_stride, rstd, dtype, stream);
+  return rope_fwd("qknorm_rope_fwd", qkv, qkv_stride, q_weight, k_weight, cos_sin, max_len, tokens, seq_len, false, nullptr, hq, hkv, d,
+                  eps, out, out_stride, rstd, dtype, stream);
 }
 
 extern "C" int gmlm_qknorm_rope_pos_fwd(const void* qkv, int64_t qkv_stride, const float* q_weight, const float* k_weight,
                                         const float* cos_sin, int64_t max_len, int64_t tokens, const int32_t* pos_ids, int64_t hq,
                                         int64_t hkv, int64_t d, float eps, void* out, int64_t out_stride, float* rstd, int dtype,
                                         gmlm_stream_t stream) {
-  static const char* who = "qknorm_rope_pos_fwd";
-  GMLM_REQUIRE(pos_ids, "%s: null pos_ids", who);
-  return rope_fwd(who, qkv, qkv_stride, q_weight, k_weight, cos_sin, max_len, tokens, 1, pos_ids, hq, hkv, d, eps, out, out_stride,
-                  rstd, dtype, stream);
+  return rope_fwd("qknorm_rope_pos_fwd", qkv, qkv_stride, q_weight, k_weight, cos_sin, max_len, tokens, 1, true, pos_ids, hq, hkv, d, eps,
+                  out, out_stride, rstd, dtype, stream);
 }
 
 extern "C" size_t gmlm_qknorm_rope_bwd_workspace_bytes(int64_t tokens, int64_t hq, int64_t hkv, int dtype) {
@@ -452,21 +458,22 @@ extern "C" size_t gmlm_qknorm_rope_bwd_workspace_bytes(int64_t tokens, int64_t h
 
 static int rope_bwd(const char* who, void* dqkv, int64_t dqkv_stride, const void* qkv, int64_t qkv_stride, const float* q_weight,
                     const float* k_weight, const float* cos_sin, int64_t max_len, const float* rstd, int64_t tokens,
-                    int64_t seq_len, const int32_t* pos_ids, int64_t hq, int64_t hkv, int64_t d, float* dq_weight,
+                    int64_t seq_len, bool by_pos, const int32_t* pos_ids, int64_t hq, int64_t hkv, int64_t d, float* dq_weight,
                     float* dk_weight, int dtype, void* workspace, size_t workspace_bytes, gmlm_stream_t stream) {
-  int rc = rope_check(who, qkv, qkv_stride, dqkv, dqkv_stride, (hq + hkv) * 128, q_weight, k_weight, cos_sin, tokens, seq_len,
-                      max_len, hq, hkv, d, dtype);
+  int rc = rope_sizes(who, qkv_stride, dqkv_stride, (hq + hkv) * 128, tokens, seq_len, max_len, hq, hkv, d, dtype);
   if (rc != GMLM_OK) return rc;
-  GMLM_REQUIRE(rstd && dq_weight && dk_weight && dk_weight == dq_weight + 128, "%s: dq_weight | dk_weight are one fp32 [2, 128] buffer", who);
-  if (!workspace || workspace_bytes < gmlm_qknorm_rope_bwd_workspace_bytes(tokens, hq, hkv, dtype)) {
-    set_error("%s: workspace too small", who);
-    return GMLM_EWORKSPACE;
-  }
+  // the one output a call with no token still has: zero weight gradients
+  GMLM_REQUIRE(dq_weight && dk_weight && dk_weight == dq_weight + 128, "%s: dq_weight | dk_weight are one fp32 [2, 128] buffer", who);
   hipStream_t st = as_stream(stream);
   if (tokens == 0) {
     hipError_t e = zero_async(dq_weight, 256 * sizeof(float), st);
     if (e != hipSuccess) { set_error("%s: zero fill failed: %s", who, hipGetErrorString(e)); return GMLM_ELAUNCH; }
     return GMLM_OK;
+  }
+  if ((rc = rope_ptrs(who, qkv, dqkv, q_weight, k_weight, cos_sin, rstd, by_pos, pos_ids)) != GMLM_OK) return rc;
+  if (!workspace || workspace_bytes < gmlm_qknorm_rope_bwd_workspace_bytes(tokens, hq, hkv, dtype)) {
+    set_error("%s: workspace too small", who);
+    return GMLM_EWORKSPACE;
   }
   const int nb = (int)rope_bwd_blocks(tokens * (hq + hkv), dtype);
   float* partial = static_cast<float*>(workspace);
@@ -487,7 +494,7 @@ extern "C" int gmlm_qknorm_rope_bwd(void* dqkv, int64_t dqkv_stride, const void*
                                     int64_t tokens, int64_t seq_len, int64_t hq, int64_t hkv, int64_t d, float* dq_weight,
                                     float* dk_weight, int dtype, void* workspace, size_t workspace_bytes, gmlm_stream_t stream) {
   return rope_bwd("qknorm_rope_bwd", dqkv, dqkv_stride, qkv, qkv_stride, q_weight, k_weight, cos_sin, max_len, rstd, tokens, seq_len,
-                  nullptr, hq, hkv, d, dq_weight, dk_weight, dtype, workspace, workspace_bytes, stream);
+                  false, nullptr, hq, hkv, d, dq_weight, dk_weight, dtype, workspace, workspace_bytes, stream);
 }
 
 extern "C" int gmlm_qknorm_rope_pos_bwd(void* dqkv, int64_t dqkv_stride, const void* qkv, int64_t qkv_stride,
@@ -495,10 +502,8 @@ extern "C" int gmlm_qknorm_rope_pos_bwd(void* dqkv, int64_t dqkv_stride, const v
                                         const float* rstd, int64_t tokens, const int32_t* pos_ids, int64_t hq, int64_t hkv,
                                         int64_t d, float* dq_weight, float* dk_weight, int dtype, void* workspace,
                                         size_t workspace_bytes, gmlm_stream_t stream) {
-  static const char* who = "qknorm_rope_pos_bwd";
-  GMLM_REQUIRE(pos_ids, "%s: null pos_ids", who);
-  return rope_bwd(who, dqkv, dqkv_stride, qkv, qkv_stride, q_weight, k_weight, cos_sin, max_len, rstd, tokens, 1, pos_ids, hq, hkv, d,
-                  dq_weight, dk_weight, dtype, workspace, workspace_bytes, stream);
+  return rope_bwd("qknorm_rope_pos_bwd", dqkv, dqkv_stride, qkv, qkv_stride, q_weight, k_weight, cos_sin, max_len, rstd, tokens, 1, true,
+                  pos_ids, hq, hkv, d, dq_weight, dk_weight, dtype, workspace, workspace_bytes, stream);
 }
 
 static int swiglu_check(const char* who, int64_t rows, int64_t inter, int dtype) {

@@ -415,7 +415,7 @@ def _rows_view(t: torch.Tensor, h: int, d: int):
     """[b, l, h*d-wide slice] view -> (tensor, row stride in elements); last dim must be contiguous."""
     if t.stride(-1) != 1 or t.shape[-1] != h * d:
         raise ValueError("attention operands must be [b, l, h*d] with a contiguous last dim")
-    if t.stride(0) != t.shape[1] * t.stride(1) and t.shape[0] > 1:
+    if t.stride(0) != t.shape[1] * t.stride(1) and t.shape[0] > 1 and t.shape[1] > 0:
         raise ValueError("attention operands must have batch stride = l * row stride")
     return t.stride(1)
 
@@ -904,7 +904,7 @@ def _qkv_rows(qkv: torch.Tensor, width: int):
         raise ValueError(f"fused projection rows must be contiguous and at least {width} wide")
     tokens = qkv.numel() // qkv.shape[-1]
     stride = qkv.stride(-2)
-    if qkv.dim() == 3 and qkv.shape[0] > 1 and qkv.stride(0) != qkv.shape[1] * stride:
+    if qkv.dim() == 3 and qkv.shape[0] > 1 and tokens > 0 and qkv.stride(0) != qkv.shape[1] * stride:
         raise ValueError("fused projection rows must have batch stride = l * row stride")
     return tokens, stride
 

@@ -321,6 +321,11 @@ int gmlm_wgrad_bf16(const void* dy, int64_t ld_dy, const void* x, int64_t ld_x, 
 /* ---------------------------------------------------------------------------------------------
  * Row kernels of the pre-norm decoder-style text encoders (Qwen3 geometry).  bf16 or fp32 storage (`dtype`), fp32
  * arithmetic, one rounding on store; every pointer 16-byte aligned; sums over rows run in a fixed order (no atomics).
+ * Order of the checks, here and in the causal attention below: sizes, strides and dtype are validated first; then a call
+ * with nothing to do (rows = 0, tokens = 0, l = 0) returns GMLM_OK before any data pointer is required, so the NULL
+ * pointers of empty tensors are fine.  Such a call launches nothing, except that a backward with a weight gradient (dw,
+ * dq_weight | dk_weight: required even then) fills it with zeros.  gmlm_qknorm_rope_*: seq_len = 0 is accepted only with
+ * tokens = 0.
  * ------------------------------------------------------------------------------------------- */
 /* Residual add + RMSNorm over rows of width f (a multiple of 8 (bf16) / 4 (fp32), at most 4096):
  *   sum = a + b, stored to s in `dtype` (b and s are given together or both NULL: sum = a, nothing stored);
