@@ -83,6 +83,7 @@ SIGNATURES = {
     "gmlm_meanpool_scatter_fwd": (C.c_int, [_p, _p, _p, _i64, _i64, _i64, _p, _i32, _p, _p]),
     "gmlm_meanpool_scatter_bwd": (C.c_int, [_p, _p, _p, _i64, _i64, _i64, _p, _i32, _p, _p]),
     "gmlm_softmask_blend_fwd": (C.c_int, [_p, _p, _p, _f32, _i64, _i64, _p, _i64, _i32, _p]),
+    "gmlm_softmask_blend_bwd_workspace_bytes": (_sz, [_i64, _i64]),
     "gmlm_softmask_blend_bwd": (C.c_int, [_p, _i64, _p, _f32, _i64, _i64, _p, _p, _sz, _p]),
     "gmlm_bias_gelu_fwd": (C.c_int, [_p, _p, _i64, _i64, _f32, _u64, _p, _p, _i32, _p]),
     "gmlm_bias_gelu_bwd_workspace_bytes": (_sz, [_i64, _i64, _i32]),

@@ -105,12 +105,12 @@ extern "C" int gmlm_attention_fwd(const void* q, const void* k, const void* v, c
                                   int dtype, const int32_t* cu_seqlens, int64_t max_len, const int32_t* seq_groups, int64_t num_groups,
                                   gmlm_stream_t stream) {
   int rc = attn_check("attention_fwd", b, h, lq, lk, d, dtype);
+  if (rc != GMLM_OK) return rc;   // sizes and dtype first: their message must not be replaced by a later check's
   GMLM_REQUIRE(!seq_groups || (cu_seqlens && num_groups > 0 && num_groups <= b), "attention_fwd: seq_groups needs packed mode and 0 < num_groups <= b");
   GMLM_REQUIRE(!out_lo || (dtype == GMLM_BF16 && aligned16(out_lo)), "attention_fwd: out_lo is the bf16 residual of a bf16 output (16-byte aligned)");
   GMLM_REQUIRE(!cu_seqlens || (lq == lk && max_len > 0 && !kv_len), "attention_fwd: packed mode needs lq == lk = total rows, max_len > 0, kv_len NULL");
   GMLM_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "attention_fwd: dropout_p must be in [0,1)");
   GMLM_REQUIRE(scale > 0.f, "attention_fwd: scale must be positive");
-  if (rc != GMLM_OK) return rc;
   if (b == 0 || lq == 0) return GMLM_OK;
   if ((rc = attn_stride_check("attention_fwd", "q", q, q_stride, h * d, dtype)) != GMLM_OK) return rc;
   if (lk > 0) {
@@ -170,13 +170,14 @@ extern "C" int gmlm_attention_bwd(const void* q, const void* k, const void* v, c
                                   void* workspace, size_t workspace_bytes, float* dbias_partial, float* dbias,
                                   const void* out_lo, const int32_t* seq_groups, int64_t num_groups, gmlm_stream_t stream) {
   int rc = attn_check("attention_bwd", b, h, lq, lk, d, dtype);
+  if (rc != GMLM_OK) return rc;   // sizes and dtype first: their message must not be replaced by a later check's
   GMLM_REQUIRE(!seq_groups || (cu_seqlens && num_groups > 0 && num_groups <= b), "attention_bwd: seq_groups needs packed mode and 0 < num_groups <= b");
   GMLM_REQUIRE(!out_lo || (dtype == GMLM_BF16 && aligned16(out_lo)), "attention_bwd: out_lo is the bf16 residual of a bf16 output (16-byte aligned)");
   GMLM_REQUIRE((dbias_partial == nullptr) == (dbias == nullptr), "attention_bwd: dbias_partial and dbias come together");
   GMLM_REQUIRE(!cu_seqlens || (lq == lk && max_len > 0 && !kv_len), "attention_bwd: packed mode needs lq == lk = total rows, max_len > 0, kv_len NULL");
-  if (rc != GMLM_OK) return rc;
-  if (b == 0 || (lq == 0 && lk == 0)) return GMLM_OK;
   GMLM_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "attention_bwd: dropout_p must be in [0,1)");
+  GMLM_REQUIRE(scale > 0.f, "attention_bwd: scale must be positive");
+  if (b == 0 || (lq == 0 && lk == 0)) return GMLM_OK;
   GMLM_REQUIRE(lq > 0 && lk > 0, "attention_bwd: empty query or key set with a non-empty counterpart is not supported");
   if ((rc = attn_stride_check("attention_bwd", "q", q, q_stride, h * d, dtype)) != GMLM_OK) return rc;
   if ((rc = attn_stride_check("attention_bwd", "k", k, k_stride, h * d, dtype)) != GMLM_OK) return rc;
@@ -185,8 +186,8 @@ extern "C" int gmlm_attention_bwd(const void* q, const void* k, const void* v, c
   if ((rc = attn_stride_check("attention_bwd", "dk", dk, dk_stride, h * d, dtype)) != GMLM_OK) return rc;
   if ((rc = attn_stride_check("attention_bwd", "dv", dv, dv_stride, h * d, dtype)) != GMLM_OK) return rc;
   GMLM_REQUIRE(out && dout && lse && aligned16(out) && aligned16(dout), "attention_bwd: null or misaligned out/dout/lse");
-  GMLM_REQUIRE(workspace && workspace_bytes >= gmlm_attention_bwd_workspace_bytes(cu_seqlens ? 1 : b, h, lq, lk, d),
-               "attention_bwd: workspace too small");
+  GMLM_REQUIRE_WS(workspace && workspace_bytes >= gmlm_attention_bwd_workspace_bytes(cu_seqlens ? 1 : b, h, lq, lk, d),
+                  "attention_bwd: workspace too small");
   hipStream_t st = as_stream(stream);
   AttnParams p{};
   attn_fill(p, q, k, v, kv_len, b, h, lq, lk, q_stride, k_stride, v_stride, scale, dropout_p, seed, seed_dev);

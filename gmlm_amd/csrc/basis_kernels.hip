@@ -149,8 +149,8 @@ extern "C" int gmlm_basis_compose_bwd(const float* comp, const float* weight, co
   if (rc != GMLM_OK) return rc;
   GMLM_REQUIRE(comp && weight && dw && dweight && dcomp && aligned16(weight) && aligned16(dw) && aligned16(dweight),
                "basis_compose_bwd: null or misaligned pointer");
-  GMLM_REQUIRE(workspace && workspace_bytes >= gmlm_basis_compose_bwd_workspace_bytes(r_active, num_bases, cols),
-               "basis_compose_bwd: workspace too small");
+  GMLM_REQUIRE_WS(workspace && workspace_bytes >= gmlm_basis_compose_bwd_workspace_bytes(r_active, num_bases, cols),
+                  "basis_compose_bwd: workspace too small");
   const int blocks = basis_blocks(cols);
   float* partial = static_cast<float*>(workspace);
   hipStream_t st = as_stream(stream);

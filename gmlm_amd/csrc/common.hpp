@@ -25,6 +25,15 @@ void set_error(const char* fmt, ...);
     }                                      \
   } while (0)
 
+// a missing or short workspace has its own code (gmlm_hip.h: GMLM_EWORKSPACE), in every entry point that takes one
+#define GMLM_REQUIRE_WS(cond, ...)         \
+  do {                                     \
+    if (!(cond)) {                         \
+      ::gmlm::set_error(__VA_ARGS__);      \
+      return GMLM_EWORKSPACE;              \
+    }                                      \
+  } while (0)
+
 #define GMLM_HIP(expr)                                                                  \
   do {                                                                                  \
     hipError_t _e = (expr);                                                             \

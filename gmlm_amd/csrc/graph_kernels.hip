@@ -171,8 +171,8 @@ extern "C" int gmlm_edge_bucket(const int64_t* src, const int32_t* deg, int64_t 
 
 extern "C" int gmlm_relation_histogram(const int64_t* edge_type, int64_t e, int num_relations, int32_t* rel_count,
                                        gmlm_stream_t stream) {
-  GMLM_REQUIRE(num_relations > 0 && num_relations <= 64 && rel_count && (e == 0 || edge_type),
-               "relation_histogram: num_relations must be in [1, 64]");
+  GMLM_REQUIRE(num_relations > 0 && num_relations <= 64, "relation_histogram: num_relations must be in [1, 64]");
+  GMLM_REQUIRE(e >= 0 && rel_count && (e == 0 || edge_type), "relation_histogram: bad arguments");
   GMLM_HIP(zero_async(rel_count, sizeof(int32_t) * num_relations, as_stream(stream)));
   if (e == 0) return GMLM_OK;
   rel_hist_kernel<<<grid_cap(cdiv(e, 256), 1024), 256, 0, as_stream(stream)>>>(edge_type, e, num_relations, rel_count);
@@ -190,10 +190,10 @@ extern "C" int gmlm_segment_sort(const int64_t* node, const int64_t* rel, const 
                                  int64_t e, int64_t num_segments, int32_t* keys, int32_t* perm, int32_t* rowptr,
                                  int32_t* bad_flag, void* workspace, size_t workspace_bytes, gmlm_stream_t stream) {
   GMLM_REQUIRE(e >= 0 && num_segments >= 0 && r_active >= 1 && rowptr && bad_flag, "segment_sort: bad arguments");
-  GMLM_REQUIRE(e == 0 || (node && perm && workspace), "segment_sort: null pointer");
+  GMLM_REQUIRE(e == 0 || (node && perm), "segment_sort: null pointer");
   GMLM_REQUIRE(!rel || rel_remap, "segment_sort: rel given without rel_remap");
   GMLM_REQUIRE(num_segments < (1ll << 31) - 1 && e < (1ll << 31) - 1, "segment_sort: int32 index range exceeded");
-  GMLM_REQUIRE(workspace_bytes >= gmlm_segment_sort_workspace_bytes(e), "segment_sort: workspace too small");
+  GMLM_REQUIRE_WS((e == 0 || workspace) && workspace_bytes >= gmlm_segment_sort_workspace_bytes(e), "segment_sort: workspace too small");
   hipStream_t st = as_stream(stream);
   GMLM_HIP(zero_async(bad_flag, sizeof(int32_t), st));
   if (e == 0) {

@@ -471,6 +471,7 @@ extern "C" int gmlm_graphnorm_bwd_stats(const void* g, int dtype, const void* x,
                                         size_t workspace_bytes, gmlm_stream_t stream) {
   const SeedArg seed{seed_host, seed_dev};
   GMLM_REQUIRE(n >= 0 && f > 0 && gs, "graphnorm_bwd_stats: bad arguments");
+  GMLM_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "graphnorm_bwd_stats: dropout_p must be in [0,1)");
   GMLM_REQUIRE(dtype == GMLM_F32 || dtype == GMLM_BF16, "graphnorm_bwd_stats: unsupported dtype");
   GMLM_REQUIRE(n == 0 || (g && x && mean && rstd && weight && bias && mean_scale), "graphnorm_bwd_stats: null pointer");
   const uint32_t th = dropout_threshold(dropout_p);
@@ -488,6 +489,7 @@ extern "C" int gmlm_graphnorm_bwd_apply(const void* g, int dtype, const void* x,
                                         void* dx, float* dweight, float* dbias, float* dmean_scale, gmlm_stream_t stream) {
   const SeedArg seed{seed_host, seed_dev};
   GMLM_REQUIRE(n >= 0 && n_total >= n && n_total > 0 && f > 0 && gs, "graphnorm_bwd_apply: bad arguments");
+  GMLM_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "graphnorm_bwd_apply: dropout_p must be in [0,1)");
   GMLM_REQUIRE(dtype == GMLM_F32 || dtype == GMLM_BF16, "graphnorm_bwd_apply: unsupported dtype");
   GMLM_REQUIRE(mean && rstd && weight && bias && mean_scale && (n == 0 || (g && x && dx)), "graphnorm_bwd_apply: null pointer");
   const uint32_t th = dropout_threshold(dropout_p);
@@ -521,7 +523,8 @@ extern "C" int gmlm_bias_res_layernorm_fwd(const void* x, const float* bias, con
   if (rc != GMLM_OK) return rc;
   if (rows == 0) return GMLM_OK;
   GMLM_REQUIRE(x && gamma && beta && y, "bias_res_layernorm_fwd: null pointer");
-  GMLM_REQUIRE(aligned16(x) && aligned16(y) && (!residual || aligned16(residual)), "bias_res_layernorm_fwd: 16-byte alignment required");
+  GMLM_REQUIRE(aligned16(x) && aligned16(y) && aligned16(residual) && aligned16(bias) && aligned16(gamma) && aligned16(beta),
+               "bias_res_layernorm_fwd: 16-byte alignment required");
   const uint32_t th = dropout_threshold(dropout_p);
   const float ks = dropout_keep_scale(th);
   hipStream_t st = as_stream(stream);
@@ -558,7 +561,10 @@ extern "C" int gmlm_bias_res_layernorm_bwd(const void* dy, const void* x, const 
     return GMLM_OK;
   }
   GMLM_REQUIRE(dy && x && gamma && beta && mean && rstd && dx, "bias_res_layernorm_bwd: null pointer");
-  GMLM_REQUIRE(workspace && workspace_bytes >= gmlm_layernorm_bwd_workspace_bytes(rows, f), "bias_res_layernorm_bwd: workspace too small");
+  GMLM_REQUIRE(aligned16(dy) && aligned16(x) && aligned16(dx) && aligned16(residual) && aligned16(dresidual) && aligned16(bias) &&
+                   aligned16(gamma) && aligned16(beta),
+               "bias_res_layernorm_bwd: 16-byte alignment required");
+  GMLM_REQUIRE_WS(workspace && workspace_bytes >= gmlm_layernorm_bwd_workspace_bytes(rows, f), "bias_res_layernorm_bwd: workspace too small");
   const uint32_t th = dropout_threshold(dropout_p);
   const float ks = dropout_keep_scale(th);
   const int blocks = ln_bwd_blocks(rows);

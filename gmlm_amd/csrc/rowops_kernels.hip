@@ -224,6 +224,8 @@ extern "C" int gmlm_softmask_blend_fwd(const float* x, const uint8_t* mask, cons
   return GMLM_OK;
 }
 
+extern "C" size_t gmlm_softmask_blend_bwd_workspace_bytes(int64_t n, int64_t f) { return col_reduce_workspace_bytes(n, f, 1); }
+
 extern "C" int gmlm_softmask_blend_bwd(const float* dout, int64_t dout_stride, const uint8_t* mask, float beta, int64_t n,
                                        int64_t f, float* dtoken, void* workspace, size_t workspace_bytes,
                                        gmlm_stream_t stream) {
@@ -283,7 +285,7 @@ extern "C" int gmlm_bias_gelu_bwd(const void* dy, const void* x, const float* bi
   const BgGeom ge = bias_gelu_bwd_geom(rows, f / (dtype == GMLM_F32 ? 4 : 8));
   float* partial = nullptr;
   if (dbias) {
-    GMLM_REQUIRE(workspace && workspace_bytes >= gmlm_bias_gelu_bwd_workspace_bytes(rows, f, dtype), "bias_gelu_bwd: workspace too small");
+    GMLM_REQUIRE_WS(workspace && workspace_bytes >= gmlm_bias_gelu_bwd_workspace_bytes(rows, f, dtype), "bias_gelu_bwd: workspace too small");
     partial = static_cast<float*>(workspace);
   }
 #define BW(T, D) bias_gelu_bwd_kernel<T, D><<<ge.grid, ge.block, 0, st>>>((const T*)dy, (const T*)x, bias, rows, f, th, ks, seed, (T*)dx, partial)

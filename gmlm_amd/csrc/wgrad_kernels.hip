@@ -263,7 +263,7 @@ extern "C" size_t gmlm_wgrad_workspace_bytes(int64_t t, int64_t n, int64_t k, in
 extern "C" int gmlm_wgrad_bf16(const void* dy, int64_t ld_dy, const void* x, int64_t ld_x, int64_t t, int64_t n, int64_t k,
                                int splits, float* out, int64_t ld_out, int flags, void* workspace, size_t workspace_bytes,
                                gmlm_stream_t stream) {
-  GMLM_REQUIRE(dy && x && out && workspace, "wgrad_bf16: null pointer");
+  GMLM_REQUIRE(dy && x && out, "wgrad_bf16: null pointer");
   GMLM_REQUIRE(t >= wg::BT && n > 0 && k > 0, "wgrad_bf16: need t >= %d and n, k > 0 (t=%lld n=%lld k=%lld)", wg::BT, (long long)t,
                (long long)n, (long long)k);
   GMLM_REQUIRE(n % wg::TILE == 0 && k % wg::TILE == 0, "wgrad_bf16: n and k must be multiples of %d (n=%lld k=%lld)", wg::TILE,
@@ -277,7 +277,7 @@ extern "C" int gmlm_wgrad_bf16(const void* dy, int64_t ld_dy, const void* x, int
   GMLM_REQUIRE(ld_dy < (1ll << 26) && ld_x < (1ll << 26), "wgrad_bf16: row stride too large");
   const int s = wgrad_splits(t, n, k, splits);
   const size_t need = (size_t)s * (size_t)n * (size_t)k * sizeof(float);
-  if (workspace_bytes < need) {
+  if (!workspace || workspace_bytes < need) {
     set_error("wgrad_bf16: workspace of %zu bytes, need %zu", workspace_bytes, need);
     return GMLM_EWORKSPACE;
   }

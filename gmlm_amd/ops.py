@@ -798,7 +798,7 @@ class SoftMask(torch.autograd.Function):
         beta, n, f, tshape = ctx.cfg
         g = g.float().contiguous()
         dtok = torch.empty(f, dtype=torch.float32, device=g.device)
-        ws = _ws(lib().gmlm_colstats_workspace_bytes(n, f), g.device)
+        ws = _ws(lib().gmlm_softmask_blend_bwd_workspace_bytes(n, f), g.device)
         check(lib().gmlm_softmask_blend_bwd(_ptr(g), g.stride(0), _ptr(m8), beta, n, f, _ptr(dtok), _ptr(ws), ws.numel(),
                                             _stream()), "gmlm_softmask_blend_bwd")
         return None, None, dtok.view(tshape), None, None, None

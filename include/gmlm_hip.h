@@ -12,6 +12,17 @@
  *    (a hipStream_t passed as void*; NULL = the null stream);
  *  - every call returns 0 on success or a negative GMLM_E* code; gmlm_last_error() then returns a
  *    thread-local message; arguments are validated on the host BEFORE any launch;
+ *  - a pointer may be NULL only where its entry says so ("nullable", "optional", "NULL = ...", or required under a stated
+ *    condition); `stream` and every `seed_dev` are nullable everywhere.  Sizes, strides and dtype are checked before a call
+ *    with nothing to do returns GMLM_OK, and such a call needs no data pointer, except an output that it has to fill with
+ *    zeros (deg, rel_count, rowptr, s1 / s2, gs, dtoken, dgamma / dbeta / dbias, dw, dq_weight) and the cu_seqlens of the
+ *    causal varlen entries;
+ *  - workspaces: an entry point with a `workspace` has a `*_workspace_bytes` companion that takes the same sizes.  A NULL
+ *    workspace or fewer bytes than the companion returns is GMLM_EWORKSPACE, every other refusal is GMLM_EINVAL; the
+ *    companion of an empty problem still returns a positive size (gmlm_wgrad_bf16 has no empty problem: below t = 32 its
+ *    companion returns 0 and the call is refused).  No workspace needs initialising;
+ *  - alignment: "16-byte aligned" pointers are checked (GMLM_EINVAL); a pointer without that remark is read and written
+ *    with scalar accesses and needs only the alignment of its element type;
  *  - tensors are row-major and dense unless a stride argument says otherwise (strides in elements);
  *  - dtype: GMLM_F32 or GMLM_BF16 selects the storage type of activations; accumulation and all
  *    statistics are fp32; index arrays are int32 unless the reference hands over int64 (edge_index);
@@ -53,7 +64,9 @@ int gmlm_device_check(int* cu_count, int* wave_size, char* arch, int arch_len);
  *           (main.py:257-267) and RGCNConv's per-relation masked_edge_index compaction
  *           (PyG RGCNConv.forward, call sites main.py:272-308).
  * ------------------------------------------------------------------------------------------- */
-/* deg[v] = #{e : index[e] == v}; deg is zeroed by the call.  index values must be in [0, n). */
+/* deg[v] = #{e : index[e] == v}; deg is zeroed by the call.  index values must be in [0, n).
+ * K1 pointers are required whenever the array they name has an element (index when e > 0, deg when n > 0, ...); all
+ * accesses are scalar. */
 int gmlm_degree_i32(const int64_t* index, int64_t e, int64_t n, int32_t* deg, gmlm_stream_t stream);
 /* PyG `degree` drop-in: float32 counts. */
 int gmlm_degree_f32(const int64_t* index, int64_t e, int64_t n, float* deg, gmlm_stream_t stream);
@@ -61,12 +74,14 @@ int gmlm_degree_f32(const int64_t* index, int64_t e, int64_t n, float* deg, gmlm
  * source id outside [0, n) is typed 0 here (no out-of-bounds read) and rejected by gmlm_segment_sort's checks. */
 int gmlm_edge_bucket(const int64_t* src, const int32_t* deg, int64_t e, int64_t n, int64_t* edge_type,
                      gmlm_stream_t stream);
-/* rel_count[r] = #{e : edge_type[e] == r}, r < num_relations (zeroed by the call). */
+/* rel_count[r] = #{e : edge_type[e] == r}, r < num_relations in [1, 64] (zeroed by the call, also when e = 0). */
 int gmlm_relation_histogram(const int64_t* edge_type, int64_t e, int num_relations, int32_t* rel_count,
                             gmlm_stream_t stream);
 
 /* Stable segment sort.  key[e] = node[e] * r_active + (rel ? rel_remap[rel[e]] : 0).
- * Outputs: keys[e] (unsorted int32 keys, optional), perm[t] = original id of the t-th edge in
+ * rel is nullable (then rel_remap is unused; given, it requires rel_remap).  node and perm are required when e > 0; rowptr
+ * and bad_flag (zeroed by the call) always: e = 0 still fills rowptr with zeros.
+ * Outputs: keys[e] (unsorted int32 keys, nullable), perm[t] = original id of the t-th edge in
  * (key, original id) order, rowptr[s] = first t with sorted key >= s, s in [0, num_segments].
  * Edges whose relation maps to a negative remap entry are an error (GMLM_EINVAL is reported by
  * the caller-side check; the kernel clamps them to segment 0 and sets *bad_flag != 0). */
@@ -100,6 +115,8 @@ int gmlm_segment_inv_count(const int32_t* rowptr, int64_t num_segments, float* i
  * (`long_seg` [n_long], `chunk_ptr` [n_long+1], `chunk_owner` [n_chunks]) are index data built once per
  * graph by the caller (or on the device: gmlm_split_plan_build, entries of -1 = unused slot); pass long_threshold = 0 /
  * n_long = 0 for no splitting.
+ * src is required when src_rows > 0, idx when a segment has an edge (the caller's rowptr decides; not checkable on the
+ * host), edge_w is nullable (w_t = 1), the four plan arrays are required exactly when long_threshold > 0 and n_long > 0.
  * ------------------------------------------------------------------------------------------- */
 /* Split plan built on the device, for segment sets that change every step (the embedding-gradient segment sums: token /
  * position ids of the step's batch; replaces the scatter-add of hf BertEmbeddings' backward).  Arrays have CAPACITY size -
@@ -123,6 +140,7 @@ int gmlm_rgcn_mean_spmm(const void* src, int64_t src_rows, int64_t src_stride, c
  *   weight [num_bases, cols = in*out], W [r_active, cols]; all fp32 (master parameters).
  *   backward (one pass): dweight[b, :] = sum_r comp[r, b] * dW[r, :],  dcomp[r, b] = <dW[r, :], weight[b, :]>.
  * r_active <= 5, num_bases <= 32, cols % 4 == 0.  Deterministic (fixed-order reductions).
+ * weight, w, dw and dweight are 16-byte aligned (vector accesses); comp and dcomp are scalar.  No pointer is nullable.
  * ------------------------------------------------------------------------------------------- */
 int gmlm_basis_compose_fwd(const float* comp, const float* weight, int r_active, int num_bases, int64_t cols,
                            float* w, gmlm_stream_t stream);
@@ -136,17 +154,19 @@ int gmlm_basis_compose_bwd(const float* comp, const float* weight, const float* 
  * replaces: torch_geometric.nn.GraphNorm.forward -> F.gelu -> nn.Dropout (main.py:273-275 ...)
  * ------------------------------------------------------------------------------------------- */
 /* Column statistics of x [n, f] (`dtype`): s1[c] = sum_i (x[i,c] - shift[c]), s2[c] = sum_i (x[i,c]-shift[c])^2
- * (fp32).  shift may be NULL (= 0).  partial: workspace of gmlm_colstats_workspace_bytes(n, f).
+ * (fp32).  shift may be NULL (= 0).  workspace: gmlm_colstats_workspace_bytes(n, f).  s1 and s2 are the two rows of ONE
+ * [2, f] buffer (s2 == s1 + f); n = 0 fills them with zeros.  All K4 accesses are scalar: no alignment rule.
  * In all K4 entries x, y, g and dx share ONE storage dtype (the GEMM output feeds the norm directly). */
 size_t gmlm_colstats_workspace_bytes(int64_t n, int64_t f);
 int gmlm_colstats(const void* x, int dtype, const float* shift, int64_t n, int64_t f, float* s1, float* s2,
                   void* workspace, size_t workspace_bytes, gmlm_stream_t stream);
 /* mean[c], rstd[c] from (s1, s2, shift) over n_total rows:  mu = shift + s1/n; o = x - mu*ms;
- * var = E[o^2]; rstd = 1/sqrt(var + eps). */
+ * var = E[o^2]; rstd = 1/sqrt(var + eps).  shift is nullable (= 0), as in gmlm_colstats. */
 int gmlm_graphnorm_finalize(const float* s1, const float* s2, const float* shift, const float* mean_scale,
                             int64_t n_total, int64_t f, float eps, float* mean, float* rstd, gmlm_stream_t stream);
 /* y = dropout(gelu(weight * (x - mean*ms) * rstd + bias)); y stored as `dtype`; act != 0 applies GELU.
- * dropout: keep-probability scaling 1/(1-p), mask = hash(seed, element index) (replayable).
+ * dropout: keep-probability scaling 1/(1-p), mask = hash(seed, element index) (replayable); dropout_p in [0, 1), checked
+ * alike by the forward and both backward passes, which must draw the same mask.
  * Every entry with a `seed` also takes `seed_dev`: NULL, or a device pointer to one uint64 that the kernel ADDS to `seed`
  * when it runs.  A captured hipGraph replays its arguments unchanged; pointing seed_dev at a counter that the graph itself
  * increments gives every replay fresh masks while forward / recompute / backward of one replay still agree. */
@@ -154,12 +174,15 @@ int gmlm_graphnorm_apply(const void* x, const float* mean, const float* rstd, co
                          const float* bias, const float* mean_scale, int64_t n, int64_t f, int act,
                          float dropout_p, uint64_t seed, const uint64_t* seed_dev, void* y, int dtype, gmlm_stream_t stream);
 /* backward, pass 1: column sums needed by the closed form.  g = dL/dy (dtype), x = saved pre-norm input.
- * gs[0,c] = sum_i gz[i,c], gs[1,c] = sum_i gz[i,c] * ohat[i,c]   (gz = g through dropout and GELU) */
+ * gs[0,c] = sum_i gz[i,c], gs[1,c] = sum_i gz[i,c] * ohat[i,c]   (gz = g through dropout and GELU)
+ * workspace: gmlm_colstats_workspace_bytes(n, f) (the same two-row column reduction); n = 0 fills gs with zeros. */
 int gmlm_graphnorm_bwd_stats(const void* g, int dtype, const void* x, const float* mean, const float* rstd,
                              const float* weight, const float* bias, const float* mean_scale, int64_t n, int64_t f,
                              int act, float dropout_p, uint64_t seed, const uint64_t* seed_dev, float* gs /* [2, f] */,
                              void* workspace, size_t workspace_bytes, gmlm_stream_t stream);
-/* backward, pass 2: dx (`dtype`) and parameter grads from the (all-reduced) column sums over n_total rows. */
+/* backward, pass 2: dx (`dtype`) and parameter grads from the (all-reduced) column sums over n_total rows.
+ * dweight, dbias and dmean_scale (fp32 [f]) are each nullable: a NULL one is not written.  They are written even when
+ * n = 0 (a rank without rows still holds the all-reduced sums), so the parameters and gs are required then too. */
 int gmlm_graphnorm_bwd_apply(const void* g, int dtype, const void* x, const float* mean, const float* rstd,
                              const float* weight, const float* bias, const float* mean_scale, const float* gs,
                              int64_t n, int64_t n_total, int64_t f, int act, float dropout_p, uint64_t seed, const uint64_t* seed_dev,
@@ -171,12 +194,17 @@ int gmlm_graphnorm_bwd_apply(const void* g, int dtype, const void* x, const floa
  *           BertEmbeddings LayerNorm (hf:...:105), MultiScaleFusion.layer_norm (main.py:180),
  *           fusion_network LayerNorm+GELU (main.py:238-239).
  * z = dropout(x + bias) + residual;  y = act(LN(z) * gamma + beta)
+ * f: a multiple of 8 (bf16) / 4 (fp32), at most 1024.  x, y, dy, dx, residual, dresidual (`dtype`) and bias, gamma, beta
+ * (fp32 [f]) are 16-byte aligned: all are read and written 16 bytes at a time.  bias and residual are nullable (absent
+ * term), in the backward dresidual too (not written).  mean / rstd (fp32 [rows]) are nullable outputs of the forward (not
+ * stored) and required inputs of the backward.
  * ------------------------------------------------------------------------------------------- */
 int gmlm_bias_res_layernorm_fwd(const void* x, const float* bias, const void* residual, const float* gamma,
                                 const float* beta, int64_t rows, int64_t f, float eps, int act, float dropout_p,
                                 uint64_t seed, const uint64_t* seed_dev, void* y, float* mean, float* rstd, int dtype, gmlm_stream_t stream);
 /* dz (written to dx; the residual branch receives the same dz; dbias = column sum of dx through dropout)
- * partial parameter grads are reduced inside: dgamma/dbeta/dbias [f] fp32 (zero-initialised by the call). */
+ * partial parameter grads are reduced inside: dgamma/dbeta/dbias [f] fp32, each nullable (a NULL one is not written);
+ * rows = 0 fills the given ones with zeros.  workspace: gmlm_layernorm_bwd_workspace_bytes(rows, f). */
 size_t gmlm_layernorm_bwd_workspace_bytes(int64_t rows, int64_t f);
 int gmlm_bias_res_layernorm_bwd(const void* dy, const void* x, const float* bias, const void* residual,
                                 const float* gamma, const float* beta, const float* mean, const float* rstd,
@@ -191,7 +219,11 @@ int gmlm_bias_res_layernorm_bwd(const void* dy, const void* x, const float* bias
  *           K7 CrossAttention.forward's dense [1,8,N,N] softmax (main.py:159-163), no mask.
  * Layout: q [b, lq, h, d], k/v [b, lk, h, d] with row strides (elements) *_stride between
  * consecutive positions and h*d contiguous inside a position (so a fused [.., 3*h*d] QKV buffer
- * works without a copy); out [b, lq, h, d] dense; lse [b, h, lq] fp32 (log-sum-exp of scaled scores).
+ * works without a copy); out [b, lq, h, d] dense; lse [b, h, lq] fp32 (log-sum-exp of scaled scores; nullable in the
+ * forward = not stored, every forward kernel skips the store; required by the backward).
+ * q, k, v, out, out_lo, dout, dq, dk, dv are 16-byte aligned and every row stride is a multiple of 8 (bf16) / 4 (fp32)
+ * elements, at least h*d and below 2^24.  b*h <= 65535, scale > 0, dropout_p in [0, 1) (forward and backward alike).
+ * k and v are required when lk > 0.
  * kv_len: int32 [b] valid key count per sequence (NULL = all lk keys valid); keys >= kv_len[b]
  * are masked out exactly like the additive -inf padding mask of create_bidirectional_mask.
  * d in {64, 96}.  MFMA: bf16 32x32x16 for GMLM_BF16, f32 32x32x2 for GMLM_F32.
@@ -226,7 +258,7 @@ int gmlm_attention_fwd(const void* q, const void* k, const void* v, const int32_
                        float scale, float dropout_p, uint64_t seed, const uint64_t* seed_dev, void* out, void* out_lo, float* lse,
                        int dtype, const int32_t* cu_seqlens, int64_t max_len, const int32_t* seq_groups, int64_t num_groups,
                        gmlm_stream_t stream);
-/* packed mode: pass b = 1 (delta is [h, total_rows]) */
+/* packed mode: pass b = 1 (delta is [h, total_rows]).  The workspace is required on every path. */
 size_t gmlm_attention_bwd_workspace_bytes(int64_t b, int64_t h, int64_t lq, int64_t lk, int64_t d);
 int gmlm_attention_bwd(const void* q, const void* k, const void* v, const void* out, const void* dout,
                        const float* lse, const int32_t* kv_len, int64_t b, int64_t h, int64_t lq, int64_t lk,
@@ -265,7 +297,8 @@ int gmlm_attention_d128_bwd(const void* q, const void* k, const void* v, const v
  * output gradient by token id / position id (gmlm_segment_sort + gmlm_rgcn_mean_spmm with mean = 0).
  * F.embedding raises on an id outside its table; here an id outside [0, vocab) / [0, npos) is never read out of bounds (it is
  * clamped) and sets *bad_flag = 1 (device int32, nullable, NOT cleared by the call): the caller checks it when it next
- * synchronises, or validates its (static) id tensors once up front, as the Python host does. */
+ * synchronises, or validates its (static) id tensors once up front, as the Python host does.
+ * p % 4 == 0; word, pos, type0 and out are 16-byte aligned. */
 int gmlm_embed_sum_fwd(const float* word, const float* pos, const float* type0, const int64_t* tok, const int64_t* pos_ids,
                        int64_t rows, int64_t p, int64_t vocab, int64_t npos, void* out, int dtype, int32_t* bad_flag,
                        gmlm_stream_t stream);
@@ -275,6 +308,10 @@ int gmlm_embed_sum_fwd(const float* word, const float* pos, const float* type0, 
  * out[node_idx[b], :] = sum_t hs[b,t,:] * [t < len[b]] / max(len[b], 1e-9)     (out fp32 [n, p])
  * -------------------------------------------------------------------------------------------
  * cu_seqlens != NULL: hs is packed [total_rows, p], sequence b = rows [cu[b], cu[b+1]) (len / l unused).
+ * One of len / cu_seqlens is required, the other nullable.  b <= 65535.  Scalar accesses: no alignment rule.
+ * hs is required when l > 0; in packed mode (l is passed as 0) whenever a sequence has a row, which the caller's
+ * cu_seqlens decides and the host cannot check.  node_idx, out / dout and dhs are required.  b = 0 returns at once, the
+ * padded backward with l = 0 too.
  */
 int gmlm_meanpool_scatter_fwd(const void* hs, const int32_t* len, const int64_t* node_idx, int64_t b, int64_t l,
                               int64_t p, float* out, int dtype, const int32_t* cu_seqlens, gmlm_stream_t stream);
@@ -284,19 +321,24 @@ int gmlm_meanpool_scatter_bwd(const float* dout, const int32_t* len, const int64
 /* ---------------------------------------------------------------------------------------------
  * K9  soft-mask row blend                                           (main.py:92-99)
  * out[i,:] = mask[i] ? (1-beta)*x[i,:] + beta*token : x[i,:]     (out row stride out_stride, dtype out)
- * bwd: dtoken[c] = beta * sum_{i: mask[i]} dout[i,c]
+ * bwd: dtoken[c] = beta * sum_{i: mask[i]} dout[i,c]     (n = 0 fills dtoken with zeros)
+ * Scalar accesses: no alignment rule, any out_stride / dout_stride >= f.  No pointer is nullable.
+ * bwd workspace: gmlm_softmask_blend_bwd_workspace_bytes(n, f).
  * ------------------------------------------------------------------------------------------- */
 int gmlm_softmask_blend_fwd(const float* x, const uint8_t* mask, const float* token, float beta, int64_t n,
                             int64_t f, void* out, int64_t out_stride, int dtype, gmlm_stream_t stream);
+size_t gmlm_softmask_blend_bwd_workspace_bytes(int64_t n, int64_t f);
 int gmlm_softmask_blend_bwd(const float* dout, int64_t dout_stride, const uint8_t* mask, float beta, int64_t n,
                             int64_t f, float* dtoken, void* workspace, size_t workspace_bytes, gmlm_stream_t stream);
 
 /* GELU (exact erf) + dropout elementwise with optional bias, used for BertIntermediate
- * (hf:modeling_bert.py:333-336) and classifier.1 (main.py:245): y = dropout(gelu(x + bias)). */
+ * (hf:modeling_bert.py:333-336) and classifier.1 (main.py:245): y = dropout(gelu(x + bias)).
+ * f: a multiple of 8 (bf16) / 4 (fp32); x, y, dy, dx 16-byte aligned; bias (fp32 [f], scalar loads) is nullable. */
 int gmlm_bias_gelu_fwd(const void* x, const float* bias, int64_t rows, int64_t f, float dropout_p, uint64_t seed, const uint64_t* seed_dev,
                        void* y, int dtype, gmlm_stream_t stream);
 /* dx = dy * dropout_mask * gelu'(x + bias); dbias (nullable) [f] = column sums of dx, accumulated in fp32
- * inside the same pass (workspace: gmlm_bias_gelu_bwd_workspace_bytes). */
+ * inside the same pass (workspace: gmlm_bias_gelu_bwd_workspace_bytes; required with dbias, unused and nullable
+ * without it).  rows = 0 fills dbias with zeros. */
 size_t gmlm_bias_gelu_bwd_workspace_bytes(int64_t rows, int64_t f, int dtype);
 int gmlm_bias_gelu_bwd(const void* dy, const void* x, const float* bias, int64_t rows, int64_t f, float dropout_p,
                        uint64_t seed, const uint64_t* seed_dev, void* dx, float* dbias, int dtype, void* workspace, size_t workspace_bytes,

@@ -261,13 +261,13 @@ def test_refusals_decided_before_any_launch(lib):
     need = lib.gmlm_basis_compose_bwd_workspace_bytes(ra, nb, cols)
     assert need == basis_blocks(cols) * ra * nb * 4
     rc = lib.gmlm_basis_compose_bwd(a, a, a, ra, nb, cols, a, a, a, need - 4, None)
-    assert rc == -1 and msgs[(0, 4)] in lib.gmlm_last_error()
+    assert rc == -2 and msgs[(0, 4)] in lib.gmlm_last_error()
 
     e = 3001
     need = lib.gmlm_segment_sort_workspace_bytes(e)
     assert need >= 3 * 4 * e
     rc = lib.gmlm_segment_sort(a, None, None, 1, e, 40, None, a, a, a, a, need - 1, None)
-    assert rc == -1 and b"workspace too small" in lib.gmlm_last_error()
+    assert rc == -2 and b"workspace too small" in lib.gmlm_last_error()
 
     items = 65535 * THRESH
     rc = lib.gmlm_split_plan_build(a, 1, items, THRESH, a, a, a, None)

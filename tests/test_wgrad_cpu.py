@@ -46,7 +46,8 @@ def test_wgrad_workspace_plan():
 ])
 def test_wgrad_rejects_bad_arguments(bad):
     lib = _lib_or_skip()
-    assert _call(lib, **bad) == -1                       # GMLM_EINVAL, returned before anything is launched
+    # GMLM_EINVAL, returned before anything is launched; a missing workspace is GMLM_EWORKSPACE like a short one
+    assert _call(lib, **bad) == (-2 if bad == dict(ws=0) else -1)
     assert b"wgrad_bf16" in lib.gmlm_last_error()
 
 
