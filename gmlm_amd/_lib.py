@@ -1,4 +1,4 @@
-"""ctypes binding of libgmlm_hip.so (C ABI: include/gmlm_hip.h).
+"""ctypes binding of libgmlm_hip.so (C ABI: include/gmlm_hip.h and include/gmlm_hip_split.h).
 
 The product path has NO fallback: if the shared library is missing or a call fails, a Python
 exception is raised.  Build with ``python -c "import __graft_entry__ as g; g.build()"`` or
@@ -92,6 +92,11 @@ SIGNATURES = {
     "gmlm_wgrad_bf16": (C.c_int, [_p, _i64, _p, _i64, _i64, _i64, _i64, _i32, _p, _i64, _i32, _p, _sz, _p]),
 }
 
+# second header, include/gmlm_hip_split.h (the bf16x3 operand split); same conventions, bound next to the first table
+SIGNATURES_SPLIT = {
+    "gmlm_split_bf16x3": (C.c_int, [_p, _i64, _i64, _i64, _i64, _p, _i64, _i64, _i32, _p]),
+}
+
 
 class GmlmHipError(RuntimeError):
     pass
@@ -110,7 +115,7 @@ def lib() -> C.CDLL:
             f"{LIB_PATH} not found: the HIP extension is not built. Run `make -C gmlm_amd/csrc` "
             "(or __graft_entry__.build()). gmlm_amd has no CPU / eager fallback.")
     handle = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_SPLIT.items()):
         fn = getattr(handle, name)  # AttributeError here = header / library mismatch
         fn.restype, fn.argtypes = res, args
     if handle.gmlm_version() != 1:

@@ -54,9 +54,15 @@ def _layer_masters(layer):
             so.dense.weight, layer.intermediate.dense.weight, layer.output.dense.weight)
 
 
-def prepare_weights(plm, cd):
+def prepare_weights(plm, cd, gemm_precision="native"):
     """One flat buffer in the compute dtype for all layers' GEMM weights, filled by ONE multi-tensor copy
-    (Q/K/V rows land directly in the fused [3P, P] operand, so there is no concatenation either)."""
+    (Q/K/V rows land directly in the fused [3P, P] operand, so there is no concatenation either).
+    ``gemm_precision`` "bf16x3" (fp32 only): ``lw.w*`` then hold ``ops.SplitWeight`` objects, the two bf16 three-part forms of the
+    fused fp32 operand, split once here for all micro-batches; ``nn._mm`` picks the GEMM by the operand's type."""
+    if gemm_precision not in ("native", "bf16x3"):
+        raise ValueError(f"gemm_precision must be 'native' or 'bf16x3', got {gemm_precision!r}")
+    if gemm_precision == "bf16x3" and cd != torch.float32:
+        raise ValueError("gemm_precision='bf16x3' keeps fp32 storage: the compute dtype must be float32")
     layers = list(plm.encoder.layer)
     out, srcs, dsts = [], [], []
     with torch.no_grad():
@@ -103,6 +109,9 @@ def prepare_weights(plm, cd):
             out.append(lw)
         if dsts:
             torch._foreach_copy_(dsts, srcs)
+        if gemm_precision == "bf16x3":
+            for lw in out:
+                lw.wqkv, lw.wo, lw.wi, lw.wo2 = (ops.SplitWeight(w) for w in (lw.wqkv, lw.wo, lw.wi, lw.wo2))
     return out
 
 

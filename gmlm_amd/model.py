@@ -22,7 +22,7 @@ from torch.utils.checkpoint import checkpoint
 
 from . import bert, ops, qwen3
 from .graph import GraphCache, RelCSR
-from .nn import (SPLITK_ROW_QUANTUM, CrossAttention, GraphNorm, MultiScaleFusion, RGCNConv, _linear, compute_dtype,
+from .nn import (GEMM_PRECISIONS, SPLITK_ROW_QUANTUM, CrossAttention, GraphNorm, MultiScaleFusion, RGCNConv, _linear, compute_dtype,
                  cross_attention_specs, linear_specs, shadow_params, use_shadow)
 
 logger = logging.getLogger(__name__)
@@ -107,8 +107,13 @@ class GraphTextLM(nn.Module):
     def __init__(self, gnn_in_channels, hidden_channels, num_classes, num_relations=5, num_bases=30, dropout_rate=0.3,
                  model_name='thenlper/gte-base', plm_max_length=256, *, plm_encoder=None, plm_tokenizer=None,
                  compute_dtype: Optional[torch.dtype] = None, activation_checkpointing: bool = False,
-                 plm_gradient_checkpointing: bool = False):
+                 plm_gradient_checkpointing: bool = False, gemm_precision: str = "native"):
         super().__init__()
+        if gemm_precision not in GEMM_PRECISIONS:
+            raise ValueError(f"gemm_precision must be one of {GEMM_PRECISIONS}, got {gemm_precision!r}")
+        if gemm_precision == "bf16x3" and compute_dtype not in (None, torch.float32):
+            raise ValueError("gemm_precision='bf16x3' keeps fp32 storage and runs only the dense-layer GEMMs on the bf16 matrix "
+                             f"pipe; it cannot be combined with compute_dtype={compute_dtype}")
         self.gnn_mask_token_embed = nn.Parameter(torch.zeros(1, gnn_in_channels))
         nn.init.xavier_uniform_(self.gnn_mask_token_embed)
         hc = hidden_channels
@@ -150,6 +155,9 @@ class GraphTextLM(nn.Module):
 
         self.num_relations = num_relations
         self.compute_dtype = compute_dtype
+        # "bf16x3": fp32 storage everywhere, the dense layers that go through nn._linear / nn._mm as ONE bf16 GEMM of three times
+        # the depth with an fp32 result (ops.LinearBf16x3); "native": every GEMM in the compute dtype
+        self.gemm_precision = gemm_precision
         self.activation_checkpointing = activation_checkpointing
         self.plm_gradient_checkpointing = plm_gradient_checkpointing
         self.plm_packed = True
@@ -172,8 +180,17 @@ class GraphTextLM(nn.Module):
         self._graphed = None      # gmlm_amd.graphs.GraphedStep: hipGraph recording of the GNN + head regions (capture_hip_graphs)
 
     # ------------------------------------------------------------------------------------------
-    def _cd(self) -> torch.dtype:
+    def _compute_dtype(self) -> torch.dtype:
+        """The storage / compute dtype of this call.  A bf16x3 model is an fp32 model also under ``torch.amp.autocast`` (the
+        reference's training loop wraps every step in it, main.py:348): its reduced precision is inside the GEMMs only."""
+        if self.gemm_precision == "bf16x3":
+            return torch.float32
         return compute_dtype(self.compute_dtype)
+
+    _cd = _compute_dtype
+
+    def _prepare_weights(self):
+        return self._enc.prepare_weights(self.plm_encoder, self._cd(), self.gemm_precision)
 
     @property
     def _enc(self):
@@ -236,10 +253,10 @@ class GraphTextLM(nn.Module):
         # compute-dtype operands of this region's dense layers: one flat buffer, one multi-tensor copy (nn.ParamShadow); kept on
         # the module so that a checkpoint recompute of a block (which runs in backward, outside this call) finds the same operands
         specs = linear_specs(self.residual_proj1, self.residual_proj2)
-        for k in (1, 2, 3, 4):
+        for k in (1, 2, 3, 4) if self.gemm_precision == "native" else ():   # bf16x3: the root GEMMs stay native fp32
             conv = getattr(self, f"rgcn{k}")
             specs += [(id(conv.root), [conv.root], x0.shape[1] - f_in if k == 1 else 0), (id(conv.bias), [conv.bias], 0)]
-        with shadow_params(specs, cd, x0.device) as sh:
+        with shadow_params(specs, cd, x0.device, self.gemm_precision) as sh:
             self._gnn_shadow = sh
             return self._graph_embeddings_body(x0, f_in, cd, run)
 
@@ -392,7 +409,7 @@ class GraphTextLM(nn.Module):
                     return g.encoder(self, key, tokens, args)
                 return self.encode_packed_static(tokens, key, *args, *(() if short else (None,)), weights)
             if weights is None:
-                weights = self._enc.prepare_weights(self.plm_encoder, cd)
+                weights = self._prepare_weights()
             lens_h = tokens.lens_host[idx_h]
             # length-bucketed micro-batches: every active node is encoded independently and scattered by its own
             # index, so the order is free; sorting by token count keeps the padding of each micro-batch small
@@ -457,6 +474,8 @@ class GraphTextLM(nn.Module):
         (``bucketed_layout``): its tokens are [PAD], its pooled row is the sink row N that is cut off."""
         _, s_b, t_b, _, lmax, n = key
         dev = lens_all.device
+        if weights is None and self.gemm_precision != "native":
+            weights = self._prepare_weights()
         p = self.plm_encoder.config.hidden_size
         seq = torch.repeat_interleave(torch.arange(s_b, device=dev), lens_all.long(), output_size=t_b)
         pos = torch.arange(t_b, device=dev) - cu_all[seq].long()
@@ -505,7 +524,7 @@ class GraphTextLM(nn.Module):
             gnn_embeds = self.get_graph_embeddings(gnn_input_features, edge_index, edge_type)
             tokens = self.tokenize(all_node_texts)
             with torch.cuda.stream(side):
-                weights = self._enc.prepare_weights(self.plm_encoder, self._cd())
+                weights = self._prepare_weights()
                 plm_embeds = self.encode_texts(tokens, text_processing_node_mask, plm_batch_size, mask_copy, weights)
             cur.wait_stream(side)                                     # join
             plm_embeds.record_stream(cur)                             # allocated on `side`, read (and saved for backward) on `cur`
@@ -529,7 +548,7 @@ class GraphTextLM(nn.Module):
                 self.active_index.record_stream(cur)
             return g.head(gnn_embeds, plm_embeds)
         # (a recorded encoder casts the weights inside its own graph)
-        weights = None if (replay and g.encoder_enabled) else self._enc.prepare_weights(self.plm_encoder, self._cd())
+        weights = None if (replay and g.encoder_enabled) else self._prepare_weights()
         gnn_embeds = g.gnn(gnn_input_features) if replay else \
             self.get_graph_embeddings(gnn_input_features, edge_index, edge_type)               # fp32 [N, P]
         tokens = self.tokenize(all_node_texts)
@@ -547,6 +566,9 @@ class GraphTextLM(nn.Module):
         for THIS input shape and ``edge_index`` tensor; ``forward`` then replays them (training mode, same shape, same
         edge tensor) and runs eagerly otherwise.  For the launch-bound small configurations (gmlm_amd/graphs.py)."""
         from . import graphs
+        if self.gemm_precision != "native":
+            raise NotImplementedError("hipGraph capture of a gemm_precision='bf16x3' model is not implemented: record a native "
+                                      "model, or run this one eagerly")
         if self._enc is not bert and encoder:
             raise NotImplementedError("hipGraph capture of the text encoder covers BERT-geometry encoders only; pass encoder=False "
                                       "to record the GNN and head regions around an eager Qwen3 encoder")
@@ -561,7 +583,7 @@ class GraphTextLM(nn.Module):
         fn, c = self.fusion_network, self.classifier
         specs = (cross_attention_specs(self.graph_to_text_attn) + cross_attention_specs(self.text_to_graph_attn)
                  + linear_specs(c[3]) + [(id(fn[0].weight), [fn[0].weight], 0), (id(c[0].weight), [c[0].weight], 0)])
-        with shadow_params(specs, cd, gnn_embeds.device) as sh:
+        with shadow_params(specs, cd, gnn_embeds.device, self.gemm_precision) as sh:
             if sh is not None and self._branch_stream is not None and self.dist is None:
                 sh.record_stream(self._branch_stream)              # the second cross-attention reads its operands on the branch
             return self._head_body(gnn_embeds, plm_embeds, cd)
@@ -572,6 +594,7 @@ class GraphTextLM(nn.Module):
         ring = self.dist.ring_attention if (self.dist is not None and self.dist.use_ring) else None
         gather = self.dist.all_gather_rows if (self.dist is not None and ring is None) else None
         self.graph_to_text_attn.compute_dtype = self.text_to_graph_attn.compute_dtype = cd
+        self.graph_to_text_attn.gemm_precision = self.text_to_graph_attn.gemm_precision = self.gemm_precision
         bs = self._branch_stream if self.dist is None else None
         if bs is not None:
             # whole-step recording (graphs.py): the two cross-attentions are independent - the second one goes to a branch of

@@ -54,15 +54,27 @@ def _glorot(t: torch.Tensor) -> None:
         t.uniform_(-a, a)
 
 
-def _linear(x, weight, bias=None):
+GEMM_PRECISIONS = ("native", "bf16x3")
+
+
+def _linear(x, weight, bias=None, gemm_precision="native"):
     """x @ weight^T (+ bias) in x's dtype with autocast off (explicit precision policy).  Inside ``shadow_params`` the operands
-    come from the region's shadow and the gradients go to the fp32 masters directly; otherwise per-call casts."""
+    come from the region's shadow and the gradients go to the fp32 masters directly; otherwise per-call casts.
+    ``gemm_precision`` "bf16x3" (fp32 ``x`` on the GPU): outside a shadow the weight is split for this call (ops.SplitWeight);
+    a shadow built for that mode already holds the split weights, whatever is passed here."""
     sh = _SHADOW
     if sh is not None and x.dtype == sh.dtype:
         wc = sh.get(id(weight))
         bc = sh.get(id(bias)) if bias is not None else None
         if wc is not None and (bias is None or bc is not None):
             return _mm(x, wc, bc, (weight,) + ((bias,) if bias is not None else ()))
+    if gemm_precision != "native":
+        if gemm_precision != "bf16x3":
+            raise ValueError(f"gemm_precision must be one of {GEMM_PRECISIONS}, got {gemm_precision!r}")
+        if x.dtype != torch.float32:
+            raise TypeError(f"gemm_precision='bf16x3' keeps fp32 storage; got {x.dtype} activations")
+        return _mm(x, ops.SplitWeight(weight), None if bias is None else bias.detach(),
+                   (weight,) + ((bias,) if bias is not None else ()))
     with torch.autocast("cuda", enabled=False):
         w = weight.to(x.dtype)
         b = None if bias is None else bias.to(x.dtype)
@@ -185,8 +197,11 @@ class _Linear(torch.autograd.Function):
 
 
 def _mm(x, wc, bc, masters, residual=False, bias_grad=True):
+    """``wc``: the compute-dtype copy of the weight, or its ``ops.SplitWeight`` (gemm_precision "bf16x3": the operand itself says
+    which GEMM runs, so a checkpoint recompute that is handed the same operands takes the same path)."""
     with torch.autocast("cuda", enabled=False):
-        return _Linear.apply(x, wc, bc, residual, bias_grad, *masters)
+        fn = ops.LinearBf16x3 if isinstance(wc, ops.SplitWeight) else _Linear
+        return fn.apply(x, wc, bc, residual, bias_grad, *masters)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -235,22 +250,53 @@ class ParamShadow:
             self.flat.record_stream(stream)
 
 
-_SHADOW: Optional[ParamShadow] = None
+class SplitShadow:
+    """The shadow of an fp32 region in gemm_precision "bf16x3": every 2-D entry of ``specs`` (a weight, or several stacked along
+    dim 0) as an ``ops.SplitWeight``, split ONCE per region call; every 1-D entry (a bias) as its fp32 values.  Looked up by the
+    same keys as ``ParamShadow`` and re-entered by a checkpoint recompute through ``use_shadow``.  The caller lists only the
+    parameters of layers that go through ``_linear`` / ``_mm``: what is not listed stays on the native fp32 path."""
+    dtype = torch.float32
+
+    def __init__(self, specs, device):
+        self.views = {}
+        with torch.no_grad():
+            for key, masters, pad in specs:
+                if pad:
+                    raise ValueError("bf16x3 shadow entries take no pad rows")
+                w = masters[0].detach() if len(masters) == 1 else torch.cat([m.detach() for m in masters], 0)
+                self.views[key] = ops.SplitWeight(w) if w.dim() == 2 else w
+
+    def get(self, key):
+        return self.views.get(key)
+
+    def record_stream(self, stream) -> None:
+        for v in self.views.values():
+            for t in ((v.w0, v.w1s) if isinstance(v, ops.SplitWeight) else (v,)):
+                if t.is_cuda:
+                    t.record_stream(stream)
+
+
+_SHADOW = None             # the ParamShadow / SplitShadow of the region that is running
 
 
 class shadow_params:
     """``with shadow_params(specs, dtype, device):`` - the dense layers called inside find their compute-dtype operands in the
-    shadow (``_linear`` by ``id(weight)``); no-op for fp32 (the masters ARE the operands)."""
+    shadow (``_linear`` by ``id(weight)``); no-op for fp32 (the masters ARE the operands) unless ``gemm_precision`` is "bf16x3":
+    then the shadow holds the split weights (``SplitShadow``)."""
 
-    def __init__(self, specs, dtype, device):
+    def __init__(self, specs, dtype, device, gemm_precision="native"):
         self.args = (specs, dtype, device)
+        self.x3 = gemm_precision == "bf16x3"
         self.prev = None
 
     def __enter__(self):
         global _SHADOW
         self.prev = _SHADOW
         specs, dtype, device = self.args
-        _SHADOW = ParamShadow(specs, dtype, device) if (dtype != torch.float32 and device.type == "cuda") else None
+        if self.x3 and dtype == torch.float32 and device.type == "cuda":
+            _SHADOW = SplitShadow(specs, device)
+        else:
+            _SHADOW = ParamShadow(specs, dtype, device) if (dtype != torch.float32 and device.type == "cuda") else None
         return _SHADOW
 
     def __exit__(self, *exc):
@@ -476,6 +522,7 @@ class CrossAttention(nn.Module):
         self.out_proj = nn.Linear(dim, dim)
         self.dropout = nn.Dropout(dropout)
         self.compute_dtype: Optional[torch.dtype] = None
+        self.gemm_precision = "native"          # "bf16x3": the four projections on the three-product bf16 GEMM (fp32 storage)
 
     def forward(self, x, y, kv_gather=None, ring=None):
         """x: [B, N, C] queries, y: [B, M, C] keys/values (the reference calls it with B == 1).
@@ -483,10 +530,11 @@ class CrossAttention(nn.Module):
         Node partition: ``kv_gather`` maps the local [B, M, 2C] K|V projection to the
         global one (all-gather, small graphs); ``ring(q, kv, num_heads, block, seed)`` instead runs the ring
         exchange with carried online-softmax state (gmlm_amd.dist.PartitionContext.ring_attention)."""
-        cd = compute_dtype(self.compute_dtype)
+        gp = self.gemm_precision
+        cd = torch.float32 if gp == "bf16x3" else compute_dtype(self.compute_dtype)
         b, n, c = x.shape
         xq, yk = x.to(cd), y.to(cd)
-        q = _linear(xq, self.q_proj.weight, self.q_proj.bias)
+        q = _linear(xq, self.q_proj.weight, self.q_proj.bias, gp)
         sh = _SHADOW
         wkv = sh.get(("kv_w", id(self))) if (sh is not None and yk.dtype == sh.dtype) else None
         if wkv is not None:                                           # fused K|V operand straight from the region's shadow
@@ -495,16 +543,16 @@ class CrossAttention(nn.Module):
         else:
             wkv = torch.cat([self.k_proj.weight, self.v_proj.weight], 0)
             bkv = torch.cat([self.k_proj.bias, self.v_proj.bias], 0)
-            kv = _linear(yk, wkv, bkv)                                # [B, M, 2C] fused K|V
+            kv = _linear(yk, wkv, bkv, gp)                            # [B, M, 2C] fused K|V
         if ring is not None:
             p = self.dropout.p if self.training else 0.0
             o = ring(q, kv, self.num_heads, ops.AttentionBlock(self.num_heads, self.scale, p), ops.draw_seed() if p > 0 else 0)
-            return _linear(o, self.out_proj.weight, self.out_proj.bias)
+            return _linear(o, self.out_proj.weight, self.out_proj.bias, gp)
         if kv_gather is not None:
             kv = kv_gather(kv)
         k, v = _SplitLast.apply(kv, c)
         o = attention_any_dim(q, k, v, None, self.num_heads, self.scale, self.dropout.p, self.training)
-        return _linear(o, self.out_proj.weight, self.out_proj.bias)
+        return _linear(o, self.out_proj.weight, self.out_proj.bias, gp)
 
 
 class _SplitLast(torch.autograd.Function):

@@ -108,9 +108,14 @@ def _layer_masters(layer):
             mlp.down_proj.weight)
 
 
-def prepare_weights(plm, cd):
+def prepare_weights(plm, cd, gemm_precision="native"):
     """One flat buffer in the compute dtype for all layers' GEMM weights, filled by ONE multi-tensor copy (Q/K/V rows land
-    directly in the fused [(hq + 2 hkv) * 128, P] operand, gate / up rows in the fused [2 I, P] one)."""
+    directly in the fused [(hq + 2 hkv) * 128, P] operand, gate / up rows in the fused [2 I, P] one).
+    ``gemm_precision`` "bf16x3" (fp32 only): the four operands become ``ops.SplitWeight`` objects (see bert.prepare_weights)."""
+    if gemm_precision not in ("native", "bf16x3"):
+        raise ValueError(f"gemm_precision must be 'native' or 'bf16x3', got {gemm_precision!r}")
+    if gemm_precision == "bf16x3" and cd != torch.float32:
+        raise ValueError("gemm_precision='bf16x3' keeps fp32 storage: the compute dtype must be float32")
     layers = list(plm.layers)
     out, srcs, dsts = [], [], []
     padded = lambda n: (n + 127) // 128 * 128                 # keep every operand 256-byte aligned
@@ -150,6 +155,9 @@ def prepare_weights(plm, cd):
             out.append(lw)
         if dsts:
             torch._foreach_copy_(dsts, srcs)
+        if gemm_precision == "bf16x3":
+            for lw in out:
+                lw.wqkv, lw.wo, lw.wgu, lw.wdown = (ops.SplitWeight(w) for w in (lw.wqkv, lw.wo, lw.wgu, lw.wdown))
     return out
 
 
