@@ -1,4 +1,4 @@
-"""ctypes binding of libgmlm_hip.so (C ABI: include/gmlm_hip.h and include/gmlm_hip_split.h).
+"""ctypes binding of libgmlm_hip.so (C ABI: include/gmlm_hip.h, include/gmlm_hip_split.h and include/gmlm_hip_optim.h).
 
 The product path has NO fallback: if the shared library is missing or a call fails, a Python
 exception is raised.  Build with ``python -c "import __graft_entry__ as g; g.build()"`` or
@@ -97,6 +97,14 @@ SIGNATURES_SPLIT = {
     "gmlm_split_bf16x3": (C.c_int, [_p, _i64, _i64, _i64, _i64, _p, _i64, _i64, _i32, _p]),
 }
 
+# third header, include/gmlm_hip_optim.h (gradient clipping + AdamW as one multi-tensor step)
+SIGNATURES_OPTIM = {
+    "gmlm_adamw_chunk_elems": (_i64, []),
+    "gmlm_adamw_sumsq": (C.c_int, [_p, _p, _p, _i64, _p, _p, _p]),
+    "gmlm_adamw_finalize": (C.c_int, [_p, _p, _i64, _f32, _p, _p, _i64, _p, _i64, _p, _i64, _p, _p, _p]),
+    "gmlm_adamw_update": (C.c_int, [_p, _p, _p, _p, _i64, _p, _i64, _p, _p, _p]),
+}
+
 
 class GmlmHipError(RuntimeError):
     pass
@@ -115,7 +123,7 @@ def lib() -> C.CDLL:
             f"{LIB_PATH} not found: the HIP extension is not built. Run `make -C gmlm_amd/csrc` "
             "(or __graft_entry__.build()). gmlm_amd has no CPU / eager fallback.")
     handle = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_SPLIT.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_SPLIT.items()) + list(SIGNATURES_OPTIM.items()):
         fn = getattr(handle, name)  # AttributeError here = header / library mismatch
         fn.restype, fn.argtypes = res, args
     if handle.gmlm_version() != 1:

@@ -3,8 +3,8 @@
 
 Only the step logic is mirrored (mask sampling -> soft mask -> forward -> CE(label_smoothing=0.2) ->
 backward -> clip_grad_norm_(1.0) -> AdamW(3 name-based groups) -> linear warm-up), with stock
-``torch.optim`` / schedulers exactly like the reference; logging, wandb, early stopping bookkeeping and the
-experiment driver stay with the caller.
+``torch.optim`` / schedulers exactly like the reference (``setup_optimizer(..., fused=True)`` swaps the clip + AdamW pair for
+``gmlm_amd.FusedAdamW``, opt-in); logging, wandb, early stopping bookkeeping and the experiment driver stay with the caller.
 """
 from __future__ import annotations
 
@@ -17,13 +17,15 @@ import torch.nn.functional as F
 import torch.optim as optim
 
 from . import ops
+from .optim import FusedAdamW
 
 GNN_PARAM_NAMES = ['rgcn1', 'rgcn2', 'rgcn3', 'gnorm1', 'gnorm2', 'gnorm3', 'residual_proj1', 'residual_proj2',
                    'residual_proj3']   # main.py:379 (rgcn4 / gnorm4 fall into "other", as in the reference)
 
 
-def setup_optimizer(model, lr_graph, lr_bert, lr_other, weight_decay):
-    """main.py:375-398: AdamW with three parameter groups selected by NAME."""
+def setup_optimizer(model, lr_graph, lr_bert, lr_other, weight_decay, fused=False):
+    """main.py:375-398: AdamW with three parameter groups selected by NAME.  ``fused=True``: the same groups in a
+    ``gmlm_amd.FusedAdamW`` (clip + AdamW as one multi-tensor step on the HIP kernels) instead of ``torch.optim.AdamW``."""
     graph_params, bert_params, other_params = [], [], []
     for name, param in model.named_parameters():
         if not param.requires_grad:
@@ -34,7 +36,7 @@ def setup_optimizer(model, lr_graph, lr_bert, lr_other, weight_decay):
             graph_params.append(param)
         else:
             other_params.append(param)
-    return optim.AdamW([
+    return (FusedAdamW if fused else optim.AdamW)([
         {'params': graph_params, 'lr': lr_graph, 'weight_decay': weight_decay},
         {'params': bert_params, 'lr': lr_bert, 'weight_decay': 0.01},
         {'params': other_params, 'lr': lr_other, 'weight_decay': weight_decay}])
@@ -205,8 +207,11 @@ def train_step(model, optimizer, scheduler, x, edge_index, texts, y, active_mask
     loss.backward()
     if dist_ctx is not None:
         dist_ctx.grad_buckets(model).finish()
-    torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm=grad_clip_norm)
-    optimizer.step()
+    if isinstance(optimizer, FusedAdamW):                 # one norm pass, clip coefficient applied inside the update
+        optimizer.step(max_grad_norm=grad_clip_norm)
+    else:
+        torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm=grad_clip_norm)
+        optimizer.step()
     if scheduler is not None:
         scheduler.step()
     return StepResult(float(loss_value), acc)

@@ -354,6 +354,24 @@ def mm_bf16x3(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
         return LinearBf16x3.apply(a, SplitWeight(b), None, False, True, b)
 
 
+# ---------------------------------------------------------------------------------------------
+# gradient clipping + AdamW as one multi-tensor step (include/gmlm_hip_optim.h; the tables are built by optim.FusedAdamW)
+# ---------------------------------------------------------------------------------------------
+def adamw_step(addr, numel, group, slot, chunks, num_chunks, num_tensors, hyper, num_groups, steps, num_slots, partial, nonfinite,
+               bias_corr, status, max_norm: float) -> None:
+    """The three launches of one step on the current stream: sum of squares per chunk -> norm, clip coefficient, skip, step
+    counters and bias corrections -> update of p, m, v.  Every table is a raw device address laid out as the header says."""
+    st = _stream()
+    with _span("adamw_sumsq"):
+        check(lib().gmlm_adamw_sumsq(addr, numel, chunks, num_chunks, partial, nonfinite, st), "gmlm_adamw_sumsq")
+    with _span("adamw_finalize"):
+        check(lib().gmlm_adamw_finalize(partial, nonfinite, num_chunks, float(max_norm), group, slot, num_tensors, hyper,
+                                        num_groups, steps, num_slots, bias_corr, status, st), "gmlm_adamw_finalize")
+    with _span("adamw_update"):
+        check(lib().gmlm_adamw_update(addr, numel, group, chunks, num_chunks, hyper, num_groups, bias_corr, status, st),
+              "gmlm_adamw_update")
+
+
 def device_split_plan(rowptr: torch.Tensor, num_items: int, thresh: int = 64):
     """``graph.SplitPlan`` for segments known only on the device (they change every step): capacity-sized arrays filled by ONE
     kernel, no host round trip; unused slots are -1 and skipped by the aggregation kernels (gmlm_split_plan_build)."""
