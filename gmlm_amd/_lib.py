@@ -1,4 +1,4 @@
-"""ctypes binding of libgmlm_hip.so (C ABI: include/gmlm_hip.h, include/gmlm_hip_split.h and include/gmlm_hip_optim.h).
+"""ctypes binding of libgmlm_hip.so (C ABI: include/gmlm_hip.h, gmlm_hip_split.h, gmlm_hip_optim.h and gmlm_hip_d32.h).
 
 The product path has NO fallback: if the shared library is missing or a call fails, a Python
 exception is raised.  Build with ``python -c "import __graft_entry__ as g; g.build()"`` or
@@ -105,6 +105,15 @@ SIGNATURES_OPTIM = {
     "gmlm_adamw_update": (C.c_int, [_p, _p, _p, _p, _i64, _p, _i64, _p, _p, _p]),
 }
 
+# fourth header, include/gmlm_hip_d32.h (attention at head dim 32: padded and packed, 1-D grids)
+SIGNATURES_D32 = {
+    "gmlm_attention_d32_fwd": (C.c_int, [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _f32, _u64, _p,
+                                         _p, _p, _p, _i32, _p, _i64, _p]),
+    "gmlm_attention_d32_bwd_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "gmlm_attention_d32_bwd": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32,
+                                         _f32, _u64, _p, _p, _p, _p, _i64, _i64, _i64, _i32, _p, _i64, _p, _sz, _p, _p]),
+}
+
 
 class GmlmHipError(RuntimeError):
     pass
@@ -123,7 +132,8 @@ def lib() -> C.CDLL:
             f"{LIB_PATH} not found: the HIP extension is not built. Run `make -C gmlm_amd/csrc` "
             "(or __graft_entry__.build()). gmlm_amd has no CPU / eager fallback.")
     handle = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_SPLIT.items()) + list(SIGNATURES_OPTIM.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_SPLIT.items()) + list(SIGNATURES_OPTIM.items()) + \
+            list(SIGNATURES_D32.items()):
         fn = getattr(handle, name)  # AttributeError here = header / library mismatch
         fn.restype, fn.argtypes = res, args
     if handle.gmlm_version() != 1:

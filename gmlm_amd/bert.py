@@ -22,6 +22,12 @@ from torch.utils.checkpoint import checkpoint
 from . import ops
 from .nn import _Linear, _linear, _mm, _splitk_wgrad, attention_any_dim  # noqa: F401  (dense-layer functions live in nn.py)
 
+# Head dims the encoder runs on attention kernels of their own, with the fused QKV buffer, the packed pass, the bucketed
+# layout and the recorded encoder / whole step (32: attn_d32.hip; 64 / 96: attn_kernels.hip and its siblings).  Every gate
+# reads this tuple at call time; any other head dim takes the padded pass through ``attention_any_dim`` (zero-padded heads).
+# Set back to (64, 96), a d = 32 encoder takes that route again, bit for bit.
+NATIVE_HEAD_DIMS = (32, 64, 96)
+
 
 def check_supported(plm) -> None:
     cfg = plm.config
@@ -119,7 +125,7 @@ def _layer(lw, h, lens, heads, training, p_hidden, p_attn, eps, cu=None, max_len
     pdim = h.shape[-1]
     d = pdim // heads
     scale = d ** -0.5
-    if d in (64, 96):
+    if d in NATIVE_HEAD_DIMS:
         # the fused projection adds the Q|K|V biases; their GRADIENT (the column sums of dqkv) is returned by the attention
         # operator, which can form it inside its backward kernel (ops.AttentionQKV): an explicit autograd edge
         # bias master -> attention op, no side channel between the two backward functions
@@ -174,15 +180,14 @@ def bert_encode_packed(plm, token_ids: torch.Tensor, pos_ids: torch.Tensor, cu_s
     ``groups``: optional ``ops.pack_sequence_groups`` boundaries (device int32) for the short-sequence attention kernels."""
     cfg = plm.config
     emb = plm.embeddings
+    heads = cfg.num_attention_heads
+    if cfg.hidden_size // heads not in NATIVE_HEAD_DIMS:
+        raise NotImplementedError("packed encoder pass needs head dim 32, 64 or 96 (use the padded path otherwise)")
     # word + type-0 + position rows in one pass (fp32 sums in torch's order, stored as cd); backward = segment sums by id
     x = ops.embed_sum(token_ids, pos_ids, emb.word_embeddings.weight, emb.position_embeddings.weight,
                       emb.token_type_embeddings.weight, cd)
     eps, p_hidden, p_attn = cfg.layer_norm_eps, cfg.hidden_dropout_prob, cfg.attention_probs_dropout_prob
     h = ops.bias_res_layernorm(x, None, None, emb.LayerNorm.weight, emb.LayerNorm.bias, eps, False, p_hidden, training)
-    heads = cfg.num_attention_heads
-    d = cfg.hidden_size // heads
-    if d not in (64, 96):
-        raise NotImplementedError("packed encoder pass needs head dim 64 or 96 (use the padded path otherwise)")
     if weights is None:
         weights = prepare_weights(plm, cd)
     for lw in weights:

@@ -164,7 +164,7 @@ class GraphTextLM(nn.Module):
         # pad every packed text batch to the static sizes of ``bucketed_layout`` (what a captured encoder replays; set it on an
         # eager model to run the very same padded batch without hipGraphs)
         self.plm_bucketed = False
-        # variable-length token packing in the text encoder (head dim 64 / 96)
+        # variable-length token packing in the text encoder (head dim 32 / 64 / 96)
         self.active_index = None   # set by encode_texts: ascending device index of the active nodes of the last call
         self._graphs = GraphCache(capacity=4)
         self._tokens = {}
@@ -204,9 +204,9 @@ class GraphTextLM(nn.Module):
         return cfg.hidden_size // cfg.num_attention_heads if self._enc is bert else 0
 
     def _has_packed_pass(self) -> bool:
-        """The encoder can run all active nodes as one variable-length packed batch: BERT geometry at head dim 64 / 96
-        (``bert.bert_encode_packed``) and Qwen3 (``qwen3.qwen3_encode_packed``, head dim 128)."""
-        return self._enc is qwen3 or self._packed_head_dim() in (64, 96)
+        """The encoder can run all active nodes as one variable-length packed batch: BERT geometry at a native head dim
+        (``bert.NATIVE_HEAD_DIMS``: 32 / 64 / 96, ``bert.bert_encode_packed``) and Qwen3 (``qwen3.qwen3_encode_packed``, head dim 128)."""
+        return self._enc is qwen3 or self._packed_head_dim() in bert.NATIVE_HEAD_DIMS
 
     def graph(self, edge_index: torch.Tensor, num_nodes: int, edge_type=None) -> RelCSR:
         if self.dist is not None:
@@ -394,7 +394,7 @@ class GraphTextLM(nn.Module):
         grad = self.plm_encoder.training or self.training
         heads = self.plm_encoder.config.num_attention_heads
         packed = self._has_packed_pass() and self.plm_packed
-        static_ok = self._packed_head_dim() in (64, 96)                      # bucketed layout / recorded encoder: BERT geometry only
+        static_ok = self._packed_head_dim() in bert.NATIVE_HEAD_DIMS         # bucketed layout / recorded encoder: BERT geometry only
         plm_batch_size = max(1, min(int(plm_batch_size), 65535 // heads))   # attention grids index (sequence, head) in 16 bits
         with torch.set_grad_enabled(grad and torch.is_grad_enabled()):
             # cast / fuse once, share across micro-batches (forward() has done it ahead of the GNN launches)
@@ -504,7 +504,7 @@ class GraphTextLM(nn.Module):
             heads = self.plm_encoder.config.num_attention_heads
             a = seen["idx_h"].numel()
             if (0 < a <= max(1, min(int(plm_batch_size), 65535 // heads)) and self.plm_packed
-                    and self._packed_head_dim() in (64, 96)):
+                    and self._packed_head_dim() in bert.NATIVE_HEAD_DIMS):
                 if seen["active_index"] is None:
                     seen["active_index"] = seen["idx_h"].pin_memory().to(gnn_input_features.device, non_blocking=True)
                 self.active_index = seen["active_index"]

@@ -620,6 +620,10 @@ class Attention(torch.autograd.Function):
                 check(lib().gmlm_attention_d128_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(kv_len), b, h, lq, lk, d, qs, ks, vs, float(scale),
                                                     float(p), seed, sd, _ptr(out), _ptr(out_lo), _ptr(lse), _dt(q), _stream()),
                       "gmlm_attention_d128_fwd")
+            elif d == 32:     # its own entry point (attn_d32.hip): no bound on b * h, workgroup height from max(lq, lk)
+                check(lib().gmlm_attention_d32_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(kv_len), b, h, lq, lk, d, qs, ks, vs, float(scale),
+                                                   float(p), seed, sd, _ptr(out), _ptr(out_lo), _ptr(lse), _dt(q), None, 0, _stream()),
+                      "gmlm_attention_d32_fwd")
             else:
                 check(lib().gmlm_attention_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(kv_len), b, h, lq, lk, d, qs, ks, vs, float(scale),
                                                float(p), seed, sd, _ptr(out), _ptr(out_lo), _ptr(lse), _dt(q), None, 0, None, 0,
@@ -642,6 +646,7 @@ class Attention(torch.autograd.Function):
         dk = torch.empty(b, lk, hd, dtype=q.dtype, device=q.device)
         dv = torch.empty(b, lk, hd, dtype=q.dtype, device=q.device)
         ws = _ws(lib().gmlm_attention_d128_workspace_bytes(b, h, lq) if d == 128 else
+                 lib().gmlm_attention_d32_bwd_workspace_bytes(b, h, lq) if d == 32 else
                  lib().gmlm_attention_bwd_workspace_bytes(b, h, lq, lk, d), q.device)
         with _span("attn_bwd_d%d" % d, flops=10.0 * b * h * lq * lk * d):
             sd = ctx.sd
@@ -651,6 +656,12 @@ class Attention(torch.autograd.Function):
                                                     seed, sd, _ptr(dq), _ptr(dk), _ptr(dv), hd, hd, hd, _dt(q), _ptr(ws), ws.numel(),
                                                     _stream()),
                       "gmlm_attention_d128_bwd")
+            elif d == 32:
+                check(lib().gmlm_attention_d32_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(gout), _ptr(lse), _ptr(kv_len), b, h,
+                                                   lq, lk, d, q.stride(1), k.stride(1), v.stride(1), scale, p, seed, sd, _ptr(dq),
+                                                   _ptr(dk), _ptr(dv), hd, hd, hd, _dt(q), None, 0, _ptr(ws), ws.numel(),
+                                                   _ptr(out_lo), _stream()),
+                      "gmlm_attention_d32_bwd")
             else:
                 check(lib().gmlm_attention_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(gout), _ptr(lse), _ptr(kv_len), b, h,
                                                lq, lk, d, q.stride(1), k.stride(1), v.stride(1), scale, p, seed, sd, _ptr(dq),
@@ -701,9 +712,14 @@ class AttentionQKV(torch.autograd.Function):
         nb = out.numel() * out.element_size()                   # one of q, k, v, o
         with _span("attn_fwd_d%d" % d, flops=flops, bytes=(4 + (1 if out_lo is not None else 0)) * nb):
             sd = ctx.sd = _sd()
-            check(lib().gmlm_attention_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(kv_len), b, h, l, l, d, hd3, hd3, hd3, float(scale),
-                                           float(p), seed, sd, _ptr(out), _ptr(out_lo), _ptr(lse), _dt(qkv), _ptr(cu_seqlens),
-                                           int(max_len), _ptr(groups), n_groups, _stream()), "gmlm_attention_fwd")
+            if d == 32:       # attn_d32.hip: padded and packed, no short-sequence kernels (groups was dropped above)
+                check(lib().gmlm_attention_d32_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(kv_len), b, h, l, l, d, hd3, hd3, hd3,
+                                                   float(scale), float(p), seed, sd, _ptr(out), _ptr(out_lo), _ptr(lse), _dt(qkv),
+                                                   _ptr(cu_seqlens), int(max_len), _stream()), "gmlm_attention_d32_fwd")
+            else:
+                check(lib().gmlm_attention_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(kv_len), b, h, l, l, d, hd3, hd3, hd3, float(scale),
+                                               float(p), seed, sd, _ptr(out), _ptr(out_lo), _ptr(lse), _dt(qkv), _ptr(cu_seqlens),
+                                               int(max_len), _ptr(groups), n_groups, _stream()), "gmlm_attention_fwd")
         if short:
             ctx.save_for_backward(qkv, lse, kv_len, cu_seqlens, groups)        # the fused backward never reads the forward output
         else:
@@ -729,7 +745,9 @@ class AttentionQKV(torch.autograd.Function):
         q, k, v = qkv[..., :hd], qkv[..., hd:2 * hd], qkv[..., 2 * hd:]
         dqkv = torch.empty_like(qkv)
         dq, dk, dv = dqkv[..., :hd], dqkv[..., hd:2 * hd], dqkv[..., 2 * hd:]
-        ws = _ws(lib().gmlm_attention_bwd_workspace_bytes(1 if cu_seqlens is not None else b, h, l, l, d), qkv.device)
+        nb = 1 if cu_seqlens is not None else b
+        ws = _ws(lib().gmlm_attention_d32_bwd_workspace_bytes(nb, h, l) if d == 32 else
+                 lib().gmlm_attention_bwd_workspace_bytes(nb, h, l, l, d), qkv.device)
         # short-sequence path (one launch per (sequence, head): same condition as the C entry): the column sums of dqkv --
         # the bias gradient of the fused QKV projection that produced qkv -- come out of the kernel as well
         rows = max_len if cu_seqlens is not None else l
@@ -742,11 +760,18 @@ class AttentionQKV(torch.autograd.Function):
         # q, k, v, dO in; dq, dk, dv out (+ o, o_lo on the streaming path, which forms delta from them)
         with _span("attn_bwd_d%d" % d, flops=2.5 * flops, bytes=(7 + (0 if ctx.short else 2)) * qkv.numel() // 3 * qkv.element_size()):
             sd = ctx.sd
-            check(lib().gmlm_attention_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(gout), _ptr(lse), _ptr(kv_len), b, h,
-                                           l, l, d, hd3, hd3, hd3, scale, p, seed, sd, _ptr(dq), _ptr(dk), _ptr(dv), hd3, hd3,
-                                           hd3, _dt(qkv), _ptr(cu_seqlens), max_len, _ptr(ws), ws.numel(), _ptr(part), _ptr(db),
-                                           _ptr(out_lo), _ptr(groups), n_groups, _stream()),
-                  "gmlm_attention_bwd")
+            if d == 32:
+                check(lib().gmlm_attention_d32_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(gout), _ptr(lse), _ptr(kv_len), b, h,
+                                                   l, l, d, hd3, hd3, hd3, scale, p, seed, sd, _ptr(dq), _ptr(dk), _ptr(dv), hd3,
+                                                   hd3, hd3, _dt(qkv), _ptr(cu_seqlens), max_len, _ptr(ws), ws.numel(),
+                                                   _ptr(out_lo), _stream()),
+                      "gmlm_attention_d32_bwd")
+            else:
+                check(lib().gmlm_attention_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(gout), _ptr(lse), _ptr(kv_len), b, h,
+                                               l, l, d, hd3, hd3, hd3, scale, p, seed, sd, _ptr(dq), _ptr(dk), _ptr(dv), hd3, hd3,
+                                               hd3, _dt(qkv), _ptr(cu_seqlens), max_len, _ptr(ws), ws.numel(), _ptr(part), _ptr(db),
+                                               _ptr(out_lo), _ptr(groups), n_groups, _stream()),
+                      "gmlm_attention_bwd")
         dbs = ()
         if want_db:
             if db is None:

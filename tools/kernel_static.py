@@ -9,6 +9,7 @@ the code objects' metadata and disassembly.
 has, listed with their figures.  Exit status 1 when a matched kernel differs or is missing.
 """
 import argparse
+import hashlib
 import json
 import os
 import re
@@ -79,6 +80,7 @@ def main():
     ap.add_argument("--match", required=True)
     ap.add_argument("--added", default=None)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--compact", action="store_true", help="one short line per kernel (unchanged kernels: name and figures once)")
     a = ap.parse_args()
     old, new = kernels(a.parent), kernels(a.new)
     keys = ("symbol", "vgpr", "lds_bytes", "scratch_bytes", "v_mfma", "scratch_instr", "packed_f32", "instructions")
@@ -95,6 +97,24 @@ def main():
                     "object metadata reports it, instructions / v_mfma / scratch_instr / packed_f32 counted in the disassembly",
                match=a.match, compared=len(rows), unchanged=len(rows) - bad, existing=rows, added=added)
     text = json.dumps(res, indent=1)
+    if a.compact:
+        # one line per kernel: [name without its parameter list, figures in the order of "columns"]; a changed kernel keeps its full row
+        def bare(name):
+            depth = 0
+            for i, c in enumerate(name):
+                depth += (c == "<") - (c == ">")
+                if c == "(" and depth == 0:
+                    name = name[:i]
+                    break
+            # library templates (rocprim) run to a kilobyte: keep the head and a hash of the whole name
+            return name if len(name) <= 120 else name[:96] + "...#" + hashlib.sha1(name.encode()).hexdigest()[:10]
+        flat = [[bare(r["kernel"])] + [r["parent"][k] for k in keys[1:]] if r["unchanged"] else r for r in rows]
+        extra = [k for k in (added[0] if added else {}) if k != "kernel" and k not in keys]
+        new_rows = [[bare(d["kernel"])] + [d[k] for k in list(keys[1:]) + extra] for d in added]
+        head = dict(what=res["what"], match=a.match, compared=len(rows), unchanged=len(rows) - bad,
+                    columns=["kernel"] + list(keys[1:]), added_columns=["kernel"] + list(keys[1:]) + extra)
+        lines = lambda xs: ",\n".join("  " + json.dumps(x) for x in xs)
+        text = json.dumps(head)[:-1] + ',\n "existing": [\n' + lines(flat) + '\n ],\n "added": [\n' + lines(new_rows) + "\n ]}"
     if a.out:
         with open(a.out, "w") as f:
             f.write(text + "\n")
