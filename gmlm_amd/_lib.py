@@ -1,4 +1,5 @@
-"""ctypes binding of libgmlm_hip.so (C ABI: include/gmlm_hip.h, gmlm_hip_split.h, gmlm_hip_optim.h and gmlm_hip_d32.h).
+"""ctypes binding of libgmlm_hip.so (C ABI: include/gmlm_hip.h, gmlm_hip_split.h, gmlm_hip_optim.h, gmlm_hip_d32.h and
+gmlm_hip_wide.h).
 
 The product path has NO fallback: if the shared library is missing or a call fails, a Python
 exception is raised.  Build with ``python -c "import __graft_entry__ as g; g.build()"`` or
@@ -114,6 +115,20 @@ SIGNATURES_D32 = {
                                          _f32, _u64, _p, _p, _p, _p, _i64, _i64, _i64, _i32, _p, _i64, _p, _sz, _p, _p]),
 }
 
+# fifth header, include/gmlm_hip_wide.h (encoders wider than 1,024: attention at head dims 256 / 384 / 512, LayerNorm rows to 4,096)
+SIGNATURES_WIDE = {
+    "gmlm_attention_wide_fwd": (C.c_int, [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _f32, _u64, _p,
+                                          _p, _p, _p, _i32, _p]),
+    "gmlm_attention_wide_bwd_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "gmlm_attention_wide_bwd": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32,
+                                          _f32, _u64, _p, _p, _p, _p, _i64, _i64, _i64, _i32, _p, _sz, _p]),
+    "gmlm_bias_res_layernorm_wide_fwd": (C.c_int, [_p, _p, _p, _p, _p, _i64, _i64, _f32, _i32, _f32, _u64, _p, _p, _p, _p, _i32,
+                                                   _p]),
+    "gmlm_bias_res_layernorm_wide_bwd_workspace_bytes": (_sz, [_i64, _i64]),
+    "gmlm_bias_res_layernorm_wide_bwd": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i32, _f32, _u64, _p, _p, _p, _p,
+                                                   _p, _p, _i32, _p, _sz, _p]),
+}
+
 
 class GmlmHipError(RuntimeError):
     pass
@@ -133,7 +148,7 @@ def lib() -> C.CDLL:
             "(or __graft_entry__.build()). gmlm_amd has no CPU / eager fallback.")
     handle = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_SPLIT.items()) + list(SIGNATURES_OPTIM.items()) + \
-            list(SIGNATURES_D32.items()):
+            list(SIGNATURES_D32.items()) + list(SIGNATURES_WIDE.items()):
         fn = getattr(handle, name)  # AttributeError here = header / library mismatch
         fn.restype, fn.argtypes = res, args
     if handle.gmlm_version() != 1:

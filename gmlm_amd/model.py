@@ -572,6 +572,9 @@ class GraphTextLM(nn.Module):
         if self._enc is not bert and encoder:
             raise NotImplementedError("hipGraph capture of the text encoder covers BERT-geometry encoders only; pass encoder=False "
                                       "to record the GNN and head regions around an eager Qwen3 encoder")
+        if self.plm_encoder.config.hidden_size > 1024:
+            raise NotImplementedError("hipGraph capture is not verified for a text encoder wider than 1024 (wide-head attention and wide "
+                                      "LayerNorm kernels, gmlm_hip_wide.h): run this model eagerly")
         return graphs.capture(self, gnn_input_sample, edge_index, encoder=encoder, whole_step=whole_step, concurrent=concurrent)
 
     def release_hip_graphs(self):

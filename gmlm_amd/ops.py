@@ -529,6 +529,10 @@ class GraphNormAct(torch.autograd.Function):
 # ---------------------------------------------------------------------------------------------
 # K6: bias + dropout + residual + LayerNorm (+GELU)
 # ---------------------------------------------------------------------------------------------
+LN_WIDE_ABOVE = 1024            # widest row of gmlm_bias_res_layernorm_*; wider rows (to 4,096) go to gmlm_bias_res_layernorm_wide_*
+ATTN_WIDE_DIMS = (256, 384, 512)   # head dims of gmlm_attention_wide_* (attn_wide.hip)
+
+
 class BiasResLayerNorm(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, bias, residual, gamma, beta, eps, act, p, seed):
@@ -544,9 +548,10 @@ class BiasResLayerNorm(torch.autograd.Function):
         mean = torch.empty(rows, dtype=torch.float32, device=x.device)
         rstd = torch.empty_like(mean)
         sd = ctx.sd = _sd()
-        check(lib().gmlm_bias_res_layernorm_fwd(_ptr(x2), _ptr(bf), _ptr(res2), _ptr(g), _ptr(b), rows, f, float(eps),
-                                                int(act), float(p), seed, sd, _ptr(y), _ptr(mean), _ptr(rstd), _dt(x2), _stream()),
-              "gmlm_bias_res_layernorm_fwd")
+        # rows wider than 1,024 have their own entry points (norm_wide.hip: one workgroup per row), same arguments
+        name = "gmlm_bias_res_layernorm_wide_fwd" if f > LN_WIDE_ABOVE else "gmlm_bias_res_layernorm_fwd"
+        check(getattr(lib(), name)(_ptr(x2), _ptr(bf), _ptr(res2), _ptr(g), _ptr(b), rows, f, float(eps),
+                                   int(act), float(p), seed, sd, _ptr(y), _ptr(mean), _ptr(rstd), _dt(x2), _stream()), name)
         ctx.save_for_backward(x2, res2, bf, g, b, mean, rstd)
         ctx.cfg = (int(act), float(p), seed, shape, bias is not None, residual is not None)
         return y.view(shape)
@@ -562,12 +567,14 @@ class BiasResLayerNorm(torch.autograd.Function):
         dg = torch.empty(f, dtype=torch.float32, device=x2.device)
         dbeta = torch.empty_like(dg)
         dbias = torch.empty_like(dg) if has_bias else None
-        ws = _ws(lib().gmlm_layernorm_bwd_workspace_bytes(rows, f), x2.device)
+        wide = f > LN_WIDE_ABOVE
+        ws = _ws(lib().gmlm_bias_res_layernorm_wide_bwd_workspace_bytes(rows, f) if wide else
+                 lib().gmlm_layernorm_bwd_workspace_bytes(rows, f), x2.device)
         sd = ctx.sd
-        check(lib().gmlm_bias_res_layernorm_bwd(_ptr(gy2), _ptr(x2), _ptr(bf), _ptr(res2), _ptr(g), _ptr(b), _ptr(mean),
-                                                _ptr(rstd), rows, f, act, p, seed, sd, _ptr(dx), _ptr(dres), _ptr(dg),
-                                                _ptr(dbeta), _ptr(dbias), _dt(x2), _ptr(ws), ws.numel(), _stream()),
-              "gmlm_bias_res_layernorm_bwd")
+        name = "gmlm_bias_res_layernorm_wide_bwd" if wide else "gmlm_bias_res_layernorm_bwd"
+        check(getattr(lib(), name)(_ptr(gy2), _ptr(x2), _ptr(bf), _ptr(res2), _ptr(g), _ptr(b), _ptr(mean),
+                                   _ptr(rstd), rows, f, act, p, seed, sd, _ptr(dx), _ptr(dres), _ptr(dg),
+                                   _ptr(dbeta), _ptr(dbias), _dt(x2), _ptr(ws), ws.numel(), _stream()), name)
         return (dx.view(shape), dbias, None if dres is None else dres.view(shape), dg, dbeta, None, None, None, None)
 
 
@@ -624,6 +631,10 @@ class Attention(torch.autograd.Function):
                 check(lib().gmlm_attention_d32_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(kv_len), b, h, lq, lk, d, qs, ks, vs, float(scale),
                                                    float(p), seed, sd, _ptr(out), _ptr(out_lo), _ptr(lse), _dt(q), None, 0, _stream()),
                       "gmlm_attention_d32_fwd")
+            elif d in ATTN_WIDE_DIMS:   # attn_wide.hip: the head dim split over the four waves of a workgroup, padded layout only
+                check(lib().gmlm_attention_wide_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(kv_len), b, h, lq, lk, d, qs, ks, vs, float(scale),
+                                                    float(p), seed, sd, _ptr(out), _ptr(out_lo), _ptr(lse), _dt(q), _stream()),
+                      "gmlm_attention_wide_fwd")
             else:
                 check(lib().gmlm_attention_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(kv_len), b, h, lq, lk, d, qs, ks, vs, float(scale),
                                                float(p), seed, sd, _ptr(out), _ptr(out_lo), _ptr(lse), _dt(q), None, 0, None, 0,
@@ -647,6 +658,7 @@ class Attention(torch.autograd.Function):
         dv = torch.empty(b, lk, hd, dtype=q.dtype, device=q.device)
         ws = _ws(lib().gmlm_attention_d128_workspace_bytes(b, h, lq) if d == 128 else
                  lib().gmlm_attention_d32_bwd_workspace_bytes(b, h, lq) if d == 32 else
+                 lib().gmlm_attention_wide_bwd_workspace_bytes(b, h, lq) if d in ATTN_WIDE_DIMS else
                  lib().gmlm_attention_bwd_workspace_bytes(b, h, lq, lk, d), q.device)
         with _span("attn_bwd_d%d" % d, flops=10.0 * b * h * lq * lk * d):
             sd = ctx.sd
@@ -662,6 +674,12 @@ class Attention(torch.autograd.Function):
                                                    _ptr(dk), _ptr(dv), hd, hd, hd, _dt(q), None, 0, _ptr(ws), ws.numel(),
                                                    _ptr(out_lo), _stream()),
                       "gmlm_attention_d32_bwd")
+            elif d in ATTN_WIDE_DIMS:
+                check(lib().gmlm_attention_wide_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(out_lo), _ptr(gout), _ptr(lse),
+                                                    _ptr(kv_len), b, h, lq, lk, d, q.stride(1), k.stride(1), v.stride(1), scale, p,
+                                                    seed, sd, _ptr(dq), _ptr(dk), _ptr(dv), hd, hd, hd, _dt(q), _ptr(ws), ws.numel(),
+                                                    _stream()),
+                      "gmlm_attention_wide_bwd")
             else:
                 check(lib().gmlm_attention_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(gout), _ptr(lse), _ptr(kv_len), b, h,
                                                lq, lk, d, q.stride(1), k.stride(1), v.stride(1), scale, p, seed, sd, _ptr(dq),
@@ -790,9 +808,12 @@ class AttentionBlock:
         self.h, self.scale, self.p = num_heads, float(scale), float(dropout_p)
 
     def fwd(self, q, k, v, kv_len, seed):
-        _cuda(q, k, v)
         b, lq, hd = q.shape
         lk, d = k.shape[1], hd // self.h
+        if d > 128:
+            raise NotImplementedError(f"ring attention has no block form at head dim {d}: the wide-head kernels "
+                                      "(gmlm_attention_wide_*) run on one GPU only")
+        _cuda(q, k, v)
         if d not in (64, 96):
             raise NotImplementedError(f"ring attention needs a native head dim (64 or 96), got {d}: the head-dim-128 kernels "
                                       "(gmlm_attention_d128_*) have no ring-block form")

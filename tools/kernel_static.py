@@ -5,7 +5,8 @@ the code objects' metadata and disassembly.
     python tools/kernel_static.py --parent PARENT/libgmlm_hip.so --new gmlm_amd/libgmlm_hip.so \
         --match 'attn_|d128::' --added 'causal128::|rmsnorm_|qknorm_rope_|swiglu_' --out profiles/attn_causal_static.json
 
-``--match``: kernels (demangled name, regex) that must be the same in both builds; ``--added``: kernels only the new build
+``--dynamic-lds 'REGEX=BYTES'`` (repeatable) records the dynamic LDS the host adds at launch for kernels whose static
+``lds_bytes`` is not the whole picture.  ``--match``: kernels (demangled name, regex) that must be the same in both builds; ``--added``: kernels only the new build
 has, listed with their figures.  Exit status 1 when a matched kernel differs or is missing.
 """
 import argparse
@@ -80,6 +81,9 @@ def main():
     ap.add_argument("--match", required=True)
     ap.add_argument("--added", default=None)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--dynamic-lds", action="append", default=[], metavar="REGEX=BYTES",
+                    help="dynamic LDS the host requests at launch for the kernels matching REGEX (lds_bytes is the static part only); "
+                         "recorded as given")
     ap.add_argument("--compact", action="store_true", help="one short line per kernel (unchanged kernels: name and figures once)")
     a = ap.parse_args()
     old, new = kernels(a.parent), kernels(a.new)
@@ -96,6 +100,9 @@ def main():
     res = dict(what="per-kernel static figures of two builds of libgmlm_hip.so (same flags): vgpr = .vgpr_count + AGPRs as the code "
                     "object metadata reports it, instructions / v_mfma / scratch_instr / packed_f32 counted in the disassembly",
                match=a.match, compared=len(rows), unchanged=len(rows) - bad, existing=rows, added=added)
+    dyn = {k: int(v) for k, v in (x.rsplit("=", 1) for x in a.dynamic_lds)}
+    if dyn:
+        res["dynamic_lds_bytes"] = dyn
     text = json.dumps(res, indent=1)
     if a.compact:
         # one line per kernel: [name without its parameter list, figures in the order of "columns"]; a changed kernel keeps its full row
@@ -113,6 +120,8 @@ def main():
         new_rows = [[bare(d["kernel"])] + [d[k] for k in list(keys[1:]) + extra] for d in added]
         head = dict(what=res["what"], match=a.match, compared=len(rows), unchanged=len(rows) - bad,
                     columns=["kernel"] + list(keys[1:]), added_columns=["kernel"] + list(keys[1:]) + extra)
+        if dyn:
+            head["dynamic_lds_bytes"] = dyn
         lines = lambda xs: ",\n".join("  " + json.dumps(x) for x in xs)
         text = json.dumps(head)[:-1] + ',\n "existing": [\n' + lines(flat) + '\n ],\n "added": [\n' + lines(new_rows) + "\n ]}"
     if a.out:
