@@ -1,5 +1,6 @@
 """ctypes binding of libgmlm_hip.so (C ABI: include/gmlm_hip.h, gmlm_hip_split.h, gmlm_hip_optim.h, gmlm_hip_d32.h and
-gmlm_hip_wide.h).
+gmlm_hip_wide.h): one signature table per header, positional argument types only.  Which attention entry point a head dim
+takes, and where each ABI puts its arguments by name, is the family table of ops.py (``_ATTN_FAMILIES``).
 
 The product path has NO fallback: if the shared library is missing or a call fails, a Python
 exception is raised.  Build with ``python -c "import __graft_entry__ as g; g.build()"`` or
@@ -129,6 +130,8 @@ SIGNATURES_WIDE = {
                                                    _p, _p, _i32, _p, _sz, _p]),
 }
 
+SIGNATURE_TABLES = (SIGNATURES, SIGNATURES_SPLIT, SIGNATURES_OPTIM, SIGNATURES_D32, SIGNATURES_WIDE)   # one per header, all bound by lib()
+
 
 class GmlmHipError(RuntimeError):
     pass
@@ -147,10 +150,10 @@ def lib() -> C.CDLL:
             f"{LIB_PATH} not found: the HIP extension is not built. Run `make -C gmlm_amd/csrc` "
             "(or __graft_entry__.build()). gmlm_amd has no CPU / eager fallback.")
     handle = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_SPLIT.items()) + list(SIGNATURES_OPTIM.items()) + \
-            list(SIGNATURES_D32.items()) + list(SIGNATURES_WIDE.items()):
-        fn = getattr(handle, name)  # AttributeError here = header / library mismatch
-        fn.restype, fn.argtypes = res, args
+    for table in SIGNATURE_TABLES:
+        for name, (res, args) in table.items():
+            fn = getattr(handle, name)  # AttributeError here = header / library mismatch
+            fn.restype, fn.argtypes = res, args
     if handle.gmlm_version() != 1:
         raise GmlmHipError(f"ABI version mismatch: library {handle.gmlm_version()} != binding 1")
     _lib = handle

@@ -17,7 +17,9 @@
 //    causal mask is not rank-1, so diagonal tiles select P = 0 explicitly before dS;
 //  * dK/dV: a workgroup owns 128 keys of one KV head, walks the query heads of its group in order and, per head, the query
 //    tiles from the diagonal on, accumulating into the same registers.  No atomics, no expanded K / V or dK / dV in HBM.
+// The argument checks and the AttnParams filling shared with the other attention entry points are in attn_host.hpp.
 #include "attn_stream.hpp"
+#include "attn_host.hpp"
 
 namespace gmlm {
 namespace causal128 {
@@ -252,17 +254,17 @@ __global__ __launch_bounds__(NT) void dkv_kernel(Params x) {
   }
 }
 
-// host checks shared by the forward and the backward; fills the launch parameters
+// the checks of attn_host.hpp up to the empty-problem return, with this family's head dim, layout rules and work-item bound;
+// fills the launch parameters.  sizes_ok: what the entry point adds to the size test (the varlen entries' own bounds)
 static int setup(const char* who, Params& x, const void* q, const void* k, const void* v, const int32_t* kv_len, int64_t b,
                  int64_t hq, int64_t hkv, int64_t lq, int64_t lk, int64_t d, int64_t q_stride, int64_t k_stride, int64_t v_stride,
-                 float scale, float dropout_p, int dtype) {
-  GMLM_REQUIRE(d == 128, "%s: head dim %ld not supported (this entry point takes 128)", who, (long)d);
-  GMLM_REQUIRE(b >= 0 && hq > 0 && hkv > 0 && lq >= 0 && lk >= 0, "%s: bad sizes", who);
+                 float scale, float dropout_p, const void* out_lo, int dtype, bool sizes_ok = true) {
+  int rc = attn_check_shape(who, sizes_ok && b >= 0 && hq > 0 && hkv > 0 && lq >= 0 && lk >= 0, d == 128, d, "this entry point takes 128",
+                            dtype, out_lo);
+  if (rc != GMLM_OK) return rc;
   GMLM_REQUIRE(lq == lk, "%s: causal self-attention needs lq == lk (got %ld and %ld)", who, (long)lq, (long)lk);
   GMLM_REQUIRE(hq % hkv == 0, "%s: %ld query heads are not a multiple of %ld KV heads", who, (long)hq, (long)hkv);
-  GMLM_REQUIRE(dtype == GMLM_F32 || dtype == GMLM_BF16, "%s: unsupported dtype", who);
-  GMLM_REQUIRE(dropout_p == 0.f, "%s: attention-probability dropout is not implemented for the causal kernels (dropout_p must be 0)", who);
-  GMLM_REQUIRE(scale > 0.f, "%s: scale must be positive", who);
+  if ((rc = attn_check_rates(who, dropout_p, false, scale)) != GMLM_OK) return rc;
   GMLM_REQUIRE(lq < ((int64_t)1 << 30) && cdiv(lq, BQ) * b * hq < ((int64_t)1 << 31), "%s: too many work items", who);
   x = Params{};
   attn_fill(x.a, q, k, v, kv_len, b, hq, lq, lk, q_stride, k_stride, v_stride, scale, 0.f, 0, nullptr);
@@ -276,12 +278,12 @@ static int setup(const char* who, Params& x, const void* q, const void* k, const
 // sequence returns block-uniformly.
 static int setup_varlen(const char* who, Params& x, const void* q, const void* k, const void* v, const int32_t* cu, int64_t seqs,
                         int64_t max_len, int64_t rows, int64_t hq, int64_t hkv, int64_t d, int64_t q_stride, int64_t k_stride,
-                        int64_t v_stride, float scale, float dropout_p, int dtype) {
+                        int64_t v_stride, float scale, float dropout_p, const void* out_lo, int dtype) {
   GMLM_REQUIRE(cu, "%s: null cu_seqlens", who);
   GMLM_REQUIRE(max_len > 0, "%s: max_len %ld must be positive", who, (long)max_len);
   GMLM_REQUIRE(seqs >= 0 && rows >= 0 && rows < ((int64_t)1 << 30), "%s: %ld packed rows (must be >= 0 and < 2^30)", who, (long)rows);
-  GMLM_REQUIRE(max_len < ((int64_t)1 << 30) && seqs < ((int64_t)1 << 30), "%s: bad sizes", who);
-  int rc = setup(who, x, q, k, v, nullptr, 0, hq, hkv, 0, 0, d, q_stride, k_stride, v_stride, scale, dropout_p, dtype);
+  int rc = setup(who, x, q, k, v, nullptr, 0, hq, hkv, 0, 0, d, q_stride, k_stride, v_stride, scale, dropout_p, out_lo, dtype,
+                 max_len < ((int64_t)1 << 30) && seqs < ((int64_t)1 << 30));
   if (rc != GMLM_OK) return rc;
   GMLM_REQUIRE(cdiv(max_len, BQ) * seqs * hq < ((int64_t)1 << 31), "%s: too many work items", who);
   x.a.b = seqs; x.a.lq = x.a.lk = rows; x.a.cu = cu;
@@ -306,15 +308,11 @@ extern "C" int gmlm_attention_causal_d128_fwd(const void* q, const void* k, cons
                                               void* out_lo, float* lse, int dtype, gmlm_stream_t stream) {
   static const char* who = "attention_causal_d128_fwd";
   Params x;
-  int rc = setup(who, x, q, k, v, kv_len, b, hq, hkv, lq, lk, d, q_stride, k_stride, v_stride, scale, dropout_p, dtype);
+  int rc = setup(who, x, q, k, v, kv_len, b, hq, hkv, lq, lk, d, q_stride, k_stride, v_stride, scale, dropout_p, out_lo, dtype);
   if (rc != GMLM_OK) return rc;
-  GMLM_REQUIRE(!out_lo || (dtype == GMLM_BF16 && aligned16(out_lo)), "%s: out_lo is the bf16 residual of a bf16 output (16-byte aligned)", who);
   if (b == 0 || lq == 0) return GMLM_OK;
-  if ((rc = attn_stride_check(who, "q", q, q_stride, hq * 128, dtype)) != GMLM_OK) return rc;
-  if ((rc = attn_stride_check(who, "k", k, k_stride, hkv * 128, dtype)) != GMLM_OK) return rc;
-  if ((rc = attn_stride_check(who, "v", v, v_stride, hkv * 128, dtype)) != GMLM_OK) return rc;
-  GMLM_REQUIRE(out && aligned16(out), "%s: null or misaligned out", who);
   x.a.o_w = out; x.a.o_lo_w = out_lo; x.a.lse_w = lse;
+  if ((rc = attn_check_fwd_operands(who, x.a, hq * D, hkv * D, dtype)) != GMLM_OK) return rc;
   hipStream_t st = as_stream(stream);
   const dim3 grid((unsigned)(cdiv(lq, BQ) * b * hq));
   GMLM_CAUSAL_LAUNCH(fwd_kernel, grid, st, x);
@@ -323,7 +321,7 @@ extern "C" int gmlm_attention_causal_d128_fwd(const void* q, const void* k, cons
 }
 
 extern "C" size_t gmlm_attention_causal_d128_workspace_bytes(int64_t b, int64_t hq, int64_t lq) {
-  return (size_t)(b * hq * lq > 0 ? b * hq * lq : 1) * sizeof(float);   // delta
+  return attn_delta_bytes(b, hq, lq);
 }
 
 extern "C" int gmlm_attention_causal_d128_bwd(const void* q, const void* k, const void* v, const void* out, const void* out_lo,
@@ -334,32 +332,15 @@ extern "C" int gmlm_attention_causal_d128_bwd(const void* q, const void* k, cons
                                               size_t workspace_bytes, gmlm_stream_t stream) {
   static const char* who = "attention_causal_d128_bwd";
   Params x;
-  int rc = setup(who, x, q, k, v, kv_len, b, hq, hkv, lq, lk, d, q_stride, k_stride, v_stride, scale, dropout_p, dtype);
+  int rc = setup(who, x, q, k, v, kv_len, b, hq, hkv, lq, lk, d, q_stride, k_stride, v_stride, scale, dropout_p, out_lo, dtype);
   if (rc != GMLM_OK) return rc;
-  GMLM_REQUIRE(!out_lo || (dtype == GMLM_BF16 && aligned16(out_lo)), "%s: out_lo is the bf16 residual of a bf16 output (16-byte aligned)", who);
   if (b == 0 || lq == 0) return GMLM_OK;
-  if ((rc = attn_stride_check(who, "q", q, q_stride, hq * 128, dtype)) != GMLM_OK) return rc;
-  if ((rc = attn_stride_check(who, "k", k, k_stride, hkv * 128, dtype)) != GMLM_OK) return rc;
-  if ((rc = attn_stride_check(who, "v", v, v_stride, hkv * 128, dtype)) != GMLM_OK) return rc;
-  if ((rc = attn_stride_check(who, "dq", dq, dq_stride, hq * 128, dtype)) != GMLM_OK) return rc;
-  if ((rc = attn_stride_check(who, "dk", dk, dk_stride, hkv * 128, dtype)) != GMLM_OK) return rc;
-  if ((rc = attn_stride_check(who, "dv", dv, dv_stride, hkv * 128, dtype)) != GMLM_OK) return rc;
-  GMLM_REQUIRE(out && dout && lse && aligned16(out) && aligned16(dout), "%s: null or misaligned out/dout/lse", who);
-  if (!workspace || workspace_bytes < gmlm_attention_causal_d128_workspace_bytes(b, hq, lq)) {
-    set_error("%s: workspace too small", who);
-    return GMLM_EWORKSPACE;
-  }
   AttnParams& p = x.a;
-  p.out = out; p.out_lo = out_lo; p.dout = dout; p.lse = lse;
-  p.delta = static_cast<float*>(workspace);
-  p.dq = dq; p.dk = dk; p.dv = dv;
-  p.dq_stride = dq_stride; p.dk_stride = dk_stride; p.dv_stride = dv_stride;
+  attn_fill_bwd(p, out, out_lo, dout, lse, dq, dk, dv, dq_stride, dk_stride, dv_stride, workspace);
+  if ((rc = attn_check_bwd_operands(who, p, hq * D, hkv * D, dtype, workspace_bytes, attn_delta_bytes(b, hq, lq))) != GMLM_OK) return rc;
   hipStream_t st = as_stream(stream);
   const int64_t rows = b * lq * hq;
-  if (dtype == GMLM_BF16)
-    delta_kernel<bf16_t><<<(unsigned)cdiv(rows * 16, 256), 256, 0, st>>>((const bf16_t*)out, (const bf16_t*)out_lo, (const bf16_t*)dout, rows, lq, hq, p.delta);
-  else
-    delta_kernel<float><<<(unsigned)cdiv(rows * 32, 256), 256, 0, st>>>((const float*)out, nullptr, (const float*)dout, rows, lq, hq, p.delta);
+  GMLM_ATTN_DELTA_LAUNCH(delta_kernel, p, rows, dtype == GMLM_BF16 ? 16 : 32, st, lq, hq);
   GMLM_LAUNCH_CHECK();
   const dim3 gq((unsigned)(cdiv(lq, BQ) * b * hq));
   GMLM_CAUSAL_LAUNCH(dq_kernel, gq, st, x);
@@ -378,15 +359,11 @@ extern "C" int gmlm_attention_causal_d128_varlen_fwd(const void* q, const void* 
   static const char* who = "attention_causal_d128_varlen_fwd";
   Params x;
   int rc = setup_varlen(who, x, q, k, v, cu_seqlens, num_seqs, max_len, total_rows, hq, hkv, d, q_stride, k_stride, v_stride, scale,
-                        dropout_p, dtype);
+                        dropout_p, out_lo, dtype);
   if (rc != GMLM_OK) return rc;
-  GMLM_REQUIRE(!out_lo || (dtype == GMLM_BF16 && aligned16(out_lo)), "%s: out_lo is the bf16 residual of a bf16 output (16-byte aligned)", who);
   if (num_seqs == 0 || total_rows == 0) return GMLM_OK;
-  if ((rc = attn_stride_check(who, "q", q, q_stride, hq * 128, dtype)) != GMLM_OK) return rc;
-  if ((rc = attn_stride_check(who, "k", k, k_stride, hkv * 128, dtype)) != GMLM_OK) return rc;
-  if ((rc = attn_stride_check(who, "v", v, v_stride, hkv * 128, dtype)) != GMLM_OK) return rc;
-  GMLM_REQUIRE(out && aligned16(out), "%s: null or misaligned out", who);
   x.a.o_w = out; x.a.o_lo_w = out_lo; x.a.lse_w = lse;
+  if ((rc = attn_check_fwd_operands(who, x.a, hq * D, hkv * D, dtype)) != GMLM_OK) return rc;
   hipStream_t st = as_stream(stream);
   const dim3 grid((unsigned)(cdiv(max_len, BQ) * num_seqs * hq));
   GMLM_CAUSAL_LAUNCH(fwd_kernel, grid, st, x);
@@ -395,7 +372,7 @@ extern "C" int gmlm_attention_causal_d128_varlen_fwd(const void* q, const void* 
 }
 
 extern "C" size_t gmlm_attention_causal_d128_varlen_workspace_bytes(int64_t total_rows, int64_t hq) {
-  return (size_t)(total_rows * hq > 0 ? total_rows * hq : 1) * sizeof(float);   // delta [hq, total_rows]
+  return attn_delta_bytes(1, hq, total_rows);   // delta [hq, total_rows]
 }
 
 extern "C" int gmlm_attention_causal_d128_varlen_bwd(const void* q, const void* k, const void* v, const void* out,
@@ -408,32 +385,15 @@ extern "C" int gmlm_attention_causal_d128_varlen_bwd(const void* q, const void* 
   static const char* who = "attention_causal_d128_varlen_bwd";
   Params x;
   int rc = setup_varlen(who, x, q, k, v, cu_seqlens, num_seqs, max_len, total_rows, hq, hkv, d, q_stride, k_stride, v_stride, scale,
-                        dropout_p, dtype);
+                        dropout_p, out_lo, dtype);
   if (rc != GMLM_OK) return rc;
-  GMLM_REQUIRE(!out_lo || (dtype == GMLM_BF16 && aligned16(out_lo)), "%s: out_lo is the bf16 residual of a bf16 output (16-byte aligned)", who);
   if (num_seqs == 0 || total_rows == 0) return GMLM_OK;
-  if ((rc = attn_stride_check(who, "q", q, q_stride, hq * 128, dtype)) != GMLM_OK) return rc;
-  if ((rc = attn_stride_check(who, "k", k, k_stride, hkv * 128, dtype)) != GMLM_OK) return rc;
-  if ((rc = attn_stride_check(who, "v", v, v_stride, hkv * 128, dtype)) != GMLM_OK) return rc;
-  if ((rc = attn_stride_check(who, "dq", dq, dq_stride, hq * 128, dtype)) != GMLM_OK) return rc;
-  if ((rc = attn_stride_check(who, "dk", dk, dk_stride, hkv * 128, dtype)) != GMLM_OK) return rc;
-  if ((rc = attn_stride_check(who, "dv", dv, dv_stride, hkv * 128, dtype)) != GMLM_OK) return rc;
-  GMLM_REQUIRE(out && dout && lse && aligned16(out) && aligned16(dout), "%s: null or misaligned out/dout/lse", who);
-  if (!workspace || workspace_bytes < gmlm_attention_causal_d128_varlen_workspace_bytes(total_rows, hq)) {
-    set_error("%s: workspace too small", who);
-    return GMLM_EWORKSPACE;
-  }
   AttnParams& p = x.a;
-  p.out = out; p.out_lo = out_lo; p.dout = dout; p.lse = lse;
-  p.delta = static_cast<float*>(workspace);
-  p.dq = dq; p.dk = dk; p.dv = dv;
-  p.dq_stride = dq_stride; p.dk_stride = dk_stride; p.dv_stride = dv_stride;
+  attn_fill_bwd(p, out, out_lo, dout, lse, dq, dk, dv, dq_stride, dk_stride, dv_stride, workspace);
+  if ((rc = attn_check_bwd_operands(who, p, hq * D, hkv * D, dtype, workspace_bytes, attn_delta_bytes(1, hq, total_rows))) != GMLM_OK) return rc;
   hipStream_t st = as_stream(stream);
   const int64_t rows = total_rows * hq;                         // delta as one sequence of total_rows: [hq, total_rows]
-  if (dtype == GMLM_BF16)
-    delta_kernel<bf16_t><<<(unsigned)cdiv(rows * 16, 256), 256, 0, st>>>((const bf16_t*)out, (const bf16_t*)out_lo, (const bf16_t*)dout, rows, total_rows, hq, p.delta);
-  else
-    delta_kernel<float><<<(unsigned)cdiv(rows * 32, 256), 256, 0, st>>>((const float*)out, nullptr, (const float*)dout, rows, total_rows, hq, p.delta);
+  GMLM_ATTN_DELTA_LAUNCH(delta_kernel, p, rows, dtype == GMLM_BF16 ? 16 : 32, st, total_rows, hq);
   GMLM_LAUNCH_CHECK();
   const dim3 gq((unsigned)(cdiv(max_len, BQ) * num_seqs * hq));
   GMLM_CAUSAL_LAUNCH(dq_kernel, gq, st, x);

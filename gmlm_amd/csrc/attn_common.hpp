@@ -1,5 +1,6 @@
 // Shared device helpers of the attention kernels (K5/K7): MFMA operand fragments, LDS staging, dropout hash.
-// Included by every attention translation unit; the streaming kernel bodies built on it are in attn_stream.hpp.
+// Included by every attention translation unit; the streaming kernel bodies built on it are in attn_stream.hpp, the host
+// checks and parameter filling of the entry points in attn_host.hpp.
 #pragma once
 #include "common.hpp"
 
@@ -32,27 +33,6 @@ struct AttnParams {
   const uint64_t* seed_dev;   // optional device-resident counter added to seed (hipGraph replays; see SeedArg in common.hpp)
   uint32_t grid_q, grid_pairs;   // pipelined forward: 1-D grid of grid_q query blocks x grid_pairs (batch, head) pairs
 };
-
-// ---- host side, shared by the four streaming entry points (gmlm_attention_fwd/_bwd, gmlm_attention_d128_fwd/_bwd) ----
-// 8-bit dropout threshold: P(drop) = th / 256 (|error| <= 2e-3: 0.1 -> 0.1016, 0.3 -> 0.3008), keep scale uses the quantised rate
-inline uint32_t drop8(float p) { long t = lroundf(p * 256.f); return (uint32_t)(t < 0 ? 0 : (t > 255 ? 255 : t)); }
-// operand `what` of entry point `who`: 16-byte aligned rows of at least min_stride elements
-inline int attn_stride_check(const char* who, const char* what, const void* ptr, int64_t stride, int64_t min_stride, int dtype) {
-  const int v = dtype == GMLM_F32 ? 4 : 8;
-  GMLM_REQUIRE(ptr && aligned16(ptr), "%s(%s): null or not 16-byte aligned pointer", who, what);
-  GMLM_REQUIRE(stride >= min_stride && stride % v == 0 && stride < (1 << 24),
-               "%s(%s): row stride %ld must be >= %ld, < 2^24 and a multiple of %d", who, what, (long)stride, (long)min_stride, v);
-  return GMLM_OK;
-}
-// the fields every entry point sets the same way (output / gradient pointers and the packed-mode fields are the caller's)
-inline void attn_fill(AttnParams& p, const void* q, const void* k, const void* v, const int32_t* kv_len, int64_t b, int64_t h,
-                      int64_t lq, int64_t lk, int64_t q_stride, int64_t k_stride, int64_t v_stride, float scale, float dropout_p,
-                      uint64_t seed, const uint64_t* seed_dev) {
-  p.q = q; p.k = k; p.v = v; p.kv_len = kv_len;
-  p.b = b; p.h = h; p.lq = lq; p.lk = lk; p.q_stride = q_stride; p.k_stride = k_stride; p.v_stride = v_stride;
-  p.scale = scale; p.seed = seed; p.seed_dev = seed_dev;
-  p.drop_thresh = drop8(dropout_p); p.keep_scale = 256.f / (256.f - (float)p.drop_thresh);
-}
 
 // per-(batch, head) view: padded layout [b, l, ...] or packed layout (cu_seqlens)
 __device__ __forceinline__ void seq_view(const AttnParams& p, int64_t b, int64_t hd, int64_t& lq_, int64_t& lk_, int64_t& qbase,

@@ -11,7 +11,9 @@
 //  * bf16: 64-row K / V (forward, dQ) and 32-row Q / dO (dK/dV) tiles, double-buffered in LDS (68 KiB / 35 KiB per
 //    workgroup); fp32 (the 1e-4 parity path, v_mfma_f32_32x32x2_f32): 32-row tiles, one buffer.  No kernel spills.
 //  * dK/dV without atomics: a workgroup owns 128 keys and walks all query tiles in order (deterministic).
+// The argument checks and the AttnParams filling shared with the other attention entry points are in attn_host.hpp.
 #include "attn_stream.hpp"
+#include "attn_host.hpp"
 
 namespace gmlm {
 namespace d128 {
@@ -198,15 +200,14 @@ __global__ __launch_bounds__(NT) void dkv_kernel(Params x) {
   attn_dkv_body<T, D, NW, DROP, Cfg<T>::QT, Cfg<T>::DBUF>(x.a, it.tile, it.b, it.hd, x.dout_stride);
 }
 
-// host checks shared by the forward and the backward; fills the launch parameters
+// the checks of attn_host.hpp up to the empty-problem return, with this family's head dim and work-item bound; fills the
+// launch parameters
 static int setup(const char* who, Params& x, const void* q, const void* k, const void* v, const int32_t* kv_len, int64_t b, int64_t h,
                  int64_t lq, int64_t lk, int64_t d, int64_t q_stride, int64_t k_stride, int64_t v_stride, float scale, float dropout_p,
-                 uint64_t seed, const uint64_t* seed_dev, int dtype) {
-  GMLM_REQUIRE(d == 128, "%s: head dim %ld not supported (this entry point takes 128)", who, (long)d);
-  GMLM_REQUIRE(b >= 0 && h > 0 && lq >= 0 && lk >= 0, "%s: bad sizes", who);
-  GMLM_REQUIRE(dtype == GMLM_F32 || dtype == GMLM_BF16, "%s: unsupported dtype", who);
-  GMLM_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "%s: dropout_p must be in [0,1)", who);
-  GMLM_REQUIRE(scale > 0.f, "%s: scale must be positive", who);
+                 uint64_t seed, const uint64_t* seed_dev, const void* out_lo, int dtype) {
+  int rc = attn_check_shape(who, b >= 0 && h > 0 && lq >= 0 && lk >= 0, d == 128, d, "this entry point takes 128", dtype, out_lo);
+  if (rc != GMLM_OK) return rc;
+  if ((rc = attn_check_rates(who, dropout_p, true, scale)) != GMLM_OK) return rc;
   const int64_t rows = lq > lk ? lq : lk;
   GMLM_REQUIRE(cdiv(rows, BQ) * b * h < ((int64_t)1 << 31), "%s: too many work items", who);
   x = Params{};
@@ -239,17 +240,11 @@ extern "C" int gmlm_attention_d128_fwd(const void* q, const void* k, const void*
                                        void* out_lo, float* lse, int dtype, gmlm_stream_t stream) {
   static const char* who = "attention_d128_fwd";
   Params x;
-  int rc = setup(who, x, q, k, v, kv_len, b, h, lq, lk, d, q_stride, k_stride, v_stride, scale, dropout_p, seed, seed_dev, dtype);
+  int rc = setup(who, x, q, k, v, kv_len, b, h, lq, lk, d, q_stride, k_stride, v_stride, scale, dropout_p, seed, seed_dev, out_lo, dtype);
   if (rc != GMLM_OK) return rc;
-  GMLM_REQUIRE(!out_lo || (dtype == GMLM_BF16 && aligned16(out_lo)), "%s: out_lo is the bf16 residual of a bf16 output (16-byte aligned)", who);
   if (b == 0 || lq == 0) return GMLM_OK;
-  if ((rc = attn_stride_check(who, "q", q, q_stride, h * 128, dtype)) != GMLM_OK) return rc;
-  if (lk > 0) {
-    if ((rc = attn_stride_check(who, "k", k, k_stride, h * 128, dtype)) != GMLM_OK) return rc;
-    if ((rc = attn_stride_check(who, "v", v, v_stride, h * 128, dtype)) != GMLM_OK) return rc;
-  }
-  GMLM_REQUIRE(out && aligned16(out), "%s: null or misaligned out", who);
   x.a.o_w = out; x.a.o_lo_w = out_lo; x.a.lse_w = lse;
+  if ((rc = attn_check_fwd_operands(who, x.a, h * D, h * D, dtype)) != GMLM_OK) return rc;
   hipStream_t st = as_stream(stream);
   const dim3 grid((unsigned)(cdiv(lq, BQ) * b * h));
   GMLM_D128_LAUNCH(fwd_kernel, grid, st, x);
@@ -258,7 +253,7 @@ extern "C" int gmlm_attention_d128_fwd(const void* q, const void* k, const void*
 }
 
 extern "C" size_t gmlm_attention_d128_workspace_bytes(int64_t b, int64_t h, int64_t lq) {
-  return (size_t)(b * h * lq > 0 ? b * h * lq : 1) * sizeof(float);   // delta
+  return attn_delta_bytes(b, h, lq);
 }
 
 extern "C" int gmlm_attention_d128_bwd(const void* q, const void* k, const void* v, const void* out, const void* out_lo,
@@ -269,33 +264,16 @@ extern "C" int gmlm_attention_d128_bwd(const void* q, const void* k, const void*
                                        void* workspace, size_t workspace_bytes, gmlm_stream_t stream) {
   static const char* who = "attention_d128_bwd";
   Params x;
-  int rc = setup(who, x, q, k, v, kv_len, b, h, lq, lk, d, q_stride, k_stride, v_stride, scale, dropout_p, seed, seed_dev, dtype);
+  int rc = setup(who, x, q, k, v, kv_len, b, h, lq, lk, d, q_stride, k_stride, v_stride, scale, dropout_p, seed, seed_dev, out_lo, dtype);
   if (rc != GMLM_OK) return rc;
-  GMLM_REQUIRE(!out_lo || (dtype == GMLM_BF16 && aligned16(out_lo)), "%s: out_lo is the bf16 residual of a bf16 output (16-byte aligned)", who);
   if (b == 0 || (lq == 0 && lk == 0)) return GMLM_OK;
   GMLM_REQUIRE(lq > 0 && lk > 0, "%s: empty query or key set with a non-empty counterpart is not supported", who);
-  if ((rc = attn_stride_check(who, "q", q, q_stride, h * 128, dtype)) != GMLM_OK) return rc;
-  if ((rc = attn_stride_check(who, "k", k, k_stride, h * 128, dtype)) != GMLM_OK) return rc;
-  if ((rc = attn_stride_check(who, "v", v, v_stride, h * 128, dtype)) != GMLM_OK) return rc;
-  if ((rc = attn_stride_check(who, "dq", dq, dq_stride, h * 128, dtype)) != GMLM_OK) return rc;
-  if ((rc = attn_stride_check(who, "dk", dk, dk_stride, h * 128, dtype)) != GMLM_OK) return rc;
-  if ((rc = attn_stride_check(who, "dv", dv, dv_stride, h * 128, dtype)) != GMLM_OK) return rc;
-  GMLM_REQUIRE(out && dout && lse && aligned16(out) && aligned16(dout), "%s: null or misaligned out/dout/lse", who);
-  if (!workspace || workspace_bytes < gmlm_attention_d128_workspace_bytes(b, h, lq)) {
-    set_error("%s: workspace too small", who);
-    return GMLM_EWORKSPACE;
-  }
   AttnParams& p = x.a;
-  p.out = out; p.out_lo = out_lo; p.dout = dout; p.lse = lse;
-  p.delta = static_cast<float*>(workspace);
-  p.dq = dq; p.dk = dk; p.dv = dv;
-  p.dq_stride = dq_stride; p.dk_stride = dk_stride; p.dv_stride = dv_stride;
+  attn_fill_bwd(p, out, out_lo, dout, lse, dq, dk, dv, dq_stride, dk_stride, dv_stride, workspace);
+  if ((rc = attn_check_bwd_operands(who, p, h * D, h * D, dtype, workspace_bytes, attn_delta_bytes(b, h, lq))) != GMLM_OK) return rc;
   hipStream_t st = as_stream(stream);
   const int64_t rows = b * lq * h;
-  if (dtype == GMLM_BF16)
-    delta_kernel<bf16_t><<<(unsigned)cdiv(rows * 16, 256), 256, 0, st>>>((const bf16_t*)out, (const bf16_t*)out_lo, (const bf16_t*)dout, rows, lq, h, p.delta);
-  else
-    delta_kernel<float><<<(unsigned)cdiv(rows * 32, 256), 256, 0, st>>>((const float*)out, nullptr, (const float*)dout, rows, lq, h, p.delta);
+  GMLM_ATTN_DELTA_LAUNCH(delta_kernel, p, rows, dtype == GMLM_BF16 ? 16 : 32, st, lq, h);
   GMLM_LAUNCH_CHECK();
   const dim3 gq((unsigned)(cdiv(lq, BQ) * b * h));
   GMLM_D128_LAUNCH(dq_kernel, gq, st, x);

@@ -16,7 +16,9 @@
 //        rows <= 128 ->  64 rows, 2 waves  (the encoder's 16-128 token texts: at most two work items per (sequence, head))
 //        else        -> 128 rows, 4 waves  (long sequences: four waves share each staged K / V tile)
 //    One rule for the forward, dQ and dK/dV launches of a call; all three heights of every kernel are reachable.
+// The argument checks and the AttnParams filling shared with the other attention entry points are in attn_host.hpp.
 #include "attn_stream.hpp"
+#include "attn_host.hpp"
 #include "../../include/gmlm_hip_d32.h"
 
 namespace gmlm {
@@ -67,19 +69,16 @@ __global__ __launch_bounds__(NW * 64) void dkv_kernel(AttnParams p) {
 // waves per workgroup from the longest sequence of the call (the rule of the header)
 static inline int pick_waves(int64_t rows) { return rows <= 32 ? 1 : (rows <= 128 ? 2 : 4); }
 
-// host checks shared by the forward and the backward, in the order of gmlm_hip.h (sizes and dtype first); fills the
-// launch parameters and the workgroup height
+// the checks of attn_host.hpp up to the empty-problem return, with this family's head dim, packed mode and work-item bound;
+// fills the launch parameters and the workgroup height
 static int setup(const char* who, AttnParams& p, int& nw, const void* q, const void* k, const void* v, const int32_t* kv_len,
                  int64_t b, int64_t h, int64_t lq, int64_t lk, int64_t d, int64_t q_stride, int64_t k_stride, int64_t v_stride,
                  float scale, float dropout_p, uint64_t seed, const uint64_t* seed_dev, const void* out_lo, int dtype,
                  const int32_t* cu_seqlens, int64_t max_len) {
-  GMLM_REQUIRE(b >= 0 && h > 0 && lq >= 0 && lk >= 0, "%s: bad sizes", who);
-  GMLM_REQUIRE(d == 32, "%s: head dim %ld not supported (this entry point takes 32)", who, (long)d);
-  GMLM_REQUIRE(dtype == GMLM_F32 || dtype == GMLM_BF16, "%s: unsupported dtype", who);
-  GMLM_REQUIRE(!out_lo || (dtype == GMLM_BF16 && aligned16(out_lo)), "%s: out_lo is the bf16 residual of a bf16 output (16-byte aligned)", who);
+  int rc = attn_check_shape(who, b >= 0 && h > 0 && lq >= 0 && lk >= 0, d == 32, d, "this entry point takes 32", dtype, out_lo);
+  if (rc != GMLM_OK) return rc;
   GMLM_REQUIRE(!cu_seqlens || (lq == lk && max_len > 0 && !kv_len), "%s: packed mode needs lq == lk = total rows, max_len > 0, kv_len NULL", who);
-  GMLM_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "%s: dropout_p must be in [0,1)", who);
-  GMLM_REQUIRE(scale > 0.f, "%s: scale must be positive", who);
+  if ((rc = attn_check_rates(who, dropout_p, true, scale)) != GMLM_OK) return rc;
   const int64_t rows = cu_seqlens ? max_len : (lq > lk ? lq : lk);
   nw = pick_waves(rows);
   // each factor and each partial product is bounded before the next multiply: no int64 overflow on the way to the answer
@@ -127,13 +126,8 @@ extern "C" int gmlm_attention_d32_fwd(const void* q, const void* k, const void* 
                  dtype, cu_seqlens, max_len);
   if (rc != GMLM_OK) return rc;
   if (b == 0 || lq == 0) return GMLM_OK;
-  if ((rc = attn_stride_check(who, "q", q, q_stride, h * D, dtype)) != GMLM_OK) return rc;
-  if (lk > 0) {
-    if ((rc = attn_stride_check(who, "k", k, k_stride, h * D, dtype)) != GMLM_OK) return rc;
-    if ((rc = attn_stride_check(who, "v", v, v_stride, h * D, dtype)) != GMLM_OK) return rc;
-  }
-  GMLM_REQUIRE(out && aligned16(out), "%s: null or misaligned out", who);
   p.o_w = out; p.o_lo_w = out_lo; p.lse_w = lse;
+  if ((rc = attn_check_fwd_operands(who, p, h * D, h * D, dtype)) != GMLM_OK) return rc;
   hipStream_t st = as_stream(stream);
   GMLM_D32_LAUNCH(fwd_kernel, nw, cu_seqlens ? max_len : lq, b * h, st, p);
   GMLM_LAUNCH_CHECK();
@@ -141,7 +135,7 @@ extern "C" int gmlm_attention_d32_fwd(const void* q, const void* k, const void* 
 }
 
 extern "C" size_t gmlm_attention_d32_bwd_workspace_bytes(int64_t b, int64_t h, int64_t lq) {
-  return (size_t)(b * h * lq > 0 ? b * h * lq : 1) * sizeof(float);   // delta
+  return attn_delta_bytes(b, h, lq);
 }
 
 extern "C" int gmlm_attention_d32_bwd(const void* q, const void* k, const void* v, const void* out, const void* dout,
@@ -158,26 +152,12 @@ extern "C" int gmlm_attention_d32_bwd(const void* q, const void* k, const void* 
   if (rc != GMLM_OK) return rc;
   if (b == 0 || (lq == 0 && lk == 0)) return GMLM_OK;
   GMLM_REQUIRE(lq > 0 && lk > 0, "%s: empty query or key set with a non-empty counterpart is not supported", who);
-  if ((rc = attn_stride_check(who, "q", q, q_stride, h * D, dtype)) != GMLM_OK) return rc;
-  if ((rc = attn_stride_check(who, "k", k, k_stride, h * D, dtype)) != GMLM_OK) return rc;
-  if ((rc = attn_stride_check(who, "v", v, v_stride, h * D, dtype)) != GMLM_OK) return rc;
-  if ((rc = attn_stride_check(who, "dq", dq, dq_stride, h * D, dtype)) != GMLM_OK) return rc;
-  if ((rc = attn_stride_check(who, "dk", dk, dk_stride, h * D, dtype)) != GMLM_OK) return rc;
-  if ((rc = attn_stride_check(who, "dv", dv, dv_stride, h * D, dtype)) != GMLM_OK) return rc;
-  GMLM_REQUIRE(out && dout && lse && aligned16(out) && aligned16(dout), "%s: null or misaligned out/dout/lse", who);
   const int64_t nb = cu_seqlens ? 1 : b;        // delta: packed tensors are one [total_rows, h, 32] block, delta is [h, total_rows]
-  GMLM_REQUIRE_WS(workspace && workspace_bytes >= gmlm_attention_d32_bwd_workspace_bytes(nb, h, lq), "%s: workspace too small", who);
-  p.out = out; p.out_lo = out_lo; p.dout = dout; p.lse = lse;
-  p.delta = static_cast<float*>(workspace);
-  p.dq = dq; p.dk = dk; p.dv = dv;
-  p.dq_stride = dq_stride; p.dk_stride = dk_stride; p.dv_stride = dv_stride;
+  attn_fill_bwd(p, out, out_lo, dout, lse, dq, dk, dv, dq_stride, dk_stride, dv_stride, workspace);
+  if ((rc = attn_check_bwd_operands(who, p, h * D, h * D, dtype, workspace_bytes, attn_delta_bytes(nb, h, lq))) != GMLM_OK) return rc;
   hipStream_t st = as_stream(stream);
   const int64_t rows = nb * lq * h;
-  const unsigned gd = (unsigned)cdiv(rows * 8, (int64_t)256);
-  if (dtype == GMLM_BF16)
-    delta_kernel<bf16_t><<<gd, 256, 0, st>>>((const bf16_t*)out, (const bf16_t*)out_lo, (const bf16_t*)dout, rows, lq, h, p.delta);
-  else
-    delta_kernel<float><<<gd, 256, 0, st>>>((const float*)out, nullptr, (const float*)dout, rows, lq, h, p.delta);
+  GMLM_ATTN_DELTA_LAUNCH(delta_kernel, p, rows, 8, st, lq, h);
   GMLM_LAUNCH_CHECK();
   GMLM_D32_LAUNCH(dq_kernel, nw, cu_seqlens ? max_len : lq, b * h, st, p);
   GMLM_LAUNCH_CHECK();

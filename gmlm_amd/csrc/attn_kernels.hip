@@ -17,9 +17,11 @@
 //    loops over query tiles).  P is recomputed from Q, K and the forward's log-sum-exp.
 //  * padding: keys >= kv_len[b] get probability exactly 0 (the reference adds finfo.min and
 //    softmaxes: the same zeros in fp32); whole tiles past kv_len are skipped.
-// The device code of these kernels is in attn_stream.hpp (one body per kernel, shared with attn_d128.hip); this file
-// holds their d = 64 / 96 entry points and the dispatch of gmlm_attention_fwd / gmlm_attention_bwd.
+// The device code of these kernels is in attn_stream.hpp (one body per kernel, shared with attn_d128.hip) and the host contract
+// of every attention entry point in attn_host.hpp; this file holds the d = 64 / 96 kernel entry points, what
+// gmlm_attention_fwd / gmlm_attention_bwd check beyond that contract, and their dispatch.
 #include "attn_stream.hpp"
+#include "attn_host.hpp"
 #include "colreduce.hpp"
 
 namespace gmlm {
@@ -50,10 +52,15 @@ __global__ __launch_bounds__(NW * 64) void attn_bwd_dkv_kernel(AttnParams p) {
   attn_dkv_body<T, D, NW, DROP, QT, sizeof(T) == 2 && QT <= 64>(p, blockIdx.x, blockIdx.y / p.h, blockIdx.y % p.h, p.h * D);
 }
 
-static int attn_check(const char* who, int64_t b, int64_t h, int64_t lq, int64_t lk, int64_t d, int dtype) {
-  GMLM_REQUIRE(b >= 0 && h > 0 && lq >= 0 && lk >= 0, "%s: bad sizes", who);
-  GMLM_REQUIRE(d == 64 || d == 96, "%s: head dim %ld not supported (64 or 96)", who, (long)d);
-  GMLM_REQUIRE(dtype == GMLM_F32 || dtype == GMLM_BF16, "%s: unsupported dtype", who);
+// the host checks of gmlm_attention_fwd / _bwd up to the empty-problem return, in the order of attn_host.hpp
+static int attn_check(const char* who, int64_t b, int64_t h, int64_t lq, int64_t lk, int64_t d, int dtype, const void* out_lo,
+                      const int32_t* kv_len, const int32_t* cu_seqlens, int64_t max_len, const int32_t* seq_groups, int64_t num_groups,
+                      float dropout_p, float scale) {
+  int rc = attn_check_shape(who, b >= 0 && h > 0 && lq >= 0 && lk >= 0, d == 64 || d == 96, d, "64 or 96", dtype, out_lo);
+  if (rc != GMLM_OK) return rc;
+  GMLM_REQUIRE(!cu_seqlens || (lq == lk && max_len > 0 && !kv_len), "%s: packed mode needs lq == lk = total rows, max_len > 0, kv_len NULL", who);
+  GMLM_REQUIRE(!seq_groups || (cu_seqlens && num_groups > 0 && num_groups <= b), "%s: seq_groups needs packed mode and 0 < num_groups <= b", who);
+  if ((rc = attn_check_rates(who, dropout_p, true, scale)) != GMLM_OK) return rc;
   GMLM_REQUIRE(b * h <= 65535, "%s: batch*heads %ld > 65535", who, (long)(b * h));   // grid.y of the two-dimensional launches
   return GMLM_OK;
 }
@@ -104,23 +111,14 @@ extern "C" int gmlm_attention_fwd(const void* q, const void* k, const void* v, c
                                   float scale, float dropout_p, uint64_t seed, const uint64_t* seed_dev, void* out, void* out_lo, float* lse,
                                   int dtype, const int32_t* cu_seqlens, int64_t max_len, const int32_t* seq_groups, int64_t num_groups,
                                   gmlm_stream_t stream) {
-  int rc = attn_check("attention_fwd", b, h, lq, lk, d, dtype);
-  if (rc != GMLM_OK) return rc;   // sizes and dtype first: their message must not be replaced by a later check's
-  GMLM_REQUIRE(!seq_groups || (cu_seqlens && num_groups > 0 && num_groups <= b), "attention_fwd: seq_groups needs packed mode and 0 < num_groups <= b");
-  GMLM_REQUIRE(!out_lo || (dtype == GMLM_BF16 && aligned16(out_lo)), "attention_fwd: out_lo is the bf16 residual of a bf16 output (16-byte aligned)");
-  GMLM_REQUIRE(!cu_seqlens || (lq == lk && max_len > 0 && !kv_len), "attention_fwd: packed mode needs lq == lk = total rows, max_len > 0, kv_len NULL");
-  GMLM_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "attention_fwd: dropout_p must be in [0,1)");
-  GMLM_REQUIRE(scale > 0.f, "attention_fwd: scale must be positive");
+  static const char* who = "attention_fwd";
+  int rc = attn_check(who, b, h, lq, lk, d, dtype, out_lo, kv_len, cu_seqlens, max_len, seq_groups, num_groups, dropout_p, scale);
+  if (rc != GMLM_OK) return rc;
   if (b == 0 || lq == 0) return GMLM_OK;
-  if ((rc = attn_stride_check("attention_fwd", "q", q, q_stride, h * d, dtype)) != GMLM_OK) return rc;
-  if (lk > 0) {
-    if ((rc = attn_stride_check("attention_fwd", "k", k, k_stride, h * d, dtype)) != GMLM_OK) return rc;
-    if ((rc = attn_stride_check("attention_fwd", "v", v, v_stride, h * d, dtype)) != GMLM_OK) return rc;
-  }
-  GMLM_REQUIRE(out && aligned16(out), "attention_fwd: null or misaligned out");
   AttnParams p{};
   attn_fill(p, q, k, v, kv_len, b, h, lq, lk, q_stride, k_stride, v_stride, scale, dropout_p, seed, seed_dev);
   p.o_w = out; p.o_lo_w = out_lo; p.lse_w = lse; p.cu = cu_seqlens; p.groups = seq_groups;
+  if ((rc = attn_check_fwd_operands(who, p, h * d, h * d, dtype)) != GMLM_OK) return rc;
   const int64_t rows_q = cu_seqlens ? max_len : lq;
   hipStream_t st = as_stream(stream);
 #ifdef GMLM_ATTN_STAMP
@@ -159,7 +157,7 @@ extern "C" int gmlm_attention_fwd(const void* q, const void* k, const void* v, c
 
 extern "C" size_t gmlm_attention_bwd_workspace_bytes(int64_t b, int64_t h, int64_t lq, int64_t lk, int64_t d) {
   (void)lk; (void)d;
-  return (size_t)(b * h * lq > 0 ? b * h * lq : 1) * sizeof(float);  // delta
+  return attn_delta_bytes(b, h, lq);
 }
 
 extern "C" int gmlm_attention_bwd(const void* q, const void* k, const void* v, const void* out, const void* dout,
@@ -169,50 +167,29 @@ extern "C" int gmlm_attention_bwd(const void* q, const void* k, const void* v, c
                                   int64_t dk_stride, int64_t dv_stride, int dtype, const int32_t* cu_seqlens, int64_t max_len,
                                   void* workspace, size_t workspace_bytes, float* dbias_partial, float* dbias,
                                   const void* out_lo, const int32_t* seq_groups, int64_t num_groups, gmlm_stream_t stream) {
-  int rc = attn_check("attention_bwd", b, h, lq, lk, d, dtype);
-  if (rc != GMLM_OK) return rc;   // sizes and dtype first: their message must not be replaced by a later check's
-  GMLM_REQUIRE(!seq_groups || (cu_seqlens && num_groups > 0 && num_groups <= b), "attention_bwd: seq_groups needs packed mode and 0 < num_groups <= b");
-  GMLM_REQUIRE(!out_lo || (dtype == GMLM_BF16 && aligned16(out_lo)), "attention_bwd: out_lo is the bf16 residual of a bf16 output (16-byte aligned)");
-  GMLM_REQUIRE((dbias_partial == nullptr) == (dbias == nullptr), "attention_bwd: dbias_partial and dbias come together");
-  GMLM_REQUIRE(!cu_seqlens || (lq == lk && max_len > 0 && !kv_len), "attention_bwd: packed mode needs lq == lk = total rows, max_len > 0, kv_len NULL");
-  GMLM_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "attention_bwd: dropout_p must be in [0,1)");
-  GMLM_REQUIRE(scale > 0.f, "attention_bwd: scale must be positive");
+  static const char* who = "attention_bwd";
+  int rc = attn_check(who, b, h, lq, lk, d, dtype, out_lo, kv_len, cu_seqlens, max_len, seq_groups, num_groups, dropout_p, scale);
+  if (rc != GMLM_OK) return rc;
+  GMLM_REQUIRE((dbias_partial == nullptr) == (dbias == nullptr), "%s: dbias_partial and dbias come together", who);
   if (b == 0 || (lq == 0 && lk == 0)) return GMLM_OK;
-  GMLM_REQUIRE(lq > 0 && lk > 0, "attention_bwd: empty query or key set with a non-empty counterpart is not supported");
-  if ((rc = attn_stride_check("attention_bwd", "q", q, q_stride, h * d, dtype)) != GMLM_OK) return rc;
-  if ((rc = attn_stride_check("attention_bwd", "k", k, k_stride, h * d, dtype)) != GMLM_OK) return rc;
-  if ((rc = attn_stride_check("attention_bwd", "v", v, v_stride, h * d, dtype)) != GMLM_OK) return rc;
-  if ((rc = attn_stride_check("attention_bwd", "dq", dq, dq_stride, h * d, dtype)) != GMLM_OK) return rc;
-  if ((rc = attn_stride_check("attention_bwd", "dk", dk, dk_stride, h * d, dtype)) != GMLM_OK) return rc;
-  if ((rc = attn_stride_check("attention_bwd", "dv", dv, dv_stride, h * d, dtype)) != GMLM_OK) return rc;
-  GMLM_REQUIRE(out && dout && lse && aligned16(out) && aligned16(dout), "attention_bwd: null or misaligned out/dout/lse");
-  GMLM_REQUIRE_WS(workspace && workspace_bytes >= gmlm_attention_bwd_workspace_bytes(cu_seqlens ? 1 : b, h, lq, lk, d),
-                  "attention_bwd: workspace too small");
-  hipStream_t st = as_stream(stream);
+  GMLM_REQUIRE(lq > 0 && lk > 0, "%s: empty query or key set with a non-empty counterpart is not supported", who);
+  const int64_t nb = cu_seqlens ? 1 : b;        // delta: packed tensors are one [total_rows, h, d] block
   AttnParams p{};
   attn_fill(p, q, k, v, kv_len, b, h, lq, lk, q_stride, k_stride, v_stride, scale, dropout_p, seed, seed_dev);
-  p.out = out; p.out_lo = out_lo; p.dout = dout; p.lse = lse; p.cu = cu_seqlens; p.groups = seq_groups;
+  attn_fill_bwd(p, out, out_lo, dout, lse, dq, dk, dv, dq_stride, dk_stride, dv_stride, workspace);
+  p.cu = cu_seqlens; p.groups = seq_groups; p.dbias_part = dbias_partial;
+  if ((rc = attn_check_bwd_operands(who, p, h * d, h * d, dtype, workspace_bytes, attn_delta_bytes(nb, h, lq))) != GMLM_OK) return rc;
+  hipStream_t st = as_stream(stream);
   const int64_t rows_q = cu_seqlens ? max_len : lq, rows_k = cu_seqlens ? max_len : lk;
-  const int64_t nb = cu_seqlens ? 1 : b;        // delta kernel: packed tensors are one [total_rows, h, d] block
-  p.delta = static_cast<float*>(workspace);
-  p.dq = dq; p.dk = dk; p.dv = dv; p.dbias_part = dbias_partial;
-  p.dq_stride = dq_stride; p.dk_stride = dk_stride; p.dv_stride = dv_stride;
   if (dtype == GMLM_BF16 && d == 64 && rows_q <= 128 && rows_k <= 128 && b * h >= 512) {
     // short sequences, enough of them to fill the chip: one fused launch (delta + dQ + dK/dV), no workspace, O is not read
     const int64_t rmax = rows_q > rows_k ? rows_q : rows_k;
     return attn_short_bwd_launch(p, seq_groups ? 128 : rmax, seq_groups ? num_groups : b, dbias, st);
   }
-  GMLM_REQUIRE(!dbias, "attention_bwd: the fused bias-gradient sums exist only on the short-sequence path (bf16, d = 64, <= 128 rows, b*h >= 512)");
+  GMLM_REQUIRE(!dbias, "%s: the fused bias-gradient sums exist only on the short-sequence path (bf16, d = 64, <= 128 rows, b*h >= 512)", who);
   const int64_t rows = nb * lq * h;
-  {
-    const int cpr = (int)d / (dtype == GMLM_BF16 ? 8 : 4);
-    const int lanes = cpr <= 8 ? 8 : (cpr <= 16 ? 16 : 32);
-    const int64_t threads = rows * lanes;
-    if (dtype == GMLM_BF16)
-      attn_delta_kernel<bf16_t><<<(unsigned)cdiv(threads, 256), 256, 0, st>>>((const bf16_t*)out, (const bf16_t*)out_lo, (const bf16_t*)dout, rows, (int)d, lq, h, p.delta);
-    else
-      attn_delta_kernel<float><<<(unsigned)cdiv(threads, 256), 256, 0, st>>>((const float*)out, nullptr, (const float*)dout, rows, (int)d, lq, h, p.delta);
-  }
+  const int cpr = (int)d / (dtype == GMLM_BF16 ? 8 : 4);
+  GMLM_ATTN_DELTA_LAUNCH(attn_delta_kernel, p, rows, cpr <= 8 ? 8 : (cpr <= 16 ? 16 : 32), st, (int)d, lq, h);
   GMLM_LAUNCH_CHECK();
   if (dtype == GMLM_BF16 && d == 96) {
     // CrossAttention geometry: LDS-DMA staged kernels (attn_bwd_pipe.hip): no staging registers (the register-staged 2- / 4-wave

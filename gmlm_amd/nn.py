@@ -570,44 +570,39 @@ class _SplitLast(torch.autograd.Function):
         return torch.cat([ga, gb], -1), None
 
 
-def attention_any_dim(q, k, v, kv_len, num_heads, scale, dropout_p, training):
-    """K5/K7 with head dims the MFMA tiling does not cover natively zero-padded to 64 / 96 / 128 (exact:
-    zero columns change neither the scores nor the real output columns)."""
+def _attention_padded(q, k, v, kv_len, num_heads, scale, dropout_p, training, native):
+    """ops.attention with the head dim zero-padded to the next of ``native`` (ascending) and the output cut back: exact, zero
+    columns change neither the scores nor the real output columns.  ``scale`` is the caller's, of the TRUE head dim."""
     b, lq, hd = q.shape
     d = hd // num_heads
-    if d in (64, 96, 128):
+    dp = next(n for n in native if n >= d)
+    if dp == d:
         return ops.attention(q, k, v, kv_len, num_heads, scale, dropout_p, training)
-    if d > 128:
-        raise NotImplementedError(f"attention head dim {d} > 128 is not supported by the gfx950 kernels")
-    dp = 64 if d < 64 else (96 if d < 96 else 128)
 
     def pad(t):
         return F.pad(t.reshape(t.shape[0], t.shape[1], num_heads, d), (0, dp - d)).reshape(t.shape[0], t.shape[1], num_heads * dp)
 
     o = ops.attention(pad(q), pad(k), pad(v), kv_len, num_heads, scale, dropout_p, training)
     return o.reshape(b, lq, num_heads, dp)[..., :d].reshape(b, lq, hd)
+
+
+def attention_any_dim(q, k, v, kv_len, num_heads, scale, dropout_p, training):
+    """K5/K7 at head dims up to 128: those the MFMA tiling does not cover natively run zero-padded to 64 / 96 / 128."""
+    d = q.shape[-1] // num_heads
+    if d > 128:
+        raise NotImplementedError(f"attention head dim {d} > 128 is not supported by the gfx950 kernels")
+    return _attention_padded(q, k, v, kv_len, num_heads, scale, dropout_p, training, (64, 96, 128))
 
 
 def attention_wide_dim(q, k, v, kv_len, num_heads, scale, dropout_p, training):
     """K5/K7 at head dims 129 ... 512 (the CrossAttention of an encoder wider than 1,024) on the wide-head kernels
-    (gmlm_attention_wide_*, native at 256 / 384 / 512): other head dims are zero-padded to the next of the three and the
-    output is cut back, which is exact by the argument of ``attention_any_dim``.  ``scale`` is the caller's (of the TRUE
-    head dim) and passes through unchanged."""
-    b, lq, hd = q.shape
-    d = hd // num_heads
-    if d in ops.ATTN_WIDE_DIMS:
-        return ops.attention(q, k, v, kv_len, num_heads, scale, dropout_p, training)
+    (gmlm_attention_wide_*, native at 256 / 384 / 512): other head dims run zero-padded to the next of the three."""
+    d = q.shape[-1] // num_heads
     if d > 512:
         raise NotImplementedError(f"attention head dim {d} > 512 is not supported by the gfx950 kernels")
     if d <= 128:
         raise ValueError(f"attention_wide_dim takes head dims 129 ... 512, got {d}: use attention_any_dim")
-    dp = 256 if d < 256 else (384 if d < 384 else 512)
-
-    def pad(t):
-        return F.pad(t.reshape(t.shape[0], t.shape[1], num_heads, d), (0, dp - d)).reshape(t.shape[0], t.shape[1], num_heads * dp)
-
-    o = ops.attention(pad(q), pad(k), pad(v), kv_len, num_heads, scale, dropout_p, training)
-    return o.reshape(b, lq, num_heads, dp)[..., :d].reshape(b, lq, hd)
+    return _attention_padded(q, k, v, kv_len, num_heads, scale, dropout_p, training, ops.ATTN_WIDE_DIMS)
 
 
 class _ScaledProjectionSum(torch.autograd.Function):

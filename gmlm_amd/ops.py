@@ -5,6 +5,8 @@ Tensors are PyTorch-owned device memory handed to the C ABI as raw pointers toge
 """
 from __future__ import annotations
 
+from collections import namedtuple
+from operator import itemgetter
 from typing import Optional
 
 import torch
@@ -533,6 +535,12 @@ LN_WIDE_ABOVE = 1024            # widest row of gmlm_bias_res_layernorm_*; wider
 ATTN_WIDE_DIMS = (256, 384, 512)   # head dims of gmlm_attention_wide_* (attn_wide.hip)
 
 
+def _ln_entries(f: int):   # (forward, backward, workspace size); rows wider than 1,024: norm_wide.hip (a workgroup per row), same arguments
+    if f > LN_WIDE_ABOVE:
+        return "gmlm_bias_res_layernorm_wide_fwd", "gmlm_bias_res_layernorm_wide_bwd", "gmlm_bias_res_layernorm_wide_bwd_workspace_bytes"
+    return "gmlm_bias_res_layernorm_fwd", "gmlm_bias_res_layernorm_bwd", "gmlm_layernorm_bwd_workspace_bytes"
+
+
 class BiasResLayerNorm(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, bias, residual, gamma, beta, eps, act, p, seed):
@@ -548,8 +556,7 @@ class BiasResLayerNorm(torch.autograd.Function):
         mean = torch.empty(rows, dtype=torch.float32, device=x.device)
         rstd = torch.empty_like(mean)
         sd = ctx.sd = _sd()
-        # rows wider than 1,024 have their own entry points (norm_wide.hip: one workgroup per row), same arguments
-        name = "gmlm_bias_res_layernorm_wide_fwd" if f > LN_WIDE_ABOVE else "gmlm_bias_res_layernorm_fwd"
+        name = _ln_entries(f)[0]
         check(getattr(lib(), name)(_ptr(x2), _ptr(bf), _ptr(res2), _ptr(g), _ptr(b), rows, f, float(eps),
                                    int(act), float(p), seed, sd, _ptr(y), _ptr(mean), _ptr(rstd), _dt(x2), _stream()), name)
         ctx.save_for_backward(x2, res2, bf, g, b, mean, rstd)
@@ -567,11 +574,9 @@ class BiasResLayerNorm(torch.autograd.Function):
         dg = torch.empty(f, dtype=torch.float32, device=x2.device)
         dbeta = torch.empty_like(dg)
         dbias = torch.empty_like(dg) if has_bias else None
-        wide = f > LN_WIDE_ABOVE
-        ws = _ws(lib().gmlm_bias_res_layernorm_wide_bwd_workspace_bytes(rows, f) if wide else
-                 lib().gmlm_layernorm_bwd_workspace_bytes(rows, f), x2.device)
+        _, name, ws_name = _ln_entries(f)
+        ws = _ws(getattr(lib(), ws_name)(rows, f), x2.device)
         sd = ctx.sd
-        name = "gmlm_bias_res_layernorm_wide_bwd" if wide else "gmlm_bias_res_layernorm_bwd"
         check(getattr(lib(), name)(_ptr(gy2), _ptr(x2), _ptr(bf), _ptr(res2), _ptr(g), _ptr(b), _ptr(mean),
                                    _ptr(rstd), rows, f, act, p, seed, sd, _ptr(dx), _ptr(dres), _ptr(dg),
                                    _ptr(dbeta), _ptr(dbias), _dt(x2), _ptr(ws), ws.numel(), _stream()), name)
@@ -601,6 +606,57 @@ def _short_path(dtype, d: int, rows: int, pairs: int) -> bool:
     return dtype == torch.bfloat16 and d == 64 and rows <= 128 and pairs >= 512
 
 
+# A head-dim family of non-causal attention entry points: names, and getters that put arguments named as in the headers in ABI
+# order.  The orders are where families differ: out_lo last or after `out`, packed mode, seq_groups and dbias (`short`) or not.
+_AttnFamily = namedtuple("_AttnFamily", "fwd bwd ws fwd_args bwd_args ws_args packed short")
+_ATTN_FWD_ARGS = "q k v kv_len b h lq lk d q_stride k_stride v_stride scale dropout_p seed seed_dev out out_lo lse dtype "
+_ATTN_BWD_ARGS = "kv_len b h lq lk d q_stride k_stride v_stride scale dropout_p seed seed_dev dq dk dv dq_stride dk_stride dv_stride dtype "
+_ATTN_OPTIONAL = dict(cu_seqlens=None, max_len=0, seq_groups=None, num_groups=0, dbias_partial=None, dbias=None)
+
+
+def _attn_family(stem, ws, ws_args, fwd_tail, bwd_head, bwd_tail):
+    return _AttnFamily(stem + "_fwd", stem + "_bwd", stem + ws, itemgetter(*(_ATTN_FWD_ARGS + fwd_tail).split()),
+                       itemgetter(*(bwd_head + _ATTN_BWD_ARGS + bwd_tail).split()), itemgetter(*ws_args.split()),
+                       "cu_seqlens" in fwd_tail, "seq_groups" in fwd_tail)
+
+
+_ATTN_D64 = _attn_family("gmlm_attention", "_bwd_workspace_bytes", "h lq lk d", "cu_seqlens max_len seq_groups num_groups stream",
+                         "q k v out dout lse ", "cu_seqlens max_len workspace workspace_bytes dbias_partial dbias out_lo seq_groups "
+                         "num_groups stream")                                                    # d = 64 / 96: attn_kernels.hip
+_ATTN_D32 = _attn_family("gmlm_attention_d32", "_bwd_workspace_bytes", "h lq", "cu_seqlens max_len stream", "q k v out dout lse ",
+                         "cu_seqlens max_len workspace workspace_bytes out_lo stream")            # attn_d32.hip: no bound on b * h
+_ATTN_D128, _ATTN_WIDE = (_attn_family(stem_, ws_, "h lq", "stream", "q k v out out_lo dout lse ", "workspace workspace_bytes stream")
+                          for stem_, ws_ in (("gmlm_attention_d128", "_workspace_bytes"), ("gmlm_attention_wide", "_bwd_workspace_bytes")))
+_ATTN_FAMILIES = {64: _ATTN_D64, 96: _ATTN_D64, 32: _ATTN_D32, 128: _ATTN_D128, **{d_: _ATTN_WIDE for d_ in ATTN_WIDE_DIMS}}
+
+
+def _attn_family_of(a, fused_qkv):
+    """One lookup per call.  A head dim without a family goes to the d = 64 / 96 entries, whose own check refuses it by name;
+    so does a fused-QKV call (AttentionQKV) at a head dim whose family has no packed mode.  An argument the ABI lacks is an error."""
+    fam = _ATTN_FAMILIES.get(a["d"], _ATTN_D64)
+    if fused_qkv and not fam.packed:
+        fam = _ATTN_D64
+    if (a["cu_seqlens"] is not None and not fam.packed) or ((a["seq_groups"] is not None or a["dbias"] is not None) and not fam.short):
+        raise _lib.GmlmHipError(f"{fam.fwd[:-4]}_*: no packed mode / seq_groups / fused bias sums at head dim {a['d']}")
+    return fam
+
+
+def _attention_fwd(fused_qkv=False, **a):
+    """The one forward call: every argument by its header name (pointers as pointers), placed by the family's order."""
+    a = {**_ATTN_OPTIONAL, **a, "stream": _stream()}
+    fam = _attn_family_of(a, fused_qkv)
+    check(getattr(lib(), fam.fwd)(*fam.fwd_args(a)), fam.fwd)
+
+
+def _attention_bwd(device, fused_qkv=False, **a):
+    """The one backward call, same conventions; allocates the family's workspace (delta: a packed batch is one sequence)."""
+    a = {**_ATTN_OPTIONAL, **a, "stream": _stream()}
+    fam = _attn_family_of(a, fused_qkv)
+    ws = _ws(getattr(lib(), fam.ws)(a["b"] if a["cu_seqlens"] is None else 1, *fam.ws_args(a)), device)
+    a.update(workspace=ws.data_ptr(), workspace_bytes=ws.numel())
+    check(getattr(lib(), fam.bwd)(*fam.bwd_args(a)), fam.bwd)
+
+
 class Attention(torch.autograd.Function):
     """out[b, lq, h*d] = softmax(q k^T * scale + key-padding mask) v with streaming softmax.
 
@@ -623,23 +679,9 @@ class Attention(torch.autograd.Function):
         out_lo = torch.empty_like(out) if want_lo else None
         with _span("attn_fwd_d%d" % d, flops=4.0 * b * h * lq * lk * d):
             sd = ctx.sd = _sd()
-            if d == 128:      # its own entry point (attn_d128.hip): padded layout only, no bound on b * h
-                check(lib().gmlm_attention_d128_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(kv_len), b, h, lq, lk, d, qs, ks, vs, float(scale),
-                                                    float(p), seed, sd, _ptr(out), _ptr(out_lo), _ptr(lse), _dt(q), _stream()),
-                      "gmlm_attention_d128_fwd")
-            elif d == 32:     # its own entry point (attn_d32.hip): no bound on b * h, workgroup height from max(lq, lk)
-                check(lib().gmlm_attention_d32_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(kv_len), b, h, lq, lk, d, qs, ks, vs, float(scale),
-                                                   float(p), seed, sd, _ptr(out), _ptr(out_lo), _ptr(lse), _dt(q), None, 0, _stream()),
-                      "gmlm_attention_d32_fwd")
-            elif d in ATTN_WIDE_DIMS:   # attn_wide.hip: the head dim split over the four waves of a workgroup, padded layout only
-                check(lib().gmlm_attention_wide_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(kv_len), b, h, lq, lk, d, qs, ks, vs, float(scale),
-                                                    float(p), seed, sd, _ptr(out), _ptr(out_lo), _ptr(lse), _dt(q), _stream()),
-                      "gmlm_attention_wide_fwd")
-            else:
-                check(lib().gmlm_attention_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(kv_len), b, h, lq, lk, d, qs, ks, vs, float(scale),
-                                               float(p), seed, sd, _ptr(out), _ptr(out_lo), _ptr(lse), _dt(q), None, 0, None, 0,
-                                               _stream()),
-                      "gmlm_attention_fwd")
+            _attention_fwd(q=_ptr(q), k=_ptr(k), v=_ptr(v), kv_len=_ptr(kv_len), b=b, h=h, lq=lq, lk=lk, d=d, q_stride=qs, k_stride=ks,
+                           v_stride=vs, scale=float(scale), dropout_p=float(p), seed=seed, seed_dev=sd, out=_ptr(out),
+                           out_lo=_ptr(out_lo), lse=_ptr(lse), dtype=_dt(q))
         ctx.save_for_backward(q, k, v, out, lse, kv_len, out_lo)
         ctx.cfg = (h, float(scale), float(p), seed)
         return out
@@ -652,40 +694,14 @@ class Attention(torch.autograd.Function):
         lk = k.shape[1]
         d = hd // h
         gout = gout.contiguous().to(q.dtype)
-        # one fused [.., 3*h*d] gradient buffer when q/k/v came from a fused QKV GEMM, else three
         dq = torch.empty(b, lq, hd, dtype=q.dtype, device=q.device)
         dk = torch.empty(b, lk, hd, dtype=q.dtype, device=q.device)
         dv = torch.empty(b, lk, hd, dtype=q.dtype, device=q.device)
-        ws = _ws(lib().gmlm_attention_d128_workspace_bytes(b, h, lq) if d == 128 else
-                 lib().gmlm_attention_d32_bwd_workspace_bytes(b, h, lq) if d == 32 else
-                 lib().gmlm_attention_wide_bwd_workspace_bytes(b, h, lq) if d in ATTN_WIDE_DIMS else
-                 lib().gmlm_attention_bwd_workspace_bytes(b, h, lq, lk, d), q.device)
         with _span("attn_bwd_d%d" % d, flops=10.0 * b * h * lq * lk * d):
-            sd = ctx.sd
-            if d == 128:
-                check(lib().gmlm_attention_d128_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(out_lo), _ptr(gout), _ptr(lse),
-                                                    _ptr(kv_len), b, h, lq, lk, d, q.stride(1), k.stride(1), v.stride(1), scale, p,
-                                                    seed, sd, _ptr(dq), _ptr(dk), _ptr(dv), hd, hd, hd, _dt(q), _ptr(ws), ws.numel(),
-                                                    _stream()),
-                      "gmlm_attention_d128_bwd")
-            elif d == 32:
-                check(lib().gmlm_attention_d32_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(gout), _ptr(lse), _ptr(kv_len), b, h,
-                                                   lq, lk, d, q.stride(1), k.stride(1), v.stride(1), scale, p, seed, sd, _ptr(dq),
-                                                   _ptr(dk), _ptr(dv), hd, hd, hd, _dt(q), None, 0, _ptr(ws), ws.numel(),
-                                                   _ptr(out_lo), _stream()),
-                      "gmlm_attention_d32_bwd")
-            elif d in ATTN_WIDE_DIMS:
-                check(lib().gmlm_attention_wide_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(out_lo), _ptr(gout), _ptr(lse),
-                                                    _ptr(kv_len), b, h, lq, lk, d, q.stride(1), k.stride(1), v.stride(1), scale, p,
-                                                    seed, sd, _ptr(dq), _ptr(dk), _ptr(dv), hd, hd, hd, _dt(q), _ptr(ws), ws.numel(),
-                                                    _stream()),
-                      "gmlm_attention_wide_bwd")
-            else:
-                check(lib().gmlm_attention_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(gout), _ptr(lse), _ptr(kv_len), b, h,
-                                               lq, lk, d, q.stride(1), k.stride(1), v.stride(1), scale, p, seed, sd, _ptr(dq),
-                                               _ptr(dk), _ptr(dv), hd, hd, hd, _dt(q), None, 0, _ptr(ws), ws.numel(), None, None,
-                                               _ptr(out_lo), None, 0, _stream()),
-                      "gmlm_attention_bwd")
+            _attention_bwd(q.device, q=_ptr(q), k=_ptr(k), v=_ptr(v), out=_ptr(out), out_lo=_ptr(out_lo), dout=_ptr(gout), lse=_ptr(lse),
+                           kv_len=_ptr(kv_len), b=b, h=h, lq=lq, lk=lk, d=d, q_stride=q.stride(1), k_stride=k.stride(1),
+                           v_stride=v.stride(1), scale=scale, dropout_p=p, seed=seed, seed_dev=ctx.sd, dq=_ptr(dq), dk=_ptr(dk),
+                           dv=_ptr(dv), dq_stride=hd, dk_stride=hd, dv_stride=hd, dtype=_dt(q))
         return dq, dk, dv, None, None, None, None, None
 
 
@@ -730,14 +746,10 @@ class AttentionQKV(torch.autograd.Function):
         nb = out.numel() * out.element_size()                   # one of q, k, v, o
         with _span("attn_fwd_d%d" % d, flops=flops, bytes=(4 + (1 if out_lo is not None else 0)) * nb):
             sd = ctx.sd = _sd()
-            if d == 32:       # attn_d32.hip: padded and packed, no short-sequence kernels (groups was dropped above)
-                check(lib().gmlm_attention_d32_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(kv_len), b, h, l, l, d, hd3, hd3, hd3,
-                                                   float(scale), float(p), seed, sd, _ptr(out), _ptr(out_lo), _ptr(lse), _dt(qkv),
-                                                   _ptr(cu_seqlens), int(max_len), _stream()), "gmlm_attention_d32_fwd")
-            else:
-                check(lib().gmlm_attention_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(kv_len), b, h, l, l, d, hd3, hd3, hd3, float(scale),
-                                               float(p), seed, sd, _ptr(out), _ptr(out_lo), _ptr(lse), _dt(qkv), _ptr(cu_seqlens),
-                                               int(max_len), _ptr(groups), n_groups, _stream()), "gmlm_attention_fwd")
+            _attention_fwd(True, q=_ptr(q), k=_ptr(k), v=_ptr(v), kv_len=_ptr(kv_len), b=b, h=h, lq=l, lk=l, d=d, q_stride=hd3,
+                           k_stride=hd3, v_stride=hd3, scale=float(scale), dropout_p=float(p), seed=seed, seed_dev=sd, out=_ptr(out),
+                           out_lo=_ptr(out_lo), lse=_ptr(lse), dtype=_dt(qkv), cu_seqlens=_ptr(cu_seqlens), max_len=int(max_len),
+                           seq_groups=_ptr(groups), num_groups=n_groups)
         if short:
             ctx.save_for_backward(qkv, lse, kv_len, cu_seqlens, groups)        # the fused backward never reads the forward output
         else:
@@ -763,12 +775,8 @@ class AttentionQKV(torch.autograd.Function):
         q, k, v = qkv[..., :hd], qkv[..., hd:2 * hd], qkv[..., 2 * hd:]
         dqkv = torch.empty_like(qkv)
         dq, dk, dv = dqkv[..., :hd], dqkv[..., hd:2 * hd], dqkv[..., 2 * hd:]
-        nb = 1 if cu_seqlens is not None else b
-        ws = _ws(lib().gmlm_attention_d32_bwd_workspace_bytes(nb, h, l) if d == 32 else
-                 lib().gmlm_attention_bwd_workspace_bytes(nb, h, l, l, d), qkv.device)
         # short-sequence path (one launch per (sequence, head): same condition as the C entry): the column sums of dqkv --
         # the bias gradient of the fused QKV projection that produced qkv -- come out of the kernel as well
-        rows = max_len if cu_seqlens is not None else l
         fused_db = want_db and ctx.short
         n_groups = 0 if groups is None else groups.numel() - 1
         part = db = None
@@ -777,19 +785,11 @@ class AttentionQKV(torch.autograd.Function):
             db = torch.empty(hd3, dtype=torch.float32, device=qkv.device)
         # q, k, v, dO in; dq, dk, dv out (+ o, o_lo on the streaming path, which forms delta from them)
         with _span("attn_bwd_d%d" % d, flops=2.5 * flops, bytes=(7 + (0 if ctx.short else 2)) * qkv.numel() // 3 * qkv.element_size()):
-            sd = ctx.sd
-            if d == 32:
-                check(lib().gmlm_attention_d32_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(gout), _ptr(lse), _ptr(kv_len), b, h,
-                                                   l, l, d, hd3, hd3, hd3, scale, p, seed, sd, _ptr(dq), _ptr(dk), _ptr(dv), hd3,
-                                                   hd3, hd3, _dt(qkv), _ptr(cu_seqlens), max_len, _ptr(ws), ws.numel(),
-                                                   _ptr(out_lo), _stream()),
-                      "gmlm_attention_d32_bwd")
-            else:
-                check(lib().gmlm_attention_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(gout), _ptr(lse), _ptr(kv_len), b, h,
-                                               l, l, d, hd3, hd3, hd3, scale, p, seed, sd, _ptr(dq), _ptr(dk), _ptr(dv), hd3, hd3,
-                                               hd3, _dt(qkv), _ptr(cu_seqlens), max_len, _ptr(ws), ws.numel(), _ptr(part), _ptr(db),
-                                               _ptr(out_lo), _ptr(groups), n_groups, _stream()),
-                      "gmlm_attention_bwd")
+            _attention_bwd(qkv.device, True, q=_ptr(q), k=_ptr(k), v=_ptr(v), out=_ptr(out), out_lo=_ptr(out_lo), dout=_ptr(gout),
+                           lse=_ptr(lse), kv_len=_ptr(kv_len), b=b, h=h, lq=l, lk=l, d=d, q_stride=hd3, k_stride=hd3, v_stride=hd3,
+                           scale=scale, dropout_p=p, seed=seed, seed_dev=ctx.sd, dq=_ptr(dq), dk=_ptr(dk), dv=_ptr(dv), dq_stride=hd3,
+                           dk_stride=hd3, dv_stride=hd3, dtype=_dt(qkv), cu_seqlens=_ptr(cu_seqlens), max_len=max_len,
+                           dbias_partial=_ptr(part), dbias=_ptr(db), seq_groups=_ptr(groups), num_groups=n_groups)
         dbs = ()
         if want_db:
             if db is None:
@@ -820,10 +820,10 @@ class AttentionBlock:
         out = torch.empty(b, lq, hd, dtype=q.dtype, device=q.device)
         lse = torch.empty(b, self.h, lq, dtype=torch.float32, device=q.device)
         with _span("attn_fwd_d%d" % d, flops=4.0 * b * self.h * lq * lk * d):
-            sd = _sd()
-            check(lib().gmlm_attention_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(kv_len), b, self.h, lq, lk, d, _rows_view(q, self.h, d),
-                                           _rows_view(k, self.h, d), _rows_view(v, self.h, d), self.scale, self.p, int(seed), sd,
-                                           _ptr(out), None, _ptr(lse), _dt(q), None, 0, None, 0, _stream()), "gmlm_attention_fwd")
+            _attention_fwd(q=_ptr(q), k=_ptr(k), v=_ptr(v), kv_len=_ptr(kv_len), b=b, h=self.h, lq=lq, lk=lk, d=d,
+                           q_stride=_rows_view(q, self.h, d), k_stride=_rows_view(k, self.h, d), v_stride=_rows_view(v, self.h, d),
+                           scale=self.scale, dropout_p=self.p, seed=int(seed), seed_dev=_sd(), out=_ptr(out), out_lo=None,
+                           lse=_ptr(lse), dtype=_dt(q))
         return out, lse
 
     def bwd(self, q, k, v, out, dout, lse, kv_len, seed, out_lo=None):
@@ -834,14 +834,13 @@ class AttentionBlock:
         dq = torch.empty(b, lq, hd, dtype=q.dtype, device=q.device)
         dk = torch.empty(b, lk, hd, dtype=q.dtype, device=q.device)
         dv = torch.empty(b, lk, hd, dtype=q.dtype, device=q.device)
-        ws = _ws(lib().gmlm_attention_bwd_workspace_bytes(b, self.h, lq, lk, d), q.device)
         out, dout, lse = out.contiguous(), dout.contiguous(), lse.contiguous()
         with _span("attn_bwd_d%d" % d, flops=10.0 * b * self.h * lq * lk * d):
-            sd = _sd()
-            check(lib().gmlm_attention_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(dout), _ptr(lse), _ptr(kv_len), b, self.h,
-                                           lq, lk, d, _rows_view(q, self.h, d), _rows_view(k, self.h, d), _rows_view(v, self.h, d),
-                                           self.scale, self.p, int(seed), sd, _ptr(dq), _ptr(dk), _ptr(dv), hd, hd, hd, _dt(q), None, 0,
-                                           _ptr(ws), ws.numel(), None, None, _ptr(out_lo), None, 0, _stream()), "gmlm_attention_bwd")
+            _attention_bwd(q.device, q=_ptr(q), k=_ptr(k), v=_ptr(v), out=_ptr(out), out_lo=_ptr(out_lo), dout=_ptr(dout),
+                           lse=_ptr(lse), kv_len=_ptr(kv_len), b=b, h=self.h, lq=lq, lk=lk, d=d, q_stride=_rows_view(q, self.h, d),
+                           k_stride=_rows_view(k, self.h, d), v_stride=_rows_view(v, self.h, d), scale=self.scale, dropout_p=self.p,
+                           seed=int(seed), seed_dev=_sd(), dq=_ptr(dq), dk=_ptr(dk), dv=_ptr(dv), dq_stride=hd, dk_stride=hd,
+                           dv_stride=hd, dtype=_dt(q))
         return dq, dk, dv
 
 

@@ -224,6 +224,9 @@ int gmlm_bias_res_layernorm_bwd(const void* dy, const void* x, const float* bias
  * q, k, v, out, out_lo, dout, dq, dk, dv are 16-byte aligned and every row stride is a multiple of 8 (bf16) / 4 (fp32)
  * elements, at least h*d and below 2^24.  b*h <= 65535, scale > 0, dropout_p in [0, 1) (forward and backward alike).
  * k and v are required when lk > 0.
+ * Order of the checks, here and in every other attention entry point (d128, d32, wide, causal): sizes, head dim, dtype, out_lo,
+ * layout (packed mode, seq_groups, lq == lk, GQA divisibility), dropout_p, scale, the work-item bound; then a call with nothing
+ * to do returns GMLM_OK; then the operands, the outputs and last the workspace.  The first failed check decides code and message.
  * kv_len: int32 [b] valid key count per sequence (NULL = all lk keys valid); keys >= kv_len[b]
  * are masked out exactly like the additive -inf padding mask of create_bidirectional_mask.
  * d in {64, 96}.  MFMA: bf16 32x32x16 for GMLM_BF16, f32 32x32x2 for GMLM_F32.
