@@ -20,7 +20,8 @@ import torch
 from torch.utils.checkpoint import checkpoint
 
 from . import ops
-from .nn import _Linear, _linear, _mm, _splitk_wgrad, attention_any_dim  # noqa: F401  (dense-layer functions live in nn.py)
+from .dense import _mm, _splitk_wgrad, encoder_operands  # noqa: F401  (_splitk_wgrad: tests/test_gpu_model.py imports it from here)
+from .nn import attention_any_dim
 
 # Head dims the encoder runs on attention kernels of their own, with the fused QKV buffer, the packed pass, the bucketed
 # layout and the recorded encoder / whole step (32: attn_d32.hip; 64 / 96: attn_kernels.hip and its siblings).  Every gate
@@ -63,61 +64,22 @@ def _layer_masters(layer):
 def prepare_weights(plm, cd, gemm_precision="native"):
     """One flat buffer in the compute dtype for all layers' GEMM weights, filled by ONE multi-tensor copy
     (Q/K/V rows land directly in the fused [3P, P] operand, so there is no concatenation either).
-    ``gemm_precision`` "bf16x3" (fp32 only): ``lw.w*`` then hold ``ops.SplitWeight`` objects, the two bf16 three-part forms of the
-    fused fp32 operand, split once here for all micro-batches; ``nn._mm`` picks the GEMM by the operand's type."""
-    if gemm_precision not in ("native", "bf16x3"):
-        raise ValueError(f"gemm_precision must be 'native' or 'bf16x3', got {gemm_precision!r}")
-    if gemm_precision == "bf16x3" and cd != torch.float32:
-        raise ValueError("gemm_precision='bf16x3' keeps fp32 storage: the compute dtype must be float32")
-    layers = list(plm.encoder.layer)
-    out, srcs, dsts = [], [], []
-    with torch.no_grad():
-        dev = layers[0].attention.self.query.weight.device if layers else None
-
-        def take(shape):
-            nonlocal off
-            n = 1
-            for d in shape:
-                n *= d
-            v = flat[off:off + n].view(shape)
-            off += padded(n)
-            return v
-
-        def padded(n):                                        # keep every operand 256-byte aligned
-            return (n + 127) // 128 * 128
-
-        total = 0
-        for layer in layers:
-            wq, bq, wo, wi, wo2 = _layer_masters(layer)
-            total += padded(sum(t.numel() for t in wq)) + padded(sum(t.numel() for t in bq)) + padded(wo.numel()) \
-                + padded(wi.numel()) + padded(wo2.numel())
-        flat = torch.empty(total, dtype=cd, device=dev)
-        off = 0
-        for layer in layers:
-            sa, so = layer.attention.self, layer.attention.output
-            wq, bq, wo, wi, wo2 = _layer_masters(layer)
-            lw = LayerWeights()
-            p = wq[0].shape[1]
-            lw.wqkv = take((sum(t.shape[0] for t in wq), p))
-            lw.bqkv = take((sum(t.shape[0] for t in bq),))
-            lw.wo, lw.wi, lw.wo2 = take(tuple(wo.shape)), take(tuple(wi.shape)), take(tuple(wo2.shape))
-            r = 0
-            for w_, b_ in zip(wq, bq):
-                dsts += [lw.wqkv[r:r + w_.shape[0]], lw.bqkv[r:r + w_.shape[0]]]
-                srcs += [w_.detach(), b_.detach()]
-                r += w_.shape[0]
-            dsts += [lw.wo, lw.wi, lw.wo2]
-            srcs += [wo.detach(), wi.detach(), wo2.detach()]
-            lw.m_qkv, lw.m_wo, lw.m_wi, lw.m_wo2 = tuple(wq) + tuple(bq), (wo,), (wi,), (wo2,)
-            lw.bo, lw.bi, lw.bo2 = so.dense.bias, layer.intermediate.dense.bias, layer.output.dense.bias
-            lw.ln1w, lw.ln1b = so.LayerNorm.weight, so.LayerNorm.bias
-            lw.ln2w, lw.ln2b = layer.output.LayerNorm.weight, layer.output.LayerNorm.bias
-            out.append(lw)
-        if dsts:
-            torch._foreach_copy_(dsts, srcs)
-        if gemm_precision == "bf16x3":
-            for lw in out:
-                lw.wqkv, lw.wo, lw.wi, lw.wo2 = (ops.SplitWeight(w) for w in (lw.wqkv, lw.wo, lw.wi, lw.wo2))
+    ``gemm_precision`` "bf16x3" (fp32 only): ``lw.w*`` then hold ``dense.SplitWeight`` objects, the two bf16 three-part forms of
+    the fused fp32 operand, split once here for all micro-batches; ``dense._mm`` picks the GEMM by the operand's type."""
+    out, specs = [], []
+    for i, layer in enumerate(plm.encoder.layer):
+        wq, bq, wo, wi, wo2 = _layer_masters(layer)
+        specs += [((i, "wqkv"), wq, 0), ((i, "bqkv"), bq, 0), ((i, "wo"), [wo], 0), ((i, "wi"), [wi], 0), ((i, "wo2"), [wo2], 0)]
+        so = layer.attention.output
+        lw = LayerWeights()
+        lw.m_qkv, lw.m_wo, lw.m_wi, lw.m_wo2 = tuple(wq) + tuple(bq), (wo,), (wi,), (wo2,)
+        lw.bo, lw.bi, lw.bo2 = so.dense.bias, layer.intermediate.dense.bias, layer.output.dense.bias
+        lw.ln1w, lw.ln1b = so.LayerNorm.weight, so.LayerNorm.bias
+        lw.ln2w, lw.ln2b = layer.output.LayerNorm.weight, layer.output.LayerNorm.bias
+        out.append(lw)
+    operands = encoder_operands(specs, cd, gemm_precision)
+    for i, lw in enumerate(out):
+        lw.wqkv, lw.bqkv, lw.wo, lw.wi, lw.wo2 = (operands[(i, k)] for k in ("wqkv", "bqkv", "wo", "wi", "wo2"))
     return out
 
 
@@ -150,23 +112,29 @@ def bert_encode(plm, input_ids: torch.Tensor, lens: torch.Tensor, cd: torch.dtyp
     probability 0 in every layer, padded query rows are computed but never read by the pooling.
     ``weights``: optional ``prepare_weights(plm, cd)`` result shared across micro-batches.
     """
-    cfg = plm.config
     emb = plm.embeddings
     b, l = input_ids.shape
     x = torch.nn.functional.embedding(input_ids.long(), emb.word_embeddings.weight)   # bit-exact row gather
     x = x + (emb.token_type_embeddings.weight[0] + emb.position_embeddings.weight[:l]).unsqueeze(0)
-    eps = cfg.layer_norm_eps
-    p_hidden = cfg.hidden_dropout_prob
-    p_attn = cfg.attention_probs_dropout_prob
-    h = ops.bias_res_layernorm(x.to(cd), None, None, emb.LayerNorm.weight, emb.LayerNorm.bias, eps, False, p_hidden, training)
+    return _encode_rows(plm, x.to(cd), lens, cd, training, gradient_checkpointing, weights)
+
+
+def _encode_rows(plm, x, lens, cd, training, gradient_checkpointing, weights, *packed):
+    """Embedding LayerNorm and the layers over the embedding rows ``x`` in ``cd`` ([B, L, P] with ``lens``, or [T, P] with
+    ``packed`` = the (cu_seqlens, max_len, pair_count, groups) of ``_layer``); a checkpointed layer is recomputed with the very
+    arguments it ran with."""
+    cfg = plm.config
+    emb = plm.embeddings
+    eps, p_hidden, p_attn = cfg.layer_norm_eps, cfg.hidden_dropout_prob, cfg.attention_probs_dropout_prob
+    h = ops.bias_res_layernorm(x, None, None, emb.LayerNorm.weight, emb.LayerNorm.bias, eps, False, p_hidden, training)
     heads = cfg.num_attention_heads
     if weights is None:
         weights = prepare_weights(plm, cd)
     for lw in weights:
         if gradient_checkpointing and training and torch.is_grad_enabled():
-            h = checkpoint(_layer, lw, h, lens, heads, training, p_hidden, p_attn, eps, use_reentrant=False)
+            h = checkpoint(_layer, lw, h, lens, heads, training, p_hidden, p_attn, eps, *packed, use_reentrant=False)
         else:
-            h = _layer(lw, h, lens, heads, training, p_hidden, p_attn, eps)
+            h = _layer(lw, h, lens, heads, training, p_hidden, p_attn, eps, *packed)
     return h
 
 
@@ -186,17 +154,7 @@ def bert_encode_packed(plm, token_ids: torch.Tensor, pos_ids: torch.Tensor, cu_s
     # word + type-0 + position rows in one pass (fp32 sums in torch's order, stored as cd); backward = segment sums by id
     x = ops.embed_sum(token_ids, pos_ids, emb.word_embeddings.weight, emb.position_embeddings.weight,
                       emb.token_type_embeddings.weight, cd)
-    eps, p_hidden, p_attn = cfg.layer_norm_eps, cfg.hidden_dropout_prob, cfg.attention_probs_dropout_prob
-    h = ops.bias_res_layernorm(x, None, None, emb.LayerNorm.weight, emb.LayerNorm.bias, eps, False, p_hidden, training)
-    if weights is None:
-        weights = prepare_weights(plm, cd)
-    for lw in weights:
-        if gradient_checkpointing and training and torch.is_grad_enabled():
-            h = checkpoint(_layer, lw, h, None, heads, training, p_hidden, p_attn, eps, cu_seqlens, max_len, pair_count, groups,
-                           use_reentrant=False)
-        else:
-            h = _layer(lw, h, None, heads, training, p_hidden, p_attn, eps, cu_seqlens, max_len, pair_count, groups)
-    return h
+    return _encode_rows(plm, x, None, cd, training, gradient_checkpointing, weights, cu_seqlens, max_len, pair_count, groups)
 
 
 # ---------------------------------------------------------------------------------------------

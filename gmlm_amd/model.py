@@ -21,9 +21,9 @@ import torch.nn as nn
 from torch.utils.checkpoint import checkpoint
 
 from . import bert, ops, qwen3
+from .dense import SPLITK_ROW_QUANTUM, _linear, check_gemm_precision, linear_specs, shadow_params, use_shadow
 from .graph import GraphCache, RelCSR
-from .nn import (GEMM_PRECISIONS, SPLITK_ROW_QUANTUM, CrossAttention, GraphNorm, MultiScaleFusion, RGCNConv, _linear, compute_dtype,
-                 cross_attention_specs, linear_specs, shadow_params, use_shadow)
+from .nn import CrossAttention, GraphNorm, MultiScaleFusion, RGCNConv, compute_dtype, cross_attention_specs
 
 logger = logging.getLogger(__name__)
 
@@ -109,8 +109,7 @@ class GraphTextLM(nn.Module):
                  compute_dtype: Optional[torch.dtype] = None, activation_checkpointing: bool = False,
                  plm_gradient_checkpointing: bool = False, gemm_precision: str = "native"):
         super().__init__()
-        if gemm_precision not in GEMM_PRECISIONS:
-            raise ValueError(f"gemm_precision must be one of {GEMM_PRECISIONS}, got {gemm_precision!r}")
+        check_gemm_precision(gemm_precision)
         if gemm_precision == "bf16x3" and compute_dtype not in (None, torch.float32):
             raise ValueError("gemm_precision='bf16x3' keeps fp32 storage and runs only the dense-layer GEMMs on the bf16 matrix "
                              f"pipe; it cannot be combined with compute_dtype={compute_dtype}")
@@ -155,8 +154,8 @@ class GraphTextLM(nn.Module):
 
         self.num_relations = num_relations
         self.compute_dtype = compute_dtype
-        # "bf16x3": fp32 storage everywhere, the dense layers that go through nn._linear / nn._mm as ONE bf16 GEMM of three times
-        # the depth with an fp32 result (ops.LinearBf16x3); "native": every GEMM in the compute dtype
+        # "bf16x3": fp32 storage everywhere, the dense layers that go through dense._linear / dense._mm as ONE bf16 GEMM of three times
+        # the depth with an fp32 result (dense.LinearBf16x3); "native": every GEMM in the compute dtype
         self.gemm_precision = gemm_precision
         self.activation_checkpointing = activation_checkpointing
         self.plm_gradient_checkpointing = plm_gradient_checkpointing
@@ -174,7 +173,7 @@ class GraphTextLM(nn.Module):
         # configuration the GEMM library is rarely run in ("streams")
         self.overlap_streams = False
         self._side_stream = None
-        self._gnn_shadow = None   # nn.ParamShadow of the last get_graph_embeddings call (compute-dtype operands of its dense layers)
+        self._gnn_shadow = None   # dense.ParamShadow of the last get_graph_embeddings call (compute-dtype operands of its dense layers)
         self._branch_stream = None  # side stream for the second cross-attention while a whole-step hipGraph is recorded (graphs.py)
         self._active_seen = None  # host copy / index tables of the last active-node mask TENSOR (reused while it is not written to)
         self._graphed = None      # gmlm_amd.graphs.GraphedStep: hipGraph recording of the GNN + head regions (capture_hip_graphs)
@@ -250,7 +249,7 @@ class GraphTextLM(nn.Module):
         run = (lambda k, x: checkpoint(self._block, k, x, csr, use_reentrant=False)) \
             if (self.activation_checkpointing and self.training and torch.is_grad_enabled()) else \
             (lambda k, x: self._block(k, x, csr))
-        # compute-dtype operands of this region's dense layers: one flat buffer, one multi-tensor copy (nn.ParamShadow); kept on
+        # compute-dtype operands of this region's dense layers: one flat buffer, one multi-tensor copy (dense.ParamShadow); kept on
         # the module so that a checkpoint recompute of a block (which runs in backward, outside this call) finds the same operands
         specs = linear_specs(self.residual_proj1, self.residual_proj2)
         for k in (1, 2, 3, 4) if self.gemm_precision == "native" else ():   # bf16x3: the root GEMMs stay native fp32
@@ -426,7 +425,7 @@ class GraphTextLM(nn.Module):
                     # lengths (sizes known without a device sync), token gather on the device
                     total = int(lh.sum())
                     # large batches: pad the token count to a multiple of 16 (of 112 = lcm(14, 16) once the weight-gradient GEMMs
-                    # slice by 14 or 16: nn._splitk_wgrad) with ONE dummy sequence of [PAD] tokens behind the real ones (never
+                    # slice by 14 or 16: dense._splitk_wgrad) with ONE dummy sequence of [PAD] tokens behind the real ones (never
                     # pooled, zero gradient): the split-K weight-gradient GEMMs then cut T into equal slices with no tail rows
                     # (a tail is one more tiny GEMM and a full pass over dW per weight: 2 x 48 launches per BERT-base step),
                     # and every GEMM sees an aligned row count

@@ -5,7 +5,7 @@
   reference state dict loads unchanged.
 * ``CrossAttention`` / ``MultiScaleFusion`` keep main.py:139-180's names and shapes.
 All arithmetic that is not a plain dense GEMM runs in libgmlm_hip.so (gmlm_amd.ops); dense
-projections go to hipBLASLt through ``torch.mm`` / ``F.linear``.
+projections go to hipBLASLt through ``torch.mm`` / ``F.linear`` (gmlm_amd.dense: operand shadows, ``_linear`` / ``_mm``).
 """
 from __future__ import annotations
 
@@ -17,6 +17,9 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
+# the dense-layer path lives in dense.py; these names stay reachable here (the NATIVE_WGRAD* knobs are set on dense itself)
+from .dense import (GEMM_PRECISIONS, SPLITK_ROW_QUANTUM, _SLICES_MEASURED, ParamShadow, SplitShadow, _Linear, _linear, _mm,  # noqa: F401
+                    _mm_f32, _native_wgrad_ok, _splitk_wgrad, active_shadow, linear_specs, shadow_params, use_shadow)
 from .graph import GraphCache, RelCSR
 
 _GRAPHS = GraphCache(capacity=8)
@@ -52,286 +55,6 @@ def _glorot(t: torch.Tensor) -> None:
     a = math.sqrt(6.0 / (t.size(-2) + t.size(-1)))
     with torch.no_grad():
         t.uniform_(-a, a)
-
-
-GEMM_PRECISIONS = ("native", "bf16x3")
-
-
-def _linear(x, weight, bias=None, gemm_precision="native"):
-    """x @ weight^T (+ bias) in x's dtype with autocast off (explicit precision policy).  Inside ``shadow_params`` the operands
-    come from the region's shadow and the gradients go to the fp32 masters directly; otherwise per-call casts.
-    ``gemm_precision`` "bf16x3" (fp32 ``x`` on the GPU): outside a shadow the weight is split for this call (ops.SplitWeight);
-    a shadow built for that mode already holds the split weights, whatever is passed here."""
-    sh = _SHADOW
-    if sh is not None and x.dtype == sh.dtype:
-        wc = sh.get(id(weight))
-        bc = sh.get(id(bias)) if bias is not None else None
-        if wc is not None and (bias is None or bc is not None):
-            return _mm(x, wc, bc, (weight,) + ((bias,) if bias is not None else ()))
-    if gemm_precision != "native":
-        if gemm_precision != "bf16x3":
-            raise ValueError(f"gemm_precision must be one of {GEMM_PRECISIONS}, got {gemm_precision!r}")
-        if x.dtype != torch.float32:
-            raise TypeError(f"gemm_precision='bf16x3' keeps fp32 storage; got {x.dtype} activations")
-        return _mm(x, ops.SplitWeight(weight), None if bias is None else bias.detach(),
-                   (weight,) + ((bias,) if bias is not None else ()))
-    with torch.autocast("cuda", enabled=False):
-        w = weight.to(x.dtype)
-        b = None if bias is None else bias.to(x.dtype)
-        return F.linear(x, w, b)
-
-
-_F32_OUT = [True]          # torch.bmm(..., out_dtype=float32) available (checked on first use)
-_F32_MM = [True]           # torch.mm(..., out_dtype=float32) likewise
-
-
-_SLICES_MEASURED = {(2304, 768): 14, (3072, 768): 14, (768, 3072): 14}
-SPLITK_ROW_QUANTUM = 112   # lcm(14, 16): a token count that is a multiple of it leaves no tail rows for either slice count
-# bf16 -> fp32 weight gradients at T >= NATIVE_WGRAD_MIN_T with N, K multiples of 256 and at least NATIVE_WGRAD_MIN_TILES
-# 256 x 256 output tiles run on the split-K kernel of libgmlm_hip.so (wgrad_kernels.hip) instead of the batched hipBLASLt
-# GEMM + ATen slice sum (MI355X, T = 91,712, tools/ubench/wgrad_native.py: 1.2-1.4x on every BERT-base weight).  The
-# BERT-mini weights (1-4 tiles) stay on the library path: alone 1.3x except 256 x 256 (90 vs 50 us), but the chameleon
-# whole-step graph, where they share the chip with the GNN branch, measured 6.41-6.44 vs 6.33 ms.  False = library path (A/B).
-NATIVE_WGRAD = True
-NATIVE_WGRAD_MIN_T = 16384
-NATIVE_WGRAD_MIN_TILES = 9
-
-
-def _native_wgrad_ok(dy2: torch.Tensor, x2: torch.Tensor, keep_fp32: bool) -> bool:
-    t, n = dy2.shape
-    k = x2.shape[1]
-    return (NATIVE_WGRAD and keep_fp32 and dy2.is_cuda and dy2.dtype == torch.bfloat16 and x2.dtype == torch.bfloat16
-            and t >= NATIVE_WGRAD_MIN_T and n % ops.WGRAD_TILE == 0 and k % ops.WGRAD_TILE == 0
-            and (n // ops.WGRAD_TILE) * (k // ops.WGRAD_TILE) >= NATIVE_WGRAD_MIN_TILES
-            and dy2.stride(1) == 1 and x2.stride(1) == 1 and dy2.stride(0) % 8 == 0 and x2.stride(0) % 8 == 0
-            and dy2.data_ptr() % 16 == 0 and x2.data_ptr() % 16 == 0)
-
-
-def _splitk_wgrad(dy2: torch.Tensor, x2: torch.Tensor, keep_fp32: bool = False) -> torch.Tensor:
-    """dW [N, K] = dy2^T [N, T] @ x2 [T, K] (returned in fp32 when ``keep_fp32``, else in dy2's dtype).  The reduction dim is the token count (10^4..10^5) while the
-    output is only a few 256x256 tiles, so one hipBLASLt call leaves most CUs idle; cutting T into S
-    slices (batched GEMM, fp32 partials) and adding them fills the chip (measured 1.5-2.7x on MI355X)."""
-    if _native_wgrad_ok(dy2, x2, keep_fp32):
-        return ops.wgrad_bf16(dy2, x2)
-    t, n = dy2.shape
-    k = x2.shape[1]
-    tiles = ((n + 255) // 256) * ((k + 255) // 256)
-    s = 1
-    if tiles < 128 and t >= 16384:                    # (node-level layers, t = a few thousand rows: one GEMM; slicing them left a tail GEMM + an add per weight)
-        import math
-        # measured on MI355X (tools/ubench/wgrad_shapes.py, T = 91,712): 16 slices is within 5 % of the best power of two for every
-        # BERT shape once T >= 64k; 14 fills the chip better for three of the four BERT-base weights (QKV 322 vs 415 us, FFN
-        # 440 vs 455 and 444 vs 447 us; the 768 x 768 output projection stays at 16: 128 vs 161 us)
-        s = _SLICES_MEASURED.get((n, k), 16) if t >= 65536 else min(16, max(1, 2 ** round(math.log2(200.0 / tiles))))
-    if s == 1:
-        if keep_fp32 and dy2.dtype != torch.float32 and _F32_MM[0]:
-            try:                                          # fp32 result straight out of the GEMM: no cast pass over dW
-                return torch.mm(dy2.t(), x2, out_dtype=torch.float32)
-            except (RuntimeError, TypeError):
-                _F32_MM[0] = False
-        dw = dy2.t() @ x2
-        return dw.float() if keep_fp32 else dw
-    # a packed batch has an arbitrary token count: S equal slices of floor(T/S) rows + a tail of < S rows
-    q = t // s
-    a = dy2[:s * q].view(s, q, n).transpose(1, 2)
-    b = x2[:s * q].view(s, q, k)
-    if _F32_OUT[0] and dy2.dtype != torch.float32:
-        try:
-            dw = torch.bmm(a, b, out_dtype=torch.float32).sum(0)
-        except (RuntimeError, TypeError):
-            _F32_OUT[0] = False
-            dw = torch.bmm(a, b).float().sum(0)
-    else:
-        dw = torch.bmm(a, b).float().sum(0)
-    if s * q < t:
-        dw += dy2[s * q:].t() @ x2[s * q:]         # < S rows: one tiny GEMM, added in fp32
-    return dw if keep_fp32 else dw.to(dy2.dtype)
-
-
-class _Linear(torch.autograd.Function):
-    """y = x @ wc^T (+ bc) on hipBLASLt with the cached compute-dtype operands ``wc`` / ``bc``; the gradients go
-    to the fp32 MASTER parameters (``masters`` = the weight(s) whose rows stack up to ``wc``, then the bias(es)
-    stacking up to ``bc``): split-K weight gradient and the bias column sum stay in fp32 end to end.
-    With ``residual`` the input is also returned as a second output for the residual branch, so that the two
-    gradients of ``x`` meet HERE and the data-gradient GEMM accumulates onto the residual one (beta = 1 in the
-    GEMM epilogue) instead of autograd running a separate add kernel."""
-
-    @staticmethod
-    def forward(ctx, x, wc, bc, residual, bias_grad, *masters):
-        """``bias_grad`` False: ``bc`` is added but its masters are not among ``masters`` (their gradient is produced
-        elsewhere: ops.AttentionQKV returns the fused QKV bias gradient itself, from inside its backward kernel)."""
-        ctx.save_for_backward(x, wc)
-        ctx.masters = masters
-        ctx.has_bias = bc is not None and bias_grad
-        ctx.n_w = len(masters) // 2 if ctx.has_bias else len(masters)
-        y = torch.nn.functional.linear(x, wc, bc)
-        return (y, x.view_as(x)) if residual else y
-
-    @staticmethod
-    def backward(ctx, dy, dxres=None):
-        x, wc = ctx.saved_tensors
-        masters, n_w = ctx.masters, ctx.n_w
-        dy2 = dy.reshape(-1, dy.shape[-1])
-        x2 = x.reshape(-1, x.shape[-1])
-        dx = None
-        if ctx.needs_input_grad[0]:
-            if dxres is None:
-                dx = (dy2 @ wc).view(x.shape)
-            else:
-                # the residual gradient buffer is ours alone (it was produced for this node): accumulate in place
-                dres2 = dxres.reshape(-1, x.shape[-1])
-                dx = (dres2.addmm_(dy2, wc) if dres2.is_contiguous() else torch.addmm(dres2, dy2, wc)).view(x.shape)
-        grads = [None] * len(masters)
-        need = ctx.needs_input_grad[5:]
-        if any(need[:n_w]):
-            dw = _splitk_wgrad(dy2, x2, keep_fp32=True)
-            for i, (m, g) in enumerate(zip(masters[:n_w], dw.split([m.shape[0] for m in masters[:n_w]], 0))):
-                if need[i]:
-                    grads[i] = g if g.dtype == m.dtype else g.to(m.dtype)
-        if ctx.has_bias and any(need[n_w:]):
-            db = ops.column_sum(dy2) if dy2.is_cuda and dy2.dtype in (torch.float32, torch.bfloat16) else dy2.sum(0, dtype=torch.float32)
-            for i, (m, g) in enumerate(zip(masters[n_w:], db.split([m.shape[0] for m in masters[n_w:]], 0))):
-                if need[n_w + i]:
-                    grads[n_w + i] = g if g.dtype == m.dtype else g.to(m.dtype)
-        return (dx, None, None, None, None, *grads)
-
-
-def _mm(x, wc, bc, masters, residual=False, bias_grad=True):
-    """``wc``: the compute-dtype copy of the weight, or its ``ops.SplitWeight`` (gemm_precision "bf16x3": the operand itself says
-    which GEMM runs, so a checkpoint recompute that is handed the same operands takes the same path)."""
-    with torch.autocast("cuda", enabled=False):
-        fn = ops.LinearBf16x3 if isinstance(wc, ops.SplitWeight) else _Linear
-        return fn.apply(x, wc, bc, residual, bias_grad, *masters)
-
-
-# ---------------------------------------------------------------------------------------------
-# Compute-dtype copies of fp32 master parameters: ONE flat buffer, ONE multi-tensor copy per region
-# ---------------------------------------------------------------------------------------------
-class ParamShadow:
-    """bf16 operands of a region's dense layers.  ``specs``: list of (key, [master tensors stacked along dim 0], pad_rows):
-    each entry becomes one contiguous [sum(rows) + pad_rows, ...] view of a flat zero-initialised buffer in ``dtype`` (the pad
-    rows stay zero: the first RGCN layer's root is padded to the 16-byte-aligned input width).  Filled by ONE
-    ``_foreach_copy_`` instead of a cast kernel per parameter; the layers hand their weight / bias gradients straight to the
-    fp32 masters (``_Linear``), so no cast kernels run in backward either."""
-
-    def __init__(self, specs, dtype, device):
-        total, plan = 0, []
-        for key, masters, pad in specs:
-            rows = sum(m.shape[0] for m in masters) + pad
-            tail = tuple(masters[0].shape[1:])
-            numel = rows
-            for d in tail:
-                numel *= d
-            plan.append((key, masters, (rows,) + tail, total, numel))
-            total += (numel + 127) // 128 * 128                    # 256-byte aligned operands
-        self.dtype = dtype
-        with torch.no_grad():
-            flat = torch.zeros(total, dtype=dtype, device=device)
-            self.flat = flat
-            self.views, dsts, srcs = {}, [], []
-            for key, masters, shape, off, numel in plan:
-                v = flat[off:off + numel].view(shape)
-                self.views[key] = v
-                r0 = 0
-                for m in masters:
-                    dsts.append(v[r0:r0 + m.shape[0]])
-                    srcs.append(m.detach())
-                    r0 += m.shape[0]
-            if dsts:
-                torch._foreach_copy_(dsts, srcs)
-
-    def get(self, key):
-        return self.views.get(key)
-
-    def record_stream(self, stream) -> None:
-        """The operands are also read by kernels on ``stream`` (a branch of a recorded step): keep the allocator from recycling
-        the buffer on its own stream while that branch still runs."""
-        if self.flat.is_cuda:
-            self.flat.record_stream(stream)
-
-
-class SplitShadow:
-    """The shadow of an fp32 region in gemm_precision "bf16x3": every 2-D entry of ``specs`` (a weight, or several stacked along
-    dim 0) as an ``ops.SplitWeight``, split ONCE per region call; every 1-D entry (a bias) as its fp32 values.  Looked up by the
-    same keys as ``ParamShadow`` and re-entered by a checkpoint recompute through ``use_shadow``.  The caller lists only the
-    parameters of layers that go through ``_linear`` / ``_mm``: what is not listed stays on the native fp32 path."""
-    dtype = torch.float32
-
-    def __init__(self, specs, device):
-        self.views = {}
-        with torch.no_grad():
-            for key, masters, pad in specs:
-                if pad:
-                    raise ValueError("bf16x3 shadow entries take no pad rows")
-                w = masters[0].detach() if len(masters) == 1 else torch.cat([m.detach() for m in masters], 0)
-                self.views[key] = ops.SplitWeight(w) if w.dim() == 2 else w
-
-    def get(self, key):
-        return self.views.get(key)
-
-    def record_stream(self, stream) -> None:
-        for v in self.views.values():
-            for t in ((v.w0, v.w1s) if isinstance(v, ops.SplitWeight) else (v,)):
-                if t.is_cuda:
-                    t.record_stream(stream)
-
-
-_SHADOW = None             # the ParamShadow / SplitShadow of the region that is running
-
-
-class shadow_params:
-    """``with shadow_params(specs, dtype, device):`` - the dense layers called inside find their compute-dtype operands in the
-    shadow (``_linear`` by ``id(weight)``); no-op for fp32 (the masters ARE the operands) unless ``gemm_precision`` is "bf16x3":
-    then the shadow holds the split weights (``SplitShadow``)."""
-
-    def __init__(self, specs, dtype, device, gemm_precision="native"):
-        self.args = (specs, dtype, device)
-        self.x3 = gemm_precision == "bf16x3"
-        self.prev = None
-
-    def __enter__(self):
-        global _SHADOW
-        self.prev = _SHADOW
-        specs, dtype, device = self.args
-        if self.x3 and dtype == torch.float32 and device.type == "cuda":
-            _SHADOW = SplitShadow(specs, device)
-        else:
-            _SHADOW = ParamShadow(specs, dtype, device) if (dtype != torch.float32 and device.type == "cuda") else None
-        return _SHADOW
-
-    def __exit__(self, *exc):
-        global _SHADOW
-        _SHADOW = self.prev
-        return False
-
-
-class use_shadow:
-    """Re-enter an existing shadow (a checkpoint recompute runs a block in backward, outside the region's ``with``)."""
-
-    def __init__(self, sh):
-        self.sh, self.prev = sh, None
-
-    def __enter__(self):
-        global _SHADOW
-        self.prev = _SHADOW
-        if _SHADOW is None:
-            _SHADOW = self.sh
-        return _SHADOW
-
-    def __exit__(self, *exc):
-        global _SHADOW
-        _SHADOW = self.prev
-        return False
-
-
-def linear_specs(*mods):
-    """Shadow entries of plain ``nn.Linear`` modules: weight under id(weight), bias under id(bias)."""
-    out = []
-    for m in mods:
-        out.append((id(m.weight), [m.weight], 0))
-        if m.bias is not None:
-            out.append((id(m.bias), [m.bias], 0))
-    return out
 
 
 class _RootAddmm(torch.autograd.Function):
@@ -457,8 +180,8 @@ class RGCNConv(nn.Module):
         reverse exchange ahead of the root GEMM's backward."""
         in_pad = x.shape[1] - self.in_channels
         n = csr.num_nodes
-        sh = _SHADOW
-        rootc = sh.get(id(self.root)) if (sh is not None and x.dtype == sh.dtype) else None
+        sh = active_shadow(x.dtype)
+        rootc = sh.get(id(self.root)) if sh is not None else None
         bc = sh.get(id(self.bias)) if rootc is not None else None
         with torch.autocast("cuda", enabled=False):
             w = self.relation_weights(csr, x.dtype, in_pad, reducer)
@@ -535,8 +258,8 @@ class CrossAttention(nn.Module):
         b, n, c = x.shape
         xq, yk = x.to(cd), y.to(cd)
         q = _linear(xq, self.q_proj.weight, self.q_proj.bias, gp)
-        sh = _SHADOW
-        wkv = sh.get(("kv_w", id(self))) if (sh is not None and yk.dtype == sh.dtype) else None
+        sh = active_shadow(yk.dtype)
+        wkv = sh.get(("kv_w", id(self))) if sh is not None else None
         if wkv is not None:                                           # fused K|V operand straight from the region's shadow
             kv = _mm(yk, wkv, sh.get(("kv_b", id(self))),
                      (self.k_proj.weight, self.v_proj.weight, self.k_proj.bias, self.v_proj.bias))
@@ -687,16 +410,6 @@ class _ScaledProjectionCat(torch.autograd.Function):
             d_weights = (onehot @ colsum + bstack @ gsum).to(weights.dtype)
             d_bs = list((weights.float().view(-1, 1) * gsum.view(1, -1)).unbind(0))
         return (d_weights, None, None, None, *d_embs, *d_ws, *d_bs)
-
-
-def _mm_f32(a, b):
-    """a [N, K] @ b [P, K]^T with an fp32 result straight out of the GEMM when the operands are 16-bit."""
-    if a.dtype != torch.float32 and _F32_MM[0]:
-        try:
-            return torch.mm(a, b.t(), out_dtype=torch.float32)
-        except (RuntimeError, TypeError):
-            _F32_MM[0] = False
-    return (a @ b.t()).float()
 
 
 class MultiScaleFusion(nn.Module):

@@ -244,118 +244,6 @@ def split_bf16x3(x: torch.Tensor, order: int, stacked: bool = False, part_rows: 
     return out
 
 
-class SplitWeight:
-    """The two bf16x3 forms of one fp32 weight ``w`` [N, K], split once and used by every call of a step: ``w0`` [N, 3 K'] =
-    (hi, lo, hi) side by side for the forward GEMM, ``w1s`` [3 N', K'] = (hi, hi, lo) stacked for the data-gradient GEMM
-    (K', N' = K, N rounded up to 8; the pad rows and columns are zeros)."""
-    __slots__ = ("w0", "w1s", "n", "k")
-
-    def __init__(self, w: torch.Tensor):
-        with torch.no_grad():
-            w = w.detach()
-            self.n, self.k = w.shape
-            self.w0 = split_bf16x3(w, 0)
-            self.w1s = split_bf16x3(w, 1, stacked=True, part_rows=_up8(self.n))
-
-    @property
-    def shape(self):
-        return (self.n, self.k)
-
-
-_ADDMM_F32 = [True]        # torch.addmm(fp32, bf16, bf16, out_dtype=float32) available (checked on first use)
-
-
-def _mm_f32_out(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
-    """bf16 a @ b with the fp32 result straight out of the GEMM.  No fallback: a bf16 GEMM output would round away everything
-    the three-product form gains."""
-    try:
-        return torch.mm(a, b, out_dtype=torch.float32)
-    except TypeError as e:
-        raise _lib.GmlmHipError("gemm_precision='bf16x3' needs torch.mm(..., out_dtype=torch.float32) (bf16 operands, fp32 "
-                                "result); this PyTorch does not have it") from e
-
-
-class LinearBf16x3(torch.autograd.Function):
-    """y = x @ w^T (+ bc) for fp32 ``x`` [..., K] and a ``SplitWeight`` of the fp32 weight [N, K], every GEMM on the bf16 matrix
-    pipe with fp32 accumulation and an fp32 result; the interface and the gradient routing are those of ``nn._Linear``
-    (``masters``, ``residual``, ``bias_grad``).
-      forward          X1 = split(x, hi hi lo) [T, 3K'];  y = X1 @ w0^T
-      data gradient    DY0 = split(dy, hi lo hi) [T, 3N'];  dx = DY0 @ w1s
-      weight gradient  no further split: the contiguous [T, 3N'] / [T, 3K'] buffers viewed as [3T, N'] / [3T, K'] pair their
-                       rows (hi, lo, hi) against (hi, hi, lo);  dW = DY0.view(3T, N')^T @ X1.view(3T, K') (split-K kernel K11
-                       when 3T >= 16,384 and N', K' are multiples of 256, else the library)
-    X1 (6 bytes per element) is what is saved for backward, not x."""
-
-    @staticmethod
-    def forward(ctx, x, sw, bc, residual, bias_grad, *masters):
-        if x.dtype != torch.float32:
-            raise TypeError(f"bf16x3 dense layers take float32 activations, got {x.dtype}")
-        x2 = x.reshape(-1, x.shape[-1])
-        if x2.shape[1] != sw.k:
-            raise ValueError(f"bf16x3 linear: input width {x2.shape[1]} != weight width {sw.k}")
-        x1 = split_bf16x3(x2, 1)
-        y = _mm_f32_out(x1, sw.w0.t())
-        if bc is not None:
-            y.add_(bc)
-        ctx.save_for_backward(x1, sw.w1s)
-        ctx.masters, ctx.n, ctx.k, ctx.xshape = masters, sw.n, sw.k, x.shape
-        ctx.has_bias = bc is not None and bias_grad
-        ctx.n_w = len(masters) // 2 if ctx.has_bias else len(masters)
-        y = y.view(*x.shape[:-1], sw.n)
-        return (y, x.view_as(x)) if residual else y
-
-    @staticmethod
-    def backward(ctx, dy, dxres=None):
-        from . import nn
-        x1, w1s = ctx.saved_tensors
-        masters, n_w, n, k = ctx.masters, ctx.n_w, ctx.n, ctx.k
-        dy2 = dy.reshape(-1, n)
-        need = ctx.needs_input_grad[5:]
-        dy0 = split_bf16x3(dy2, 0) if (ctx.needs_input_grad[0] or any(need[:n_w])) else None
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dres2 = None if dxres is None else dxres.reshape(-1, k)
-            if dres2 is not None and dres2.is_contiguous() and w1s.shape[1] == k and _ADDMM_F32[0]:
-                # the residual gradient buffer is ours alone (it was produced for this node): accumulate in the GEMM epilogue
-                try:
-                    dx = torch.addmm(dres2, dy0, w1s, out_dtype=torch.float32, out=dres2)
-                except (RuntimeError, TypeError):
-                    _ADDMM_F32[0] = False
-            if dx is None:
-                dx = _mm_f32_out(dy0, w1s)
-                if dx.shape[1] != k:
-                    dx = dx[:, :k]
-                if dres2 is not None:
-                    dx = dres2.add_(dx) if dres2.is_contiguous() else dres2 + dx
-            dx = dx.reshape(ctx.xshape)
-        grads = [None] * len(masters)
-        if any(need[:n_w]):
-            t = x1.shape[0]
-            dw = nn._splitk_wgrad(dy0.view(3 * t, -1), x1.view(3 * t, -1), keep_fp32=True)     # [N', K']
-            if not (nn._F32_MM[0] and nn._F32_OUT[0]):
-                # that function falls back to a bf16 GEMM output where the library refuses the fp32 one: fine for bf16 operands
-                # of the bf16 path, but here it would round away what the three-product form gains
-                raise _lib.GmlmHipError("gemm_precision='bf16x3': the GEMM library refused an fp32 result from bf16 operands")
-            if dw.shape != (n, k):
-                dw = dw[:n, :k]
-            for i, (m, g) in enumerate(zip(masters[:n_w], dw.split([m.shape[0] for m in masters[:n_w]], 0))):
-                if need[i]:
-                    grads[i] = g if g.dtype == m.dtype else g.to(m.dtype)
-        if ctx.has_bias and any(need[n_w:]):
-            db = column_sum(dy2)
-            for i, (m, g) in enumerate(zip(masters[n_w:], db.split([m.shape[0] for m in masters[n_w:]], 0))):
-                if need[n_w + i]:
-                    grads[n_w + i] = g if g.dtype == m.dtype else g.to(m.dtype)
-        return (dx, None, None, None, None, *grads)
-
-
-def mm_bf16x3(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
-    """a [M, K] @ b [N, K]^T in fp32 from two fp32 matrices on the bf16 matrix pipe (three-product form: relative error
-    ~ 3 * 2^-16 per entry against 2^-8.5 for plain bf16 operands); differentiable in both."""
-    with torch.autocast("cuda", enabled=False):
-        return LinearBf16x3.apply(a, SplitWeight(b), None, False, True, b)
-
-
 # ---------------------------------------------------------------------------------------------
 # gradient clipping + AdamW as one multi-tensor step (include/gmlm_hip_optim.h; the tables are built by optim.FusedAdamW)
 # ---------------------------------------------------------------------------------------------

@@ -17,7 +17,7 @@ import torch
 from torch.utils.checkpoint import checkpoint
 
 from . import ops
-from .nn import _mm
+from .dense import _mm, encoder_operands
 
 
 def _sliding_window_in_use(cfg) -> bool:
@@ -98,7 +98,7 @@ def rope_table(cfg, max_len: int, device) -> torch.Tensor:
 
 class LayerWeights:
     """Per-forward view of one Qwen3DecoderLayer: the GEMM operands in the compute dtype (fused ``wqkv`` [q|k|v] and ``wgu``
-    [gate|up], ``wo``, ``wdown``; no autograd history) next to the fp32 masters their gradients go to (``nn._mm``)."""
+    [gate|up], ``wo``, ``wdown``; no autograd history) next to the fp32 masters their gradients go to (``dense._mm``)."""
     __slots__ = ("wqkv", "wo", "wgu", "wdown", "m_qkv", "m_wo", "m_gu", "m_down", "ln1", "ln2", "qn", "kn")
 
 
@@ -111,53 +111,19 @@ def _layer_masters(layer):
 def prepare_weights(plm, cd, gemm_precision="native"):
     """One flat buffer in the compute dtype for all layers' GEMM weights, filled by ONE multi-tensor copy (Q/K/V rows land
     directly in the fused [(hq + 2 hkv) * 128, P] operand, gate / up rows in the fused [2 I, P] one).
-    ``gemm_precision`` "bf16x3" (fp32 only): the four operands become ``ops.SplitWeight`` objects (see bert.prepare_weights)."""
-    if gemm_precision not in ("native", "bf16x3"):
-        raise ValueError(f"gemm_precision must be 'native' or 'bf16x3', got {gemm_precision!r}")
-    if gemm_precision == "bf16x3" and cd != torch.float32:
-        raise ValueError("gemm_precision='bf16x3' keeps fp32 storage: the compute dtype must be float32")
-    layers = list(plm.layers)
-    out, srcs, dsts = [], [], []
-    padded = lambda n: (n + 127) // 128 * 128                 # keep every operand 256-byte aligned
-    with torch.no_grad():
-        dev = layers[0].self_attn.q_proj.weight.device if layers else None
-        total = 0
-        for layer in layers:
-            wq, wo, wgu, wd = _layer_masters(layer)
-            total += padded(sum(t.numel() for t in wq)) + padded(wo.numel()) + padded(sum(t.numel() for t in wgu)) + padded(wd.numel())
-        flat = torch.empty(total, dtype=cd, device=dev)
-        off = 0
-
-        def take(rows, cols):
-            nonlocal off
-            v = flat[off:off + rows * cols].view(rows, cols)
-            off += padded(rows * cols)
-            return v
-
-        for layer in layers:
-            wq, wo, wgu, wd = _layer_masters(layer)
-            lw = LayerWeights()
-            lw.wqkv = take(sum(t.shape[0] for t in wq), wq[0].shape[1])
-            lw.wo = take(*wo.shape)
-            lw.wgu = take(sum(t.shape[0] for t in wgu), wgu[0].shape[1])
-            lw.wdown = take(*wd.shape)
-            for fused, parts in ((lw.wqkv, wq), (lw.wgu, wgu)):
-                r = 0
-                for w_ in parts:
-                    dsts.append(fused[r:r + w_.shape[0]])
-                    srcs.append(w_.detach())
-                    r += w_.shape[0]
-            dsts += [lw.wo, lw.wdown]
-            srcs += [wo.detach(), wd.detach()]
-            lw.m_qkv, lw.m_wo, lw.m_gu, lw.m_down = tuple(wq), (wo,), tuple(wgu), (wd,)
-            lw.ln1, lw.ln2 = layer.input_layernorm.weight, layer.post_attention_layernorm.weight
-            lw.qn, lw.kn = layer.self_attn.q_norm.weight, layer.self_attn.k_norm.weight
-            out.append(lw)
-        if dsts:
-            torch._foreach_copy_(dsts, srcs)
-        if gemm_precision == "bf16x3":
-            for lw in out:
-                lw.wqkv, lw.wo, lw.wgu, lw.wdown = (ops.SplitWeight(w) for w in (lw.wqkv, lw.wo, lw.wgu, lw.wdown))
+    ``gemm_precision`` "bf16x3" (fp32 only): the four operands become ``dense.SplitWeight`` objects (see bert.prepare_weights)."""
+    out, specs = [], []
+    for i, layer in enumerate(plm.layers):
+        wq, wo, wgu, wd = _layer_masters(layer)
+        specs += [((i, "wqkv"), wq, 0), ((i, "wo"), [wo], 0), ((i, "wgu"), wgu, 0), ((i, "wdown"), [wd], 0)]
+        lw = LayerWeights()
+        lw.m_qkv, lw.m_wo, lw.m_gu, lw.m_down = tuple(wq), (wo,), tuple(wgu), (wd,)
+        lw.ln1, lw.ln2 = layer.input_layernorm.weight, layer.post_attention_layernorm.weight
+        lw.qn, lw.kn = layer.self_attn.q_norm.weight, layer.self_attn.k_norm.weight
+        out.append(lw)
+    operands = encoder_operands(specs, cd, gemm_precision)
+    for i, lw in enumerate(out):
+        lw.wqkv, lw.wo, lw.wgu, lw.wdown = (operands[(i, k)] for k in ("wqkv", "wo", "wgu", "wdown"))
     return out
 
 
@@ -185,18 +151,24 @@ def qwen3_encode(plm, input_ids: torch.Tensor, lens: torch.Tensor, cd: torch.dty
     b, l = input_ids.shape
     if l > cfg.max_position_embeddings:
         raise ValueError(f"sequence length {l} exceeds max_position_embeddings {cfg.max_position_embeddings}")
+    x = torch.nn.functional.embedding(input_ids.long(), plm.embed_tokens.weight).to(cd)   # bit-exact row gather
+    return _encode_rows(plm, x, lens, rope_table(cfg, l, x.device), cd, training, gradient_checkpointing, weights)
+
+
+def _encode_rows(plm, x, lens, cs, cd, training, gradient_checkpointing, weights, *packed):
+    """The layers and the final norm over the embedding rows ``x`` ([B, L, P] with ``lens``, or [T, P] with ``packed`` = the one
+    trailing argument of ``_layer``); a checkpointed layer is recomputed with the very arguments it ran with."""
+    cfg = plm.config
     hq, hkv = cfg.num_attention_heads, cfg.num_key_value_heads
     eps, scale = cfg.rms_norm_eps, head_dim(cfg) ** -0.5
-    x = torch.nn.functional.embedding(input_ids.long(), plm.embed_tokens.weight).to(cd)   # bit-exact row gather
-    cs = rope_table(cfg, l, x.device)
     if weights is None:
         weights = prepare_weights(plm, cd)
     stream, branch = x, None
     for lw in weights:
         if gradient_checkpointing and training and torch.is_grad_enabled():
-            stream, branch = checkpoint(_layer, lw, stream, branch, lens, cs, hq, hkv, scale, eps, use_reentrant=False)
+            stream, branch = checkpoint(_layer, lw, stream, branch, lens, cs, hq, hkv, scale, eps, *packed, use_reentrant=False)
         else:
-            stream, branch = _layer(lw, stream, branch, lens, cs, hq, hkv, scale, eps)
+            stream, branch = _layer(lw, stream, branch, lens, cs, hq, hkv, scale, eps, *packed)
     return ops.add_rmsnorm(stream, branch, plm.norm.weight, eps)[1]
 
 
@@ -213,17 +185,6 @@ def qwen3_encode_packed(plm, tok: torch.Tensor, pos: torch.Tensor, cu_seqlens: t
         raise ValueError(f"sequence length {max_len} exceeds max_position_embeddings {cfg.max_position_embeddings}")
     if tok.dim() != 1 or pos.shape != tok.shape:
         raise ValueError("packed token ids and positions must be [T] tensors of one size")
-    hq, hkv = cfg.num_attention_heads, cfg.num_key_value_heads
-    eps, scale = cfg.rms_norm_eps, head_dim(cfg) ** -0.5
     x = torch.nn.functional.embedding(tok.long(), plm.embed_tokens.weight).to(cd)   # bit-exact row gather
     cs = rope_table(cfg, max_len, x.device)
-    packed = (pos.to(torch.int32), cu_seqlens, max_len)
-    if weights is None:
-        weights = prepare_weights(plm, cd)
-    stream, branch = x, None
-    for lw in weights:
-        if gradient_checkpointing and training and torch.is_grad_enabled():
-            stream, branch = checkpoint(_layer, lw, stream, branch, None, cs, hq, hkv, scale, eps, packed, use_reentrant=False)
-        else:
-            stream, branch = _layer(lw, stream, branch, None, cs, hq, hkv, scale, eps, packed)
-    return ops.add_rmsnorm(stream, branch, plm.norm.weight, eps)[1]
+    return _encode_rows(plm, x, None, cs, cd, training, gradient_checkpointing, weights, (pos.to(torch.int32), cu_seqlens, max_len))

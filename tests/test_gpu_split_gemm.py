@@ -1,4 +1,4 @@
-"""The bf16x3 split kernel (gmlm::split3, include/gmlm_hip_split.h) bit for bit against torch on the CPU, and ops.mm_bf16x3
+"""The bf16x3 split kernel (gmlm::split3, include/gmlm_hip_split.h) bit for bit against torch on the CPU, and dense.mm_bf16x3
 (forward, data gradient, weight gradient) against float64 with the elementwise bound that follows from the construction:
 
     |err_ij| <= (3 * 2^-16 + K' * 2^-23) * (|A| |B|)_ij
@@ -161,12 +161,12 @@ def rel_l2(got, ref):
 
 
 def run_mm(dev, m, k, n, seed):
-    from gmlm_amd import ops
+    from gmlm_amd import dense
     g = torch.Generator().manual_seed(seed)
     a = torch.randn(m, k, generator=g).to(dev).requires_grad_(True)
     b = (torch.randn(n, k, generator=g) * 0.5).to(dev).requires_grad_(True)
     dy = torch.randn(m, n, generator=g).to(dev)
-    y = ops.mm_bf16x3(a, b)
+    y = dense.mm_bf16x3(a, b)
     y.backward(dy)
     return a, b, dy, y.detach()
 
@@ -204,7 +204,7 @@ def test_mm_bf16x3_forward_dx_dw_vs_float64(dev, m, k, n):
 def test_weight_gradient_through_the_split_k_kernel(dev, t, native):
     """3T = 16,512 >= 16,384 with N = K = 768: the viewed [3T, .] operands reach the split-K HIP kernel (K11) unchanged;
     3T = 16,320 stays on the library path.  Same bound, K' = 3T."""
-    from gmlm_amd import nn, ops
+    from gmlm_amd import dense, nn, ops
     n = k = 768
     g = torch.Generator().manual_seed(t)
     a = (torch.randn(t, k, generator=g) * 0.5).to(dev).requires_grad_(True)
@@ -213,7 +213,7 @@ def test_weight_gradient_through_the_split_k_kernel(dev, t, native):
     x1, dy0 = ops.split_bf16x3(a.detach(), 1), ops.split_bf16x3(dy, 0)
     assert x1.shape == (t, 3 * k) and dy0.shape == (t, 3 * n)
     assert nn._native_wgrad_ok(dy0.view(3 * t, n), x1.view(3 * t, k), True) is native
-    y = ops.mm_bf16x3(a, b)
+    y = dense.mm_bf16x3(a, b)
     ran = kernels_run(lambda: y.backward(dy))
     assert any(r.startswith("wgrad_bf16_kernel") for r in ran) is native, sorted(ran)
     assert any(r.startswith("split3::split_rows_kernel<0>") for r in ran), sorted(ran)
@@ -227,15 +227,47 @@ def test_weight_gradient_through_the_split_k_kernel(dev, t, native):
     assert worst <= 1.0 and e3 <= e1 / 32
 
 
+def test_mm_with_a_split_weight_is_this_sequence_of_primitives(dev):
+    """dense._mm with a SplitWeight at T, K, N = 40, 20, 16 (K' = 24: pad columns in both operands, the [:n, :k] cut of dW and
+    the column cut of dx), the weight and the bias each stacked from two 8-row masters, residual output: the output and every
+    gradient bit for bit equal to the split kernel, torch.mm with an fp32 result and the column-sum kernel called in that order."""
+    from gmlm_amd import dense, ops
+    t, k, n = 40, 20, 16
+    g = torch.Generator().manual_seed(40)
+    x = torch.randn(t, k, generator=g).to(dev).requires_grad_(True)
+    masters = [p.to(dev).requires_grad_(True) for p in (torch.randn(8, k, generator=g), torch.randn(8, k, generator=g),
+                                                        torch.randn(8, generator=g), torch.randn(8, generator=g))]
+    dy, dres = torch.randn(t, n, generator=g).to(dev), torch.randn(t, k, generator=g).to(dev)
+    w = torch.cat([m.detach() for m in masters[:2]], 0)
+    bc = torch.cat([m.detach() for m in masters[2:]], 0)
+    sw = dense.SplitWeight(w)
+    w0, w1s = ops.split_bf16x3(w, 0), ops.split_bf16x3(w, 1, stacked=True, part_rows=n)
+    assert sw.shape == (n, k) and torch.equal(sw.w0, w0) and torch.equal(sw.w1s, w1s) and w1s.shape == (3 * n, 24)
+
+    y, xres = dense._mm(x, sw, bc, masters, residual=True)
+    assert xres._base is x and xres.data_ptr() == x.data_ptr()
+    torch.autograd.backward([y, xres], [dy, dres.clone()])
+
+    f32 = dict(out_dtype=torch.float32)
+    x1 = ops.split_bf16x3(x.detach(), 1)                                       # [T, 3 K'] (hi, hi, lo)
+    assert torch.equal(y, torch.mm(x1, w0.t(), **f32).add_(bc))
+    dy0 = ops.split_bf16x3(dy, 0)                                              # [T, 3 N'] (hi, lo, hi)
+    assert torch.equal(x.grad, dres + torch.mm(dy0, w1s, **f32)[:, :k])
+    dw = torch.mm(dy0.view(3 * t, n).t(), x1.view(3 * t, 24), **f32)[:n, :k]
+    db = ops.column_sum(dy)
+    for got, want in zip([m.grad for m in masters], [dw[:8], dw[8:], db[:8], db[8:]]):
+        assert got.dtype == torch.float32 and torch.equal(got, want)
+
+
 def test_inf_and_nan_stay_in_their_rows(dev):
     """One infinity and one NaN in x: exactly their rows of y stop being finite, nothing else.  (The row of the infinity holds
     infinities where w_hi and w_lo of that column agree in sign and NaN where they do not: inf * w_hi + inf * w_lo.)"""
-    from gmlm_amd import ops
+    from gmlm_amd import dense
     g = torch.Generator().manual_seed(8)
     x = torch.randn(8, 24, generator=g)
     w = torch.randn(16, 24, generator=g)
     x[2, 5], x[5, 7] = float("inf"), float("nan")
-    y = ops.mm_bf16x3(x.to(dev), w.to(dev)).cpu()
+    y = dense.mm_bf16x3(x.to(dev), w.to(dev)).cpu()
     finite = torch.isfinite(y)
     assert not bool(finite[2].any()) and bool(torch.isnan(y[5]).all())
     keep = [0, 1, 3, 4, 6, 7]

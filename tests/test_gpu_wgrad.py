@@ -3,7 +3,7 @@ the bf16 operands, at the BERT-base and BERT-mini shapes; determinism, hipGraph 
 import pytest
 import torch
 
-from gmlm_amd import nn, ops
+from gmlm_amd import dense, nn, ops
 
 pytestmark = pytest.mark.gpu
 
@@ -164,8 +164,8 @@ def test_wgrad_unsupported_falls_back(dev, case):
 def test_wgrad_switch_selects_library_path(dev):
     dy, x = _operands(dev, 16384, 768, 768, 5)
     try:
-        nn.NATIVE_WGRAD = False
+        dense.NATIVE_WGRAD = False
         assert not nn._native_wgrad_ok(dy, x, True)
         _check(nn._splitk_wgrad(dy, x, keep_fp32=True), dy, x)
     finally:
-        nn.NATIVE_WGRAD = True
+        dense.NATIVE_WGRAD = True

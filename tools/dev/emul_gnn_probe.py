@@ -59,8 +59,8 @@ with torch.no_grad():
     ymix = E.r(F.gelu(O.graph_norm(z.float().cpu(), on.weight, on.bias, on.mean_scale, on.eps)))
     cmp("y (HIP z, CPU norm+gelu)", y, ymix)
     # residual
-    x1 = (y.float() + gmlm_amd.nn._linear(x0[:, :f_in], m.residual_proj1.weight, m.residual_proj1.bias).float()).to(torch.bfloat16)
+    x1 = (y.float() + gmlm_amd.dense._linear(x0[:, :f_in], m.residual_proj1.weight, m.residual_proj1.bias).float()).to(torch.bfloat16)
     x1e = E.r(ye + E.lin(x0e[:, :f_in], om.residual_proj1.weight, om.residual_proj1.bias))
     cmp("x1", x1, x1e)
-    lin_h = gmlm_amd.nn._linear(x0[:, :f_in], m.residual_proj1.weight, m.residual_proj1.bias)
+    lin_h = gmlm_amd.dense._linear(x0[:, :f_in], m.residual_proj1.weight, m.residual_proj1.bias)
     cmp("residual_proj1 out", lin_h, E.lin(x0e[:, :f_in], om.residual_proj1.weight, om.residual_proj1.bias))

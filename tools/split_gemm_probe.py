@@ -1,7 +1,7 @@
 """gemm_precision="bf16x3" against native fp32 (and plain bf16, for scale) on one device, in one process.
 
 (a) per shape: the four BERT-base dense layers at T = 91,712 tokens, forward / data gradient / weight gradient each:
-      native fp32   torch.mm on fp32 operands (weight gradient: nn._splitk_wgrad, what the fp32 path runs)
+      native fp32   torch.mm on fp32 operands (weight gradient: dense._splitk_wgrad, what the fp32 path runs)
       bf16x3        the split of the activation or incoming gradient (gmlm::split3) + ONE depth-3K bf16 GEMM with an fp32 result;
                     the weight gradient reuses the two split buffers as [3T, .] views (no further split).  The weight's own split
                     happens once per step and is listed on its own line
@@ -57,7 +57,7 @@ def alternate(sides, rounds, reps):
 
 
 def per_shape(dev, t, rounds):
-    from gmlm_amd import nn, ops
+    from gmlm_amd import dense, ops
     shapes = {"qkv": (2304, 768), "attn_out": (768, 768), "ffn_in": (3072, 768), "ffn_out": (768, 3072)}
     g = torch.Generator(device=dev).manual_seed(0)
     res = {}
@@ -66,7 +66,7 @@ def per_shape(dev, t, rounds):
         w = torch.randn(n, k, device=dev, generator=g) * k ** -0.5
         dy = torch.randn(t, n, device=dev, generator=g)
         xb, wb, dyb = x.bfloat16(), w.bfloat16(), dy.bfloat16()
-        sw = ops.SplitWeight(w)
+        sw = dense.SplitWeight(w)
         x1, dy0 = ops.split_bf16x3(x, 1), ops.split_bf16x3(dy, 0)
         f32 = dict(out_dtype=torch.float32)
         r = {"N": n, "K": k, "T": t, "GFLOP": round(2.0 * t * n * k / 1e9, 1)}
@@ -79,11 +79,11 @@ def per_shape(dev, t, rounds):
                                            "bf16x3_gemm_only": lambda: torch.mm(dy0, sw.w1s, **f32),
                                            "bf16": lambda: torch.mm(dyb, wb)}, rounds, 5)
         v_dy, v_x = dy0.view(3 * t, n), x1.view(3 * t, k)
-        r["weight_gradient_ms"] = alternate({"fp32": lambda: nn._splitk_wgrad(dy, x, keep_fp32=True),
-                                             "bf16x3": lambda: nn._splitk_wgrad(v_dy, v_x, keep_fp32=True),
-                                             "bf16": lambda: nn._splitk_wgrad(dyb, xb, keep_fp32=True)}, rounds, 5)
-        r["weight_gradient_on_split_k_kernel"] = bool(nn._native_wgrad_ok(v_dy, v_x, True))
-        r["weight_split_both_forms_ms"] = stat([ev_ms(lambda: ops.SplitWeight(w), 5) for _ in range(rounds)])
+        r["weight_gradient_ms"] = alternate({"fp32": lambda: dense._splitk_wgrad(dy, x, keep_fp32=True),
+                                             "bf16x3": lambda: dense._splitk_wgrad(v_dy, v_x, keep_fp32=True),
+                                             "bf16": lambda: dense._splitk_wgrad(dyb, xb, keep_fp32=True)}, rounds, 5)
+        r["weight_gradient_on_split_k_kernel"] = bool(dense._native_wgrad_ok(v_dy, v_x, True))
+        r["weight_split_both_forms_ms"] = stat([ev_ms(lambda: dense.SplitWeight(w), 5) for _ in range(rounds)])
         tot = {s: sum(r[p][s]["median"] for p in ("forward_ms", "data_gradient_ms", "weight_gradient_ms")) for s in ("fp32", "bf16x3", "bf16")}
         r["three_gemms_ms"] = {s: round(v, 3) for s, v in tot.items()}
         r["fp32_over_bf16x3"] = round(tot["fp32"] / tot["bf16x3"], 2)

@@ -1,6 +1,6 @@
-"""Weight-gradient GEMM of the BERT shapes: the native split-K kernel (ops.wgrad_bf16, nn.NATIVE_WGRAD = True) against the
-library path (batched hipBLASLt GEMM with fp32 output + slice sum, nn.NATIVE_WGRAD = False), random bf16 operands, through
-nn._splitk_wgrad.  usage: [T=tokens] [GEOMETRY=base|mini] [SPLITS=s,s,...] [NO_REMAP=1] [ONE_PHASE=1] [AB=rounds]
+"""Weight-gradient GEMM of the BERT shapes: the native split-K kernel (ops.wgrad_bf16, dense.NATIVE_WGRAD = True) against the
+library path (batched hipBLASLt GEMM with fp32 output + slice sum, dense.NATIVE_WGRAD = False), random bf16 operands, through
+dense._splitk_wgrad.  usage: [T=tokens] [GEOMETRY=base|mini] [SPLITS=s,s,...] [NO_REMAP=1] [ONE_PHASE=1] [AB=rounds]
 python tools/ubench/wgrad_native.py
 SPLITS / NO_REMAP / ONE_PHASE time the native kernel alone at other slice counts / without the XCD grouping / with the
 one-barrier main loop (ops.wgrad_bf16 direct).  AB=r skips the library comparison and alternates the two main-loop schedules
@@ -11,7 +11,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
-from gmlm_amd import nn, ops  # noqa: E402
+from gmlm_amd import dense, ops  # noqa: E402
 
 dev = torch.device("cuda")
 T = int(os.environ.get("T", "91712"))
@@ -36,8 +36,8 @@ def timeit(f, n=20):
 
 
 def run(native):
-    nn.NATIVE_WGRAD = native
-    return timeit(lambda: nn._splitk_wgrad(dy, x, keep_fp32=True))
+    dense.NATIVE_WGRAD = native
+    return timeit(lambda: dense._splitk_wgrad(dy, x, keep_fp32=True))
 
 
 for name, n, k in SHAPES:
@@ -58,8 +58,8 @@ for name, n, k in SHAPES:
               + " ".join(f"{v:6.1f}" for v in two) + f" us   means {sum(one) / AB:6.1f} / {sum(two) / AB:6.1f}"
               f"  x{sum(one) / sum(two):4.2f}  every default run faster: {max(two) < min(one)}", flush=True)
         continue
-    nn.NATIVE_WGRAD = True
-    out = nn._splitk_wgrad(dy, x, keep_fp32=True)
+    dense.NATIVE_WGRAD = True
+    out = dense._splitk_wgrad(dy, x, keep_fp32=True)
     exact = dy.double().t() @ x.double()
     bound = (dy.double().abs().t() @ x.double().abs())
     rel = float(((out.double() - exact).abs() / bound).max())
@@ -71,4 +71,4 @@ for name, n, k in SHAPES:
         ts = timeit(lambda: ops.wgrad_bf16(dy, x, splits=s, flags=FLAGS))
         line += f"\n      S={s:2d} flags={FLAGS}: {ts:7.1f} us ({fl / ts / 1e6:6.1f} TF/s)"
     print(line, flush=True)
-nn.NATIVE_WGRAD = True
+dense.NATIVE_WGRAD = True

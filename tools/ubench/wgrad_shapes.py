@@ -1,5 +1,5 @@
 """Split-K weight-gradient GEMM forms for the BERT shapes of the bench (T = 91,698 tokens, S = 16 slices):
-fp32-output batched GEMM (what bert._splitk_wgrad issues; not covered by TunableOp) against the bf16-output batched form
+fp32-output batched GEMM (what dense._splitk_wgrad issues; not covered by TunableOp) against the bf16-output batched form
 that TunableOp can tune.  usage: [PYTORCH_TUNABLEOP_ENABLED=1] [T=tokens] [GEOMETRY=base|mini] python tools/ubench/wgrad_shapes.py [S,S,...]"""
 import torch
 dev = torch.device("cuda")
