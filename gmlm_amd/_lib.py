@@ -1,5 +1,5 @@
-"""ctypes binding of libgmlm_hip.so (C ABI: include/gmlm_hip.h, gmlm_hip_split.h, gmlm_hip_optim.h, gmlm_hip_d32.h and
-gmlm_hip_wide.h): one signature table per header, positional argument types only.  Which attention entry point a head dim
+"""ctypes binding of libgmlm_hip.so (C ABI: include/gmlm_hip.h, gmlm_hip_split.h, gmlm_hip_optim.h, gmlm_hip_d32.h,
+gmlm_hip_wide.h and gmlm_hip_modernbert.h): one signature table per header, positional argument types only.  Which attention entry point a head dim
 takes, and where each ABI puts its arguments by name, is the family table of ops.py (``_ATTN_FAMILIES``).
 
 The product path has NO fallback: if the shared library is missing or a call fails, a Python
@@ -130,7 +130,24 @@ SIGNATURES_WIDE = {
                                                    _p, _p, _i32, _p, _sz, _p]),
 }
 
-SIGNATURE_TABLES = (SIGNATURES, SIGNATURES_SPLIT, SIGNATURES_OPTIM, SIGNATURES_D32, SIGNATURES_WIDE)   # one per header, all bound by lib()
+# sixth header, include/gmlm_hip_modernbert.h (ModernBERT encoder: add + LayerNorm, rotary embedding at d = 64, GeGLU, band-limited attention)
+SIGNATURES_MODERNBERT = {
+    "gmlm_add_layernorm_fwd": (C.c_int, [_p, _p, _p, _p, _i64, _i64, _f32, _p, _p, _p, _p, _i32, _p]),
+    "gmlm_add_layernorm_bwd_workspace_bytes": (_sz, [_i64, _i64]),
+    "gmlm_add_layernorm_bwd": (C.c_int, [_p, _p, _p, _p, _p, _p, _i64, _i64, _p, _p, _p, _i32, _p, _sz, _p]),
+    "gmlm_rope64_fwd": (C.c_int, [_p, _i64, _p, _i64, _i64, _i64, _p, _i64, _i64, _i32, _p]),
+    "gmlm_rope64_bwd": (C.c_int, [_p, _i64, _p, _i64, _i64, _i64, _p, _i64, _i64, _i32, _p]),
+    "gmlm_geglu_fwd": (C.c_int, [_p, _i64, _i64, _p, _i32, _p]),
+    "gmlm_geglu_bwd": (C.c_int, [_p, _p, _i64, _i64, _p, _i32, _p]),
+    "gmlm_attention_window_fwd": (C.c_int, [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _f32, _i64, _p,
+                                            _p, _p, _i32, _p, _i64, _p]),
+    "gmlm_attention_window_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "gmlm_attention_window_bwd": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32,
+                                            _f32, _i64, _p, _p, _p, _i64, _i64, _i64, _i32, _p, _i64, _p, _sz, _p]),
+}
+
+SIGNATURE_TABLES = (SIGNATURES, SIGNATURES_SPLIT, SIGNATURES_OPTIM, SIGNATURES_D32, SIGNATURES_WIDE,
+                    SIGNATURES_MODERNBERT)   # one per header, all bound by lib()
 
 
 class GmlmHipError(RuntimeError):

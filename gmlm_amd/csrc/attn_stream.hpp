@@ -17,9 +17,15 @@ namespace gmlm {
 //   its rows.  A wave computes a tile only if the tile's first key is <= its first query (both multiples of 32), so every
 //   row of a computing wave has a valid key in every tile it computes: the running max stays finite.
 // GQA: K / V are read from head `kvh` (query head hd / group) instead of hd.
-template <typename T, int D, int NW, bool DROP, int KT, bool DBUF, bool CAUSAL = false, bool GQA = false>
+// WINDOW (lq == lk, no dropout): query i sees the keys j with |i - j| <= window below kv_len.  The key loop covers
+//   [q_tile0 - window, q_tile_end + window] within [0, kv_len) (block-uniform bounds); a wave skips the arithmetic (never a
+//   barrier) of tiles outside the band of its 32 rows; tiles wholly inside that band and below kv_len keep the compare-free
+//   path.  Unlike CAUSAL, a row can meet computed tiles in which it sees no key before the tile of its own diagonal (and, past
+//   kv_len + window, in all of them): its running max is then -inf, and both exponentials are guarded to give 0, not NaN.
+template <typename T, int D, int NW, bool DROP, int KT, bool DBUF, bool CAUSAL = false, bool GQA = false, bool WINDOW = false>
 __device__ __forceinline__ void attn_fwd_body(const AttnParams& p, int64_t tile, int64_t b, int64_t hd, int64_t o_stride,
-                                              int64_t kvh = 0) {
+                                              int64_t kvh = 0, int64_t window = 0) {
+  static_assert(!(WINDOW && (CAUSAL || DROP)), "the band mask has no causal or dropout form");
   constexpr int KB = KT / 32, NT = NW * 64, PITCH = D + Pad<T>::v, DB = D / 32, NBUF = DBUF ? 2 : 1;
   __shared__ __attribute__((aligned(16))) T ks[NBUF][KT * PITCH];
   __shared__ __attribute__((aligned(16))) T vs[NBUF][KT * PITCH];
@@ -50,27 +56,29 @@ __device__ __forceinline__ void attn_fwd_body(const AttnParams& p, int64_t tile,
   const uint32_t dq_u = drop_base(attn_seed(p), lse_base) + (uint32_t)(q_row >> 1) * kDropC1 + (uint32_t)(2 * h) * kDropC2;
   const int q_odd = (int)(q_row & 1);
   const int64_t q_tile0 = tile * (NW * 32), q_wave0 = q_tile0 + w * 32;
-  const int64_t kv_end = CAUSAL && q_tile0 + NW * 32 < kvlen ? q_tile0 + NW * 32 : kvlen;   // keys this workgroup can see
+  int64_t kv_end = CAUSAL && q_tile0 + NW * 32 < kvlen ? q_tile0 + NW * 32 : kvlen;   // keys this workgroup can see
+  if (WINDOW && q_tile0 + NW * 32 + window < kv_end) kv_end = q_tile0 + NW * 32 + window;   // last query NW*32 - 1 sees up to + window
+  const int t0 = WINDOW && q_tile0 > window ? (int)((q_tile0 - window) / KT) : 0;          // first key tile inside the band
   const int ntiles = (int)((kv_end + KT - 1) / KT);
   TileRegs<T, D, KT, NT> kr, vr;
   kr.init(p.k_stride, tid);
   vr.init(p.v_stride, tid);
-  if (ntiles > 0) {
-    kr.load(kg, p.k_stride, 0, lk_, tid);
-    vr.load(vg, p.v_stride, 0, lk_, tid);
+  if (ntiles > t0) {
+    kr.load(kg, p.k_stride, (int64_t)t0 * KT, lk_, tid);
+    vr.load(vg, p.v_stride, (int64_t)t0 * KT, lk_, tid);
     kr.store(ks[0], tid);
     vr.store(vs[0], tid);
   }
   __syncthreads();
-  for (int t = 0; t < ntiles; ++t) {
+  for (int t = t0; t < ntiles; ++t) {
     const int64_t kv0 = (int64_t)t * KT;
-    const int cur = DBUF ? (t & 1) : 0;
+    const int cur = DBUF ? ((t - t0) & 1) : 0;
     const bool more = t + 1 < ntiles;
     if (DBUF && more) {
       kr.load(kg, p.k_stride, kv0 + KT, lk_, tid);
       vr.load(vg, p.v_stride, kv0 + KT, lk_, tid);
     }
-    if (wave_live && (!CAUSAL || kv0 <= q_wave0)) {
+    if (wave_live && (!CAUSAL || kv0 <= q_wave0) && (!WINDOW || (kv0 <= q_wave0 + 31 + window && kv0 + KT - 1 + window >= q_wave0))) {
     f32x16 s[KB];
 #pragma unroll
     for (int kb = 0; kb < KB; ++kb) {
@@ -79,7 +87,10 @@ __device__ __forceinline__ void attn_fwd_body(const AttnParams& p, int64_t tile,
       mma_rows<D>(ks[cur], PITCH, kb * 32, qf, s[kb], r, h);
     }
     float rmax = -INFINITY;
-    if (kv0 + KT <= kvlen && (!CAUSAL || kv0 + KT - 1 <= q_tile0)) {   // whole tile valid (block-uniform; causal: and below the diagonal): no per-key compare
+    // whole tile valid (block-uniform; causal: and below the diagonal; window: and inside the band of all 32 rows of the
+    // wave, wave-uniform): no per-key compare
+    if (kv0 + KT <= kvlen && (!CAUSAL || kv0 + KT - 1 <= q_tile0) &&
+        (!WINDOW || (kv0 + window >= q_wave0 + 31 && kv0 + KT - 1 <= q_wave0 + window))) {
 #pragma unroll
       for (int kb = 0; kb < KB; ++kb)
 #pragma unroll
@@ -90,7 +101,7 @@ __device__ __forceinline__ void attn_fwd_body(const AttnParams& p, int64_t tile,
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
           const int64_t key = kv0 + kb * 32 + acc_row(i, h);
-          const float v = (key < kvlen && (!CAUSAL || key <= q_row)) ? s[kb][i] : -INFINITY;
+          const float v = (key < kvlen && (!CAUSAL || key <= q_row) && (!WINDOW || (key <= q_row + window && key + window >= q_row))) ? s[kb][i] : -INFINITY;
           s[kb][i] = v;
           rmax = fmaxf(rmax, v);
         }
@@ -98,18 +109,20 @@ __device__ __forceinline__ void attn_fwd_body(const AttnParams& p, int64_t tile,
     rmax = xhalf_max(rmax);
     // deferred rescale: keep the old reference max while the new one exceeds it by < 2^kDefer (probabilities
     // then stay <= 2^kDefer, harmless in fp32 / bf16); the O and l rescale is skipped for the whole wave then
-    float m_new = fmaxf(m, rmax * sl2);             // finite: key kv0 is always valid
-    const bool keep = __all(m_new - m <= kDefer);   // m = -inf (first tile) -> false
+    float m_new = fmaxf(m, rmax * sl2);             // finite: key kv0 is always valid (WINDOW: -inf while the row has seen no key)
+    // WINDOW: a row still at -inf that stays there changes nothing (-inf - -inf would be NaN and end the deferral for the wave)
+    const bool keep = __all((WINDOW && m_new == -INFINITY) || m_new - m <= kDefer);   // m = -inf (first tile) -> false
     float alpha = 1.f;
     if (keep) m_new = m;
-    else alpha = fast_exp2(m - m_new);              // m = -inf -> 0
+    else alpha = (WINDOW && m == -INFINITY) ? 0.f : fast_exp2(m - m_new);   // m = -inf -> 0 (WINDOW: also when m_new = -inf)
+    const float m_ref = (WINDOW && m_new == -INFINITY) ? 0.f : m_new;       // exponent reference: exp2(-inf - 0) = 0 for a row with no key yet
     float rsum = 0.f;
 #pragma unroll
     for (int kb = 0; kb < KB; ++kb)
 #pragma unroll
       for (int i = 0; i < 16; i += 2) {
-        const float e0 = fast_exp2(fmaf(s[kb][i], sl2, -m_new));       // masked: exp2(-inf) = 0
-        const float e1 = fast_exp2(fmaf(s[kb][i + 1], sl2, -m_new));
+        const float e0 = fast_exp2(fmaf(s[kb][i], sl2, -m_ref));       // masked: exp2(-inf) = 0
+        const float e1 = fast_exp2(fmaf(s[kb][i + 1], sl2, -m_ref));
         rsum += e0 + e1;                                               // the normaliser uses the un-dropped probabilities
         if (DROP) {
           float m0, m1;                                // keys (k, k+1): (kv0 + kb*32 + acc_row(i, 0)) >> 1 pairs on from the tile start
@@ -207,9 +220,13 @@ __device__ __forceinline__ void attn_delta_body(const T* __restrict__ o, const T
 // CAUSAL / GQA as in attn_fwd_body.  The bf16 extra contraction step cannot express a causal mask (it is not rank-1): the one
 // 32-key block that crosses a wave's diagonal selects P = 0 explicitly before dS (a select, not a product: a score above
 // the diagonal is not bounded by lse and may have overflowed).
-template <typename T, int D, int NW, bool DROP, int KT, bool DBUF, bool CAUSAL = false, bool GQA = false>
+// WINDOW as in attn_fwd_body: the same key loop; a 32-key block outside the band of the wave's rows is skipped, one that the
+// band edge crosses selects P = 0 explicitly before dS, exactly as the diagonal block does.  A query that saw no key has
+// lse = -inf: it is given probability 0 everywhere, like a row past the sequence (dQ = 0).
+template <typename T, int D, int NW, bool DROP, int KT, bool DBUF, bool CAUSAL = false, bool GQA = false, bool WINDOW = false>
 __device__ __forceinline__ void attn_dq_body(const AttnParams& p, int64_t tile, int64_t b, int64_t hd, int64_t o_stride,
-                                             int64_t kvh = 0) {
+                                             int64_t kvh = 0, int64_t window = 0) {
+  static_assert(!(WINDOW && (CAUSAL || DROP)), "the band mask has no causal or dropout form");
   constexpr int KB = KT / 32, NT = NW * 64, PITCH = D + Pad<T>::v, DB = D / 32, NBUF = DBUF ? 2 : 1;
   __shared__ __attribute__((aligned(16))) T ks[NBUF][KT * PITCH];
   __shared__ __attribute__((aligned(16))) T vs[NBUF][KT * PITCH];
@@ -230,7 +247,9 @@ __device__ __forceinline__ void attn_dq_body(const AttnParams& p, int64_t tile, 
   qf.load(static_cast<const T*>(p.q) + (qbase + qr) * p.q_stride + hd * D, q_ok, h);
   dof.load(static_cast<const T*>(p.dout) + (qbase + qr) * o_stride + hd * D, q_ok, h);
   const float sl2 = p.scale * kLog2e;
-  const float lse2 = q_ok ? p.lse[lse_base + q_row] * kLog2e : INFINITY;
+  const float lse_q = q_ok ? p.lse[lse_base + q_row] : INFINITY;
+  const bool q_on = q_ok && !(WINDOW && lse_q == -INFINITY);   // WINDOW: a query with no visible key
+  const float lse2 = q_on ? lse_q * kLog2e : INFINITY;
   const float dl = q_ok ? p.delta[lse_base + q_row] : 0.f;
   const int kvl = (int)(kvlen < (1 << 30) ? kvlen : (1 << 30));
   const uint32_t dq_u = drop_base(attn_seed(p), lse_base) + (uint32_t)(q_row >> 1) * kDropC1 + (uint32_t)(2 * h) * kDropC2;
@@ -248,7 +267,7 @@ __device__ __forceinline__ void attn_dq_body(const AttnParams& p, int64_t tile, 
     for (int s_ = 0; s_ < D / 16; ++s_)
 #pragma unroll
       for (int j = 0; j < 8; ++j) qf.v[s_][j] = (__bf16)((float)qf.v[s_][j] * sl2);
-    const float l2 = q_ok ? lse2 : 0x1p100f;                 // a row past the sequence: probability 0 everywhere
+    const float l2 = q_on ? lse2 : 0x1p100f;                 // a row past the sequence: probability 0 everywhere
     const float lh = (float)(__bf16)l2, ll = (float)(__bf16)(l2 - lh);
     const float dh = (float)(__bf16)dl, dlo = (float)(__bf16)(dl - dh);
 #pragma unroll
@@ -265,22 +284,24 @@ __device__ __forceinline__ void attn_dq_body(const AttnParams& p, int64_t tile, 
 #pragma unroll
     for (int i = 0; i < 16; ++i) dq[d][i] = 0.f;
   const int64_t q_tile0 = tile * (NW * 32), q_wave0 = q_tile0 + w * 32;
-  const int64_t kv_end = CAUSAL && q_tile0 + NW * 32 < kvlen ? q_tile0 + NW * 32 : kvlen;   // keys this workgroup can see
+  int64_t kv_end = CAUSAL && q_tile0 + NW * 32 < kvlen ? q_tile0 + NW * 32 : kvlen;   // keys this workgroup can see
+  if (WINDOW && q_tile0 + NW * 32 + window < kv_end) kv_end = q_tile0 + NW * 32 + window;   // last query NW*32 - 1 sees up to + window
   const int qi = (int)(q_row < (1 << 30) ? q_row : (1 << 30));
+  const int t0 = WINDOW && q_tile0 > window ? (int)((q_tile0 - window) / KT) : 0;          // first key tile inside the band
   const int ntiles = (int)((kv_end + KT - 1) / KT);
   TileRegs<T, D, KT, NT> kr, vr;
   kr.init(p.k_stride, tid);
   vr.init(p.v_stride, tid);
-  if (ntiles > 0) {
-    kr.load(kg, p.k_stride, 0, lk_, tid);
-    vr.load(vg, p.v_stride, 0, lk_, tid);
+  if (ntiles > t0) {
+    kr.load(kg, p.k_stride, (int64_t)t0 * KT, lk_, tid);
+    vr.load(vg, p.v_stride, (int64_t)t0 * KT, lk_, tid);
     kr.store(ks[0], tid);
     vr.store(vs[0], tid);
   }
   __syncthreads();
-  for (int t = 0; t < ntiles; ++t) {
+  for (int t = t0; t < ntiles; ++t) {
     const int64_t kv0 = (int64_t)t * KT;
-    const int cur = DBUF ? (t & 1) : 0;
+    const int cur = DBUF ? ((t - t0) & 1) : 0;
     const bool more = t + 1 < ntiles;
     if (DBUF && more) {
       kr.load(kg, p.k_stride, kv0 + KT, lk_, tid);
@@ -293,6 +314,11 @@ __device__ __forceinline__ void attn_dq_body(const AttnParams& p, int64_t tile, 
         if (kv0 + kb * 32 > q_wave0) continue;                 // key block above this wave's rows (wave-uniform; no barrier inside)
       }
       const bool diag = CAUSAL && kv0 + kb * 32 == q_wave0;    // the only key block that crosses this wave's diagonal
+      if constexpr (WINDOW) {
+        if (kv0 + kb * 32 > q_wave0 + 31 + window || kv0 + kb * 32 + 31 + window < q_wave0) continue;   // key block outside the band of this wave's rows (wave-uniform)
+      }
+      // a key block that the band edge crosses for some row of the wave (wave-uniform)
+      const bool edge = WINDOW && !(kv0 + kb * 32 + window >= q_wave0 + 31 && kv0 + kb * 32 + 31 <= q_wave0 + window);
       f32x16 s, dp;
 #pragma unroll
       for (int i = 0; i < 16; ++i) { s[i] = 0.f; dp[i] = 0.f; }
@@ -326,6 +352,13 @@ __device__ __forceinline__ void attn_dq_body(const AttnParams& p, int64_t tile, 
             const int kq = (int)kv0 + kb * 32 + acc_row(i, h);
             p0 = kq <= qi ? p0 : 0.f;
             p1 = kq + 1 <= qi ? p1 : 0.f;
+          }
+        }
+        if constexpr (WINDOW) {
+          if (edge) {
+            const int kq = (int)kv0 + kb * 32 + acc_row(i, h), wi = (int)window;    // window < 2^30 (host check)
+            p0 = (kq <= qi + wi && kq + wi >= qi) ? p0 : 0.f;
+            p1 = (kq + 1 <= qi + wi && kq + 1 + wi >= qi) ? p1 : 0.f;
           }
         }
         if (FOLD && !DROP) {
@@ -371,8 +404,13 @@ __device__ __forceinline__ void attn_dq_body(const AttnParams& p, int64_t tile, 
 // QT = query rows staged per barrier: 32 or 64 with two LDS buffers (long sequences: loads of tile t+1 under the MFMAs
 // of tile t), or 128 in one buffer for sequences of <= 128 tokens (the whole sequence behind ONE barrier: at
 // 16-128 tokens the per-tile barrier / LDS round trip, not the MFMA work, sets the block's lifetime).
-template <typename T, int D, int NW, bool DROP, int QT, bool DBUF>
-__device__ __forceinline__ void attn_dkv_body(const AttnParams& p, int64_t tile, int64_t b, int64_t hd, int64_t o_stride) {
+// WINDOW (lq == lk, no dropout): the query loop covers [k_tile0 - window, k_tile_end + window] within [0, lq) (block-uniform);
+// a 32-query block outside the band of the wave's keys is skipped, one that the band edge crosses selects P = 0 before dS; a
+// query with lse = -inf (no visible key) is staged with lse = +inf, i.e. probability 0, and adds nothing to dK or dV.
+template <typename T, int D, int NW, bool DROP, int QT, bool DBUF, bool WINDOW = false>
+__device__ __forceinline__ void attn_dkv_body(const AttnParams& p, int64_t tile, int64_t b, int64_t hd, int64_t o_stride,
+                                              int64_t window = 0) {
+  static_assert(!(WINDOW && DROP), "the band mask has no dropout form");
   constexpr int NT = NW * 64, PITCH = D + Pad<T>::v, DB = D / 32, NBUF = DBUF ? 2 : 1;
   __shared__ __attribute__((aligned(16))) T qs[NBUF][QT * PITCH];
   __shared__ __attribute__((aligned(16))) T dos[NBUF][QT * PITCH];
@@ -390,6 +428,8 @@ __device__ __forceinline__ void attn_dkv_body(const AttnParams& p, int64_t tile,
   int64_t kvlen = lk_;
   if (p.kv_len) { kvlen = p.kv_len[b]; if (kvlen > lk_) kvlen = lk_; if (kvlen < 0) kvlen = 0; }
   const int64_t key = tile * (NW * 32) + w * 32 + r;
+  const int64_t k_tile0 = tile * (NW * 32), k_wave0 = k_tile0 + w * 32;
+  const int ki = (int)(key < (1 << 30) ? key : (1 << 30));
   const bool key_in = key < lk_;           // row exists in memory
   const bool key_ok = key < kvlen;          // takes part in the softmax
   const bool wave_live = tile * (NW * 32) + w * 32 < kvlen;   // else: staging helper only (dK = dV = 0)
@@ -426,7 +466,9 @@ __device__ __forceinline__ void attn_dkv_body(const AttnParams& p, int64_t tile,
   // a whole workgroup past kv_len has nothing to accumulate (block-uniform condition)
   const bool block_live = tile * (NW * 32) < kvlen;
   if (block_live) {
-    const int ntiles = (int)((lq_ + QT - 1) / QT);
+    const int64_t q_end = WINDOW && k_tile0 + NW * 32 + window < lq_ ? k_tile0 + NW * 32 + window : lq_;   // queries that see this workgroup's keys
+    const int t0 = WINDOW && k_tile0 > window ? (int)((k_tile0 - window) / QT) : 0;
+    const int ntiles = (int)((q_end + QT - 1) / QT);
     TileRegs<T, D, QT, NT> qr, dor;
     qr.init(p.q_stride, tid);
     dor.init(o_stride, tid);
@@ -435,6 +477,7 @@ __device__ __forceinline__ void attn_dkv_body(const AttnParams& p, int64_t tile,
       if (tid < QT) {
         const bool ok = q0 + tid < lq_;
         lr = ok ? lse_g[q0 + tid] * kLog2e : INFINITY;     // +inf: probability 0 for a row past the sequence
+        if (WINDOW && lr == -INFINITY) lr = INFINITY;      // a query with no visible key: probability 0 as well
         dr = ok ? dl_g[q0 + tid] : 0.f;
       }
     };
@@ -457,18 +500,18 @@ __device__ __forceinline__ void attn_dkv_body(const AttnParams& p, int64_t tile,
         }
       }
     };
-    if (ntiles > 0) {
-      qr.load(qg, p.q_stride, 0, lq_, tid);
-      dor.load(dog, o_stride, 0, lq_, tid);
-      load_small(0);
+    if (ntiles > t0) {
+      qr.load(qg, p.q_stride, (int64_t)t0 * QT, lq_, tid);
+      dor.load(dog, o_stride, (int64_t)t0 * QT, lq_, tid);
+      load_small((int64_t)t0 * QT);
       qr.store(qs[0], tid);
       dor.store(dos[0], tid);
       store_small(0);
     }
     __syncthreads();
-    for (int t = 0; t < ntiles; ++t) {
+    for (int t = t0; t < ntiles; ++t) {
       const int64_t q0 = (int64_t)t * QT;
-      const int cur = DBUF ? (t & 1) : 0;
+      const int cur = DBUF ? ((t - t0) & 1) : 0;
       const bool more = t + 1 < ntiles;
       if (DBUF && more) {
         qr.load(qg, p.q_stride, q0 + QT, lq_, tid);
@@ -479,6 +522,11 @@ __device__ __forceinline__ void attn_dkv_body(const AttnParams& p, int64_t tile,
 #pragma unroll
       for (int qb = 0; qb < QT / 32; ++qb) {
         if (QT > 32 && q0 + qb * 32 >= lq_) break;            // block-uniform
+        if constexpr (WINDOW) {
+          if (q0 + qb * 32 > k_wave0 + 31 + window || q0 + qb * 32 + 31 + window < k_wave0) continue;   // query block outside the band of this wave's keys (wave-uniform)
+        }
+        // a query block that the band edge crosses for some key of the wave (wave-uniform)
+        const bool edge = WINDOW && !(q0 + qb * 32 + window >= k_wave0 + 31 && q0 + qb * 32 + 31 <= k_wave0 + window);
         f32x16 s, dp;
 #pragma unroll
         for (int i = 0; i < 16; ++i) { s[i] = 0.f; dp[i] = 0.f; }
@@ -495,7 +543,13 @@ __device__ __forceinline__ void attn_dkv_body(const AttnParams& p, int64_t tile,
         if constexpr (FOLD && !DROP) {
 #pragma unroll
           for (int i = 0; i < 16; ++i) {
-            const float pr = fast_exp2(s[i]);
+            float pr = fast_exp2(s[i]);
+            if constexpr (WINDOW) {
+              if (edge) {                                      // a select, not a product: see attn_dq_body
+                const int qq = (int)q0 + qb * 32 + acc_row(i, h), wi = (int)window;
+                pr = (qq <= ki + wi && qq + wi >= ki) ? pr : 0.f;
+              }
+            }
             s[i] = pr;
             dp[i] = pr * dp[i];
           }
@@ -511,8 +565,15 @@ __device__ __forceinline__ void attn_dkv_body(const AttnParams& p, int64_t tile,
             const int i = 4 * g4 + j;                        // registers i, i+1 = queries q0 + q4 + j, + 1 (even, odd)
             // query rows past the sequence carry lse = +inf in LDS, masked keys select the exponent -inf: both give
             // probability exactly 0 without a branch around the exp
-            const float p0 = FOLD ? fast_exp2(s[i]) : fast_exp2(key_ok ? fmaf(s[i], sl2, -lv[j]) : -INFINITY);
-            const float p1 = FOLD ? fast_exp2(s[i + 1]) : fast_exp2(key_ok ? fmaf(s[i + 1], sl2, -lv[j + 1]) : -INFINITY);
+            float p0 = FOLD ? fast_exp2(s[i]) : fast_exp2(key_ok ? fmaf(s[i], sl2, -lv[j]) : -INFINITY);
+            float p1 = FOLD ? fast_exp2(s[i + 1]) : fast_exp2(key_ok ? fmaf(s[i + 1], sl2, -lv[j + 1]) : -INFINITY);
+            if constexpr (WINDOW) {
+              if (edge) {
+                const int qq = (int)q0 + q4 + j, wi = (int)window;
+                p0 = (qq <= ki + wi && qq + wi >= ki) ? p0 : 0.f;
+                p1 = (qq + 1 <= ki + wi && qq + 1 + wi >= ki) ? p1 : 0.f;
+              }
+            }
             float m0 = 1.f, m1 = 1.f;
             if (DROP) drop_pair_k(dk_u + ((uint32_t)(q0 >> 1) + (uint32_t)((qb * 32 + 8 * g4 + j) >> 1)) * kDropC1, k_odd, p.drop_thresh, p.keep_scale, m0, m1);
             s[i] = p0 * m0;

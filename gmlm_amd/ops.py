@@ -1320,3 +1320,208 @@ class SwiGLU(torch.autograd.Function):
 
 def swiglu(gate_up):
     return SwiGLU.apply(gate_up)
+
+
+# ---------------------------------------------------------------------------------------------
+# ModernBERT encoder: add + LayerNorm, GeGLU, rotary embedding at d = 64 in place + (band-limited) attention
+# ---------------------------------------------------------------------------------------------
+ADD_LAYERNORM_MAX_F = 4096       # GMLM_ADD_LAYERNORM_MAX_F (include/gmlm_hip_modernbert.h)
+
+
+class AddLayerNorm(torch.autograd.Function):
+    """(s, y) with s = a + b in the compute dtype (``b`` None: s is ``a``) and y = LayerNorm(s) * gamma (+ beta, may be None).
+    ``s`` is the residual stream handed to the next add; its gradient and y's meet in ONE backward kernel."""
+
+    @staticmethod
+    def forward(ctx, a, b, gamma, beta, eps):
+        _cuda(a)
+        shape = a.shape
+        f = shape[-1]
+        a2 = a.contiguous().view(-1, f)
+        b2 = None if b is None else b.to(a.dtype).contiguous().view(-1, f)
+        rows = a2.shape[0]
+        gf = _f32c(gamma)
+        bf = None if beta is None else _f32c(beta)
+        s2 = torch.empty_like(a2) if b2 is not None else None
+        y = torch.empty_like(a2)
+        stats = torch.empty(2, rows, dtype=torch.float32, device=a.device)          # mean | rstd
+        check(lib().gmlm_add_layernorm_fwd(_ptr(a2), _ptr(b2), _ptr(gf), _ptr(bf), rows, f, float(eps), _ptr(s2), _ptr(y),
+                                           _ptr(stats[0]), _ptr(stats[1]), _dt(a2), _stream()), "gmlm_add_layernorm_fwd")
+        if s2 is None:
+            s2 = a2
+        ctx.save_for_backward(s2, gf, stats)
+        ctx.cfg = (shape, b is not None, beta is not None)
+        return (s2.view(shape) if b is not None else a.view_as(a)), y.view(shape)
+
+    @staticmethod
+    def backward(ctx, gs, gy):
+        s2, gf, stats = ctx.saved_tensors
+        shape, has_b, has_beta = ctx.cfg
+        rows, f = s2.shape
+        if gy is None:
+            gy = torch.zeros_like(s2)
+        gy2 = gy.contiguous().view(rows, f).to(s2.dtype)
+        gs2 = None if gs is None else gs.contiguous().view(rows, f).to(s2.dtype)
+        ds = torch.empty_like(s2)
+        dw = torch.empty(2 if has_beta else 1, f, dtype=torch.float32, device=s2.device)   # dgamma | dbeta: one buffer
+        ws = _ws(lib().gmlm_add_layernorm_bwd_workspace_bytes(rows, f), s2.device)
+        check(lib().gmlm_add_layernorm_bwd(_ptr(gy2), _ptr(gs2), _ptr(s2), _ptr(gf), _ptr(stats[0]), _ptr(stats[1]), rows, f, _ptr(ds),
+                                           _ptr(dw), _ptr(dw[1]) if has_beta else None, _dt(s2), _ptr(ws), ws.numel(), _stream()),
+              "gmlm_add_layernorm_bwd")
+        ds = ds.view(shape)
+        return ds, (ds if has_b else None), dw[0], (dw[1] if has_beta else None), None
+
+
+def add_layernorm(a, b, gamma, beta=None, eps=1e-5):
+    """-> (a + b, LayerNorm(a + b) * gamma + beta); ``b`` and ``beta`` may be None."""
+    return AddLayerNorm.apply(a, b, gamma, beta, eps)
+
+
+class GeGLU(torch.autograd.Function):
+    """[..., 2 I] = [gate | up] -> gelu(gate) * up [..., I] (erf GELU)."""
+
+    @staticmethod
+    def forward(ctx, u):
+        _cuda(u)
+        shape = u.shape
+        inter = shape[-1] // 2
+        u2 = u.contiguous().view(-1, 2 * inter)
+        y = torch.empty(u2.shape[0], inter, dtype=u.dtype, device=u.device)
+        check(lib().gmlm_geglu_fwd(_ptr(u2), u2.shape[0], inter, _ptr(y), _dt(u2), _stream()), "gmlm_geglu_fwd")
+        ctx.save_for_backward(u2)
+        ctx.shape = shape
+        return y.view(*shape[:-1], inter)
+
+    @staticmethod
+    def backward(ctx, gy):
+        (u2,) = ctx.saved_tensors
+        rows, inter = u2.shape[0], u2.shape[1] // 2
+        gy2 = gy.contiguous().view(rows, inter).to(u2.dtype)
+        du = torch.empty_like(u2)
+        check(lib().gmlm_geglu_bwd(_ptr(gy2), _ptr(u2), rows, inter, _ptr(du), _dt(u2), _stream()), "gmlm_geglu_bwd")
+        return du.view(ctx.shape)
+
+
+def geglu(u):
+    return GeGLU.apply(u)
+
+
+def rope64_(qkv, cos_sin, h, seq_len=0, pos_ids=None, inverse=False):
+    """Rotate (``inverse``: rotate back) the Q | K columns of fused [.., 3 * h * 64] rows IN PLACE; positions are row % seq_len,
+    or ``pos_ids`` (int32 [tokens]) when given.  Outside autograd: the building block of ``RopeWindowAttention``."""
+    tokens, stride = _qkv_rows(qkv, 3 * h * 64)
+    if cos_sin.dtype != torch.float32 or cos_sin.dim() != 3 or tuple(cos_sin.shape[1:]) != (2, 32) or not cos_sin.is_contiguous():
+        raise ValueError("cos / sin table must be a contiguous fp32 [max_len, 2, 32] tensor")
+    name = "gmlm_rope64_bwd" if inverse else "gmlm_rope64_fwd"
+    check(getattr(lib(), name)(_ptr(qkv), stride, _ptr(cos_sin), cos_sin.shape[0], tokens, int(seq_len), _ptr(pos_ids), h, 64, _dt(qkv),
+                               _stream()), name)
+    return qkv
+
+
+def window_cuts(layer_type: str, window: int, max_len: int) -> bool:
+    """The routing rule of a ModernBERT layer's attention: only a ``sliding_attention`` layer whose band |i - j| <= window
+    actually hides a key of the call's longest sequence (max_len > window + 1) runs the band-limited kernels; a full-attention
+    layer, and a sliding layer on sequences of at most window + 1 tokens (the band is vacuous), take the ``attention_qkv`` path."""
+    return layer_type == "sliding_attention" and int(max_len) > int(window) + 1
+
+
+def _window_fwd(qkv, kv_len, h, scale, window, cu, max_len, want_lo):
+    packed = cu is not None
+    l, hd3 = (qkv.shape[0] if packed else qkv.shape[1]), qkv.shape[-1]
+    b = cu.numel() - 1 if packed else qkv.shape[0]
+    hd = hd3 // 3
+    out = torch.empty(qkv.shape[:-1] + (hd,), dtype=qkv.dtype, device=qkv.device)
+    lse = torch.empty((h, l) if packed else (b, h, l), dtype=torch.float32, device=qkv.device)
+    out_lo = torch.empty_like(out) if want_lo else None
+    q, k, v = qkv[..., :hd], qkv[..., hd:2 * hd], qkv[..., 2 * hd:]
+    rows = int(max_len) if packed else l
+    span = min(rows, 2 * int(window) + 1)
+    with _span("attn_window_fwd_d64", flops=4.0 * h * 64 * b * rows * span):
+        check(lib().gmlm_attention_window_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(kv_len), b, h, l, l, 64, hd3, hd3, hd3, float(scale), 0.0,
+                                              int(window), _ptr(out), _ptr(out_lo), _ptr(lse), _dt(qkv), _ptr(cu), int(max_len),
+                                              _stream()), "gmlm_attention_window_fwd")
+    return out, out_lo, lse
+
+
+def _window_bwd(qkv, out, out_lo, gout, lse, kv_len, h, scale, window, cu, max_len, dqkv):
+    packed = cu is not None
+    l, hd3 = (qkv.shape[0] if packed else qkv.shape[1]), qkv.shape[-1]
+    b = cu.numel() - 1 if packed else qkv.shape[0]
+    hd = hd3 // 3
+    gout = gout.contiguous().to(qkv.dtype)
+    q, k, v = qkv[..., :hd], qkv[..., hd:2 * hd], qkv[..., 2 * hd:]
+    dq, dk, dv = dqkv[..., :hd], dqkv[..., hd:2 * hd], dqkv[..., 2 * hd:]
+    ws = _ws(lib().gmlm_attention_window_workspace_bytes(1 if packed else b, h, l), qkv.device)
+    rows = int(max_len) if packed else l
+    span = min(rows, 2 * int(window) + 1)
+    with _span("attn_window_bwd_d64", flops=10.0 * h * 64 * b * rows * span):
+        check(lib().gmlm_attention_window_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(out_lo), _ptr(gout), _ptr(lse), _ptr(kv_len),
+                                              b, h, l, l, 64, hd3, hd3, hd3, float(scale), 0.0, int(window), _ptr(dq), _ptr(dk),
+                                              _ptr(dv), hd3, hd3, hd3, _dt(qkv), _ptr(cu), int(max_len), _ptr(ws), ws.numel(),
+                                              _stream()), "gmlm_attention_window_bwd")
+
+
+class _RopeAttention(torch.autograd.Function):
+    """Rotary embedding at d = 64 IN PLACE on the Q | K columns of a fused [.., 3 * h * 64] projection output (marked dirty and
+    returned beside the context), then attention on the rotated buffer, in one autograd node.  ``window`` None: the
+    ``AttentionQKV`` path (padded, packed and short-sequence kernels, ``groups``); an int: the band-limited kernels.  The
+    backward runs the attention backward into ONE dqkv buffer, then the inverse rotation in place on it."""
+
+    @staticmethod
+    def forward(ctx, qkv, cs, kv_len, h, scale, window, pos_ids, cu_seqlens, max_len, pair_count, groups):
+        _cuda(qkv)
+        if not qkv.is_contiguous() or qkv.shape[-1] != 3 * h * 64:
+            raise ValueError("fused projection output must be contiguous [.., 3 * h * 64] rows")
+        packed = cu_seqlens is not None
+        if packed:
+            pos_ids = _pos_arg(qkv, pos_ids)
+            _varlen_args(qkv, cu_seqlens, max_len)
+        elif qkv.dim() != 3:
+            raise ValueError("padded fused projection output must be [b, l, 3 * h * 64]")
+        seq_len = 0 if packed else qkv.shape[1]
+        rope64_(qkv, cs, h, seq_len, pos_ids if packed else None)
+        ctx.mark_dirty(qkv)
+        ctx.rope = (cs, h, seq_len, pos_ids if packed else None)
+        ctx.window = window
+        if window is None:
+            out = AttentionQKV.forward(ctx, qkv, kv_len, h, scale, 0.0, 0, cu_seqlens, max_len, pair_count, groups)
+        else:
+            out, out_lo, lse = _window_fwd(qkv, kv_len, h, scale, window, cu_seqlens, max_len,
+                                           qkv.dtype == torch.bfloat16 and qkv.requires_grad)
+            ctx.save_for_backward(qkv, out, out_lo, lse, kv_len, cu_seqlens)
+            ctx.wcfg = (float(scale), int(max_len))
+        return out, qkv
+
+    @staticmethod
+    def backward(ctx, gout, _gqkv):
+        cs, h, seq_len, pos = ctx.rope
+        if ctx.window is None:
+            dqkv = AttentionQKV.backward(ctx, gout)[0]
+        else:
+            qkv, out, out_lo, lse, kv_len, cu = ctx.saved_tensors
+            scale, max_len = ctx.wcfg
+            dqkv = torch.empty_like(qkv)
+            _window_bwd(qkv, out, out_lo, gout, lse, kv_len, h, scale, ctx.window, cu, max_len, dqkv)
+        rope64_(dqkv, cs, h, seq_len, pos, inverse=True)
+        return (dqkv,) + (None,) * 10
+
+
+def _own_rows(qkv):
+    """Autograd cannot rebase a VIEW that a node with more than one output modifies in place (``dense.LinearBf16x3`` returns its
+    [T, N] product viewed as [b, l, N]): such a buffer is copied once; the native GEMM's output is rotated where it lies."""
+    return qkv.clone() if qkv._is_view() else qkv
+
+
+def rope_attention(qkv, cos_sin, kv_len, num_heads, scale, layer_type="full_attention", window=0):
+    """Padded layout: rotary embedding in place on ``qkv`` [b, l, 3 * h * 64] (positions 0..l-1), then full or band-limited
+    attention by ``window_cuts``; ``kv_len`` int32 [b] or None.  ``qkv`` is overwritten with its rotated form (a view is copied first: ``_own_rows``)."""
+    w = int(window) if window_cuts(layer_type, window, qkv.shape[1]) else None
+    return _RopeAttention.apply(_own_rows(qkv), cos_sin, kv_len, num_heads, scale, w, None, None, 0, None, None)[0]
+
+
+def rope_attention_varlen(qkv, cos_sin, pos_ids, cu_seqlens, max_len, num_heads, scale, layer_type="full_attention", window=0,
+                          pair_count=None, groups=None):
+    """Packed layout: ``qkv`` [T, 3 * h * 64] rows at positions ``pos_ids``, sequences by ``cu_seqlens`` (none longer than
+    ``max_len``, which also decides whether the band cuts).  ``qkv`` is overwritten with its rotated form."""
+    w = int(window) if window_cuts(layer_type, window, max_len) else None
+    return _RopeAttention.apply(_own_rows(qkv), cos_sin, None, num_heads, scale, w, pos_ids, cu_seqlens, int(max_len), pair_count, groups)[0]
