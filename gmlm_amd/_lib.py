@@ -1,5 +1,5 @@
 """ctypes binding of libgmlm_hip.so (C ABI: include/gmlm_hip.h, gmlm_hip_split.h, gmlm_hip_optim.h, gmlm_hip_d32.h,
-gmlm_hip_wide.h and gmlm_hip_modernbert.h): one signature table per header, positional argument types only.  Which attention entry point a head dim
+gmlm_hip_wide.h, gmlm_hip_modernbert.h and gmlm_hip_relbias.h): one signature table per header, positional argument types only.  Which attention entry point a head dim
 takes, and where each ABI puts its arguments by name, is the family table of ops.py (``_ATTN_FAMILIES``).
 
 The product path has NO fallback: if the shared library is missing or a call fails, a Python
@@ -149,6 +149,19 @@ SIGNATURES_MODERNBERT = {
 SIGNATURE_TABLES = (SIGNATURES, SIGNATURES_SPLIT, SIGNATURES_OPTIM, SIGNATURES_D32, SIGNATURES_WIDE,
                     SIGNATURES_MODERNBERT)   # one per header, all bound by lib()
 
+# seventh header, include/gmlm_hip_relbias.h (self-attention with a learned relative-position bias at d = 64: MPNet encoders)
+SIGNATURES_RELBIAS = {
+    "gmlm_attention_relbias_fwd": (C.c_int, [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _f32, _u64, _p,
+                                             _p, _i64, _p, _p, _p, _i32, _p, _i64, _p]),
+    "gmlm_attention_relbias_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64]),
+    "gmlm_attention_relbias_bwd": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32,
+                                             _f32, _u64, _p, _p, _i64, _p, _p, _p, _p, _i64, _i64, _i64, _i32, _p, _i64, _p, _sz,
+                                             _p]),
+}
+
+# the headers added after the sixth: SIGNATURE_TABLES keeps the six that came with ABI version 1, lib() binds both tuples
+SIGNATURE_TABLES_LATER = (SIGNATURES_RELBIAS,)
+
 
 class GmlmHipError(RuntimeError):
     pass
@@ -167,7 +180,7 @@ def lib() -> C.CDLL:
             f"{LIB_PATH} not found: the HIP extension is not built. Run `make -C gmlm_amd/csrc` "
             "(or __graft_entry__.build()). gmlm_amd has no CPU / eager fallback.")
     handle = C.CDLL(LIB_PATH)
-    for table in SIGNATURE_TABLES:
+    for table in SIGNATURE_TABLES + SIGNATURE_TABLES_LATER:
         for name, (res, args) in table.items():
             fn = getattr(handle, name)  # AttributeError here = header / library mismatch
             fn.restype, fn.argtypes = res, args

@@ -22,10 +22,18 @@ namespace gmlm {
 //   barrier) of tiles outside the band of its 32 rows; tiles wholly inside that band and below kv_len keep the compare-free
 //   path.  Unlike CAUSAL, a row can meet computed tiles in which it sees no key before the tile of its own diagonal (and, past
 //   kv_len + window, in all of them): its running max is then -inf, and both exponentials are guarded to give 0, not NaN.
-template <typename T, int D, int NW, bool DROP, int KT, bool DBUF, bool CAUSAL = false, bool GQA = false, bool WINDOW = false>
+// BIAS (lq == lk): the score of query i and key j gets the additive term rel_bias[hd][rel_m - 1 + (j - i)] (fp32 table
+//   [h, 2 * rel_m - 1], rel_m >= the longest sequence), read through the vector cache.  The scores are moved into the log2
+//   domain right behind the QK^T chain, s' = s * scale * log2 e + bias * log2 e, and everything after it (running max,
+//   deferral, exponentials) works on s' with a unit factor.  An index past the table (a padded query row or key) is clamped;
+//   such a pair is masked or never stored.
+template <typename T, int D, int NW, bool DROP, int KT, bool DBUF, bool CAUSAL = false, bool GQA = false, bool WINDOW = false,
+          bool BIAS = false>
 __device__ __forceinline__ void attn_fwd_body(const AttnParams& p, int64_t tile, int64_t b, int64_t hd, int64_t o_stride,
-                                              int64_t kvh = 0, int64_t window = 0) {
+                                              int64_t kvh = 0, int64_t window = 0, const float* rel_bias = nullptr,
+                                              int rel_m = 0) {
   static_assert(!(WINDOW && (CAUSAL || DROP)), "the band mask has no causal or dropout form");
+  static_assert(!(BIAS && (CAUSAL || GQA || WINDOW)), "the relative-position bias has no causal, grouped or band form");
   constexpr int KB = KT / 32, NT = NW * 64, PITCH = D + Pad<T>::v, DB = D / 32, NBUF = DBUF ? 2 : 1;
   __shared__ __attribute__((aligned(16))) T ks[NBUF][KT * PITCH];
   __shared__ __attribute__((aligned(16))) T vs[NBUF][KT * PITCH];
@@ -85,6 +93,16 @@ __device__ __forceinline__ void attn_fwd_body(const AttnParams& p, int64_t tile,
 #pragma unroll
       for (int i = 0; i < 16; ++i) s[kb][i] = 0.f;
       mma_rows<D>(ks[cur], PITCH, kb * 32, qf, s[kb], r, h);
+      if constexpr (BIAS) {
+        const float* bh = rel_bias + hd * (2 * rel_m - 1) + (rel_m - 1);      // entry 0 = the diagonal
+        const int rel0 = (int)(kv0 - q_row) + kb * 32;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          int rel = rel0 + acc_row(i, h);
+          rel = rel < 1 - rel_m ? 1 - rel_m : (rel > rel_m - 1 ? rel_m - 1 : rel);
+          s[kb][i] = fmaf(s[kb][i], sl2, bh[rel] * kLog2e);
+        }
+      }
     }
     float rmax = -INFINITY;
     // whole tile valid (block-uniform; causal: and below the diagonal; window: and inside the band of all 32 rows of the
@@ -109,7 +127,7 @@ __device__ __forceinline__ void attn_fwd_body(const AttnParams& p, int64_t tile,
     rmax = xhalf_max(rmax);
     // deferred rescale: keep the old reference max while the new one exceeds it by < 2^kDefer (probabilities
     // then stay <= 2^kDefer, harmless in fp32 / bf16); the O and l rescale is skipped for the whole wave then
-    float m_new = fmaxf(m, rmax * sl2);             // finite: key kv0 is always valid (WINDOW: -inf while the row has seen no key)
+    float m_new = fmaxf(m, BIAS ? rmax : rmax * sl2);             // finite: key kv0 is always valid (WINDOW: -inf while the row has seen no key)
     // WINDOW: a row still at -inf that stays there changes nothing (-inf - -inf would be NaN and end the deferral for the wave)
     const bool keep = __all((WINDOW && m_new == -INFINITY) || m_new - m <= kDefer);   // m = -inf (first tile) -> false
     float alpha = 1.f;
@@ -121,8 +139,8 @@ __device__ __forceinline__ void attn_fwd_body(const AttnParams& p, int64_t tile,
     for (int kb = 0; kb < KB; ++kb)
 #pragma unroll
       for (int i = 0; i < 16; i += 2) {
-        const float e0 = fast_exp2(fmaf(s[kb][i], sl2, -m_ref));       // masked: exp2(-inf) = 0
-        const float e1 = fast_exp2(fmaf(s[kb][i + 1], sl2, -m_ref));
+        const float e0 = fast_exp2(BIAS ? s[kb][i] - m_ref : fmaf(s[kb][i], sl2, -m_ref));       // masked: exp2(-inf) = 0
+        const float e1 = fast_exp2(BIAS ? s[kb][i + 1] - m_ref : fmaf(s[kb][i + 1], sl2, -m_ref));
         rsum += e0 + e1;                                               // the normaliser uses the un-dropped probabilities
         if (DROP) {
           float m0, m1;                                // keys (k, k+1): (kv0 + kb*32 + acc_row(i, 0)) >> 1 pairs on from the tile start
@@ -223,10 +241,15 @@ __device__ __forceinline__ void attn_delta_body(const T* __restrict__ o, const T
 // WINDOW as in attn_fwd_body: the same key loop; a 32-key block outside the band of the wave's rows is skipped, one that the
 // band edge crosses selects P = 0 explicitly before dS, exactly as the diagonal block does.  A query that saw no key has
 // lse = -inf: it is given probability 0 everywhere, like a row past the sequence (dQ = 0).
-template <typename T, int D, int NW, bool DROP, int KT, bool DBUF, bool CAUSAL = false, bool GQA = false, bool WINDOW = false>
+// BIAS as in attn_fwd_body: bias * log2 e is added to the exponent (bf16: to what leaves the MFMA chain, where a masked key
+// still sits near -2^100); dQ itself has no bias term.  The gradient of the table is a kernel of its own (attn_relbias.hip).
+template <typename T, int D, int NW, bool DROP, int KT, bool DBUF, bool CAUSAL = false, bool GQA = false, bool WINDOW = false,
+          bool BIAS = false>
 __device__ __forceinline__ void attn_dq_body(const AttnParams& p, int64_t tile, int64_t b, int64_t hd, int64_t o_stride,
-                                             int64_t kvh = 0, int64_t window = 0) {
+                                             int64_t kvh = 0, int64_t window = 0, const float* rel_bias = nullptr,
+                                             int rel_m = 0) {
   static_assert(!(WINDOW && (CAUSAL || DROP)), "the band mask has no causal or dropout form");
+  static_assert(!(BIAS && (CAUSAL || GQA || WINDOW)), "the relative-position bias has no causal, grouped or band form");
   constexpr int KB = KT / 32, NT = NW * 64, PITCH = D + Pad<T>::v, DB = D / 32, NBUF = DBUF ? 2 : 1;
   __shared__ __attribute__((aligned(16))) T ks[NBUF][KT * PITCH];
   __shared__ __attribute__((aligned(16))) T vs[NBUF][KT * PITCH];
@@ -336,14 +359,21 @@ __device__ __forceinline__ void attn_dq_body(const AttnParams& p, int64_t tile, 
 #pragma unroll
       for (int i = 0; i < 16; i += 2) {
         float p0, p1;
+        float b0 = 0.f, b1 = 0.f;                                  // BIAS: bias * log2 e of keys key, key + 1
+        if constexpr (BIAS) {
+          const float* bh = rel_bias + hd * (2 * rel_m - 1) + (rel_m - 1);
+          const int rel = (int)kv0 + kb * 32 + acc_row(i, h) - qi, lo = 1 - rel_m, hi = rel_m - 1;   // each index clamped on its own
+          b0 = bh[rel < lo ? lo : (rel > hi ? hi : rel)] * kLog2e;
+          b1 = bh[rel + 1 < lo ? lo : (rel + 1 > hi ? hi : rel + 1)] * kLog2e;
+        }
         if constexpr (FOLD) {
-          p0 = fast_exp2(s[i]);
-          p1 = fast_exp2(s[i + 1]);
+          p0 = fast_exp2(BIAS ? s[i] + b0 : s[i]);
+          p1 = fast_exp2(BIAS ? s[i + 1] + b1 : s[i + 1]);
         } else {
           const int key = (int)kv0 + kb * 32 + acc_row(i, h);      // even; registers i, i+1 = keys key, key+1
           // a masked key gets exponent -inf through a select (no branch around the exp); whole blocks skip the test;
           // a query row past the sequence has lse = +inf, i.e. probability 0 everywhere
-          float a0 = fmaf(s[i], sl2, -lse2), a1 = fmaf(s[i + 1], sl2, -lse2);
+          float a0 = fmaf(s[i], sl2, BIAS ? b0 - lse2 : -lse2), a1 = fmaf(s[i + 1], sl2, BIAS ? b1 - lse2 : -lse2);
           if (!full) { a0 = key < kvl ? a0 : -INFINITY; a1 = key + 1 < kvl ? a1 : -INFINITY; }
           p0 = fast_exp2(a0); p1 = fast_exp2(a1);
         }
@@ -407,10 +437,13 @@ __device__ __forceinline__ void attn_dq_body(const AttnParams& p, int64_t tile, 
 // WINDOW (lq == lk, no dropout): the query loop covers [k_tile0 - window, k_tile_end + window] within [0, lq) (block-uniform);
 // a 32-query block outside the band of the wave's keys is skipped, one that the band edge crosses selects P = 0 before dS; a
 // query with lse = -inf (no visible key) is staged with lse = +inf, i.e. probability 0, and adds nothing to dK or dV.
-template <typename T, int D, int NW, bool DROP, int QT, bool DBUF, bool WINDOW = false>
+// BIAS as in attn_dq_body, with the key on the lane: register i holds query q0 + qb * 32 + acc_row(i, h), so the table index
+// falls as i rises.
+template <typename T, int D, int NW, bool DROP, int QT, bool DBUF, bool WINDOW = false, bool BIAS = false>
 __device__ __forceinline__ void attn_dkv_body(const AttnParams& p, int64_t tile, int64_t b, int64_t hd, int64_t o_stride,
-                                              int64_t window = 0) {
+                                              int64_t window = 0, const float* rel_bias = nullptr, int rel_m = 0) {
   static_assert(!(WINDOW && DROP), "the band mask has no dropout form");
+  static_assert(!(BIAS && WINDOW), "the relative-position bias has no band form");
   constexpr int NT = NW * 64, PITCH = D + Pad<T>::v, DB = D / 32, NBUF = DBUF ? 2 : 1;
   __shared__ __attribute__((aligned(16))) T qs[NBUF][QT * PITCH];
   __shared__ __attribute__((aligned(16))) T dos[NBUF][QT * PITCH];
@@ -543,7 +576,14 @@ __device__ __forceinline__ void attn_dkv_body(const AttnParams& p, int64_t tile,
         if constexpr (FOLD && !DROP) {
 #pragma unroll
           for (int i = 0; i < 16; ++i) {
-            float pr = fast_exp2(s[i]);
+            float bi = 0.f;
+            if constexpr (BIAS) {
+              const float* bh = rel_bias + hd * (2 * rel_m - 1) + (rel_m - 1);
+              int rel = ki - ((int)q0 + qb * 32 + acc_row(i, h));
+              rel = rel < 1 - rel_m ? 1 - rel_m : (rel > rel_m - 1 ? rel_m - 1 : rel);
+              bi = bh[rel] * kLog2e;
+            }
+            float pr = fast_exp2(BIAS ? s[i] + bi : s[i]);
             if constexpr (WINDOW) {
               if (edge) {                                      // a select, not a product: see attn_dq_body
                 const int qq = (int)q0 + qb * 32 + acc_row(i, h), wi = (int)window;
@@ -565,8 +605,15 @@ __device__ __forceinline__ void attn_dkv_body(const AttnParams& p, int64_t tile,
             const int i = 4 * g4 + j;                        // registers i, i+1 = queries q0 + q4 + j, + 1 (even, odd)
             // query rows past the sequence carry lse = +inf in LDS, masked keys select the exponent -inf: both give
             // probability exactly 0 without a branch around the exp
-            float p0 = FOLD ? fast_exp2(s[i]) : fast_exp2(key_ok ? fmaf(s[i], sl2, -lv[j]) : -INFINITY);
-            float p1 = FOLD ? fast_exp2(s[i + 1]) : fast_exp2(key_ok ? fmaf(s[i + 1], sl2, -lv[j + 1]) : -INFINITY);
+            float b0 = 0.f, b1 = 0.f;                      // BIAS: bias * log2 e of queries q, q + 1 (table index rel, rel - 1)
+            if constexpr (BIAS) {
+              const float* bh = rel_bias + hd * (2 * rel_m - 1) + (rel_m - 1);
+              const int rel = ki - ((int)q0 + q4 + j), lo = 1 - rel_m, hi = rel_m - 1;   // each index clamped on its own
+              b0 = bh[rel < lo ? lo : (rel > hi ? hi : rel)] * kLog2e;
+              b1 = bh[rel - 1 < lo ? lo : (rel - 1 > hi ? hi : rel - 1)] * kLog2e;
+            }
+            float p0 = FOLD ? fast_exp2(BIAS ? s[i] + b0 : s[i]) : fast_exp2(key_ok ? fmaf(s[i], sl2, BIAS ? b0 - lv[j] : -lv[j]) : -INFINITY);
+            float p1 = FOLD ? fast_exp2(BIAS ? s[i + 1] + b1 : s[i + 1]) : fast_exp2(key_ok ? fmaf(s[i + 1], sl2, BIAS ? b1 - lv[j + 1] : -lv[j + 1]) : -INFINITY);
             if constexpr (WINDOW) {
               if (edge) {
                 const int qq = (int)q0 + q4 + j, wi = (int)window;

@@ -20,7 +20,7 @@ import torch
 import torch.nn as nn
 from torch.utils.checkpoint import checkpoint
 
-from . import bert, modernbert, ops, qwen3
+from . import bert, modernbert, mpnet, ops, qwen3
 from .dense import SPLITK_ROW_QUANTUM, _linear, check_gemm_precision, linear_specs, shadow_params, use_shadow
 from .graph import GraphCache, RelCSR
 from .nn import CrossAttention, GraphNorm, MultiScaleFusion, RGCNConv, compute_dtype, cross_attention_specs
@@ -138,10 +138,10 @@ class GraphTextLM(nn.Module):
             plm_encoder = AutoModel.from_pretrained(model_name, trust_remote_code=True)
             if plm_tokenizer is None:
                 plm_tokenizer = AutoTokenizer.from_pretrained(model_name, trust_remote_code=True)
-        # the encoder pass is picked by the PLM's model type: Qwen3 (gmlm_amd.qwen3), ModernBERT (gmlm_amd.modernbert), else BERT
-        # geometry (gmlm_amd.bert)
+        # the encoder pass is picked by the PLM's model type: Qwen3 (gmlm_amd.qwen3), ModernBERT (gmlm_amd.modernbert), MPNet
+        # (gmlm_amd.mpnet), else BERT geometry (gmlm_amd.bert)
         model_type = getattr(plm_encoder.config, "model_type", None)
-        self._plm_kind = model_type if model_type in ("qwen3", "modernbert") else "bert"
+        self._plm_kind = model_type if model_type in ("qwen3", "modernbert", "mpnet") else "bert"
         self._enc.check_supported(plm_encoder)
         self.plm_encoder = plm_encoder
         self.plm_tokenizer = plm_tokenizer
@@ -195,20 +195,20 @@ class GraphTextLM(nn.Module):
 
     @property
     def _enc(self):
-        return {"qwen3": qwen3, "modernbert": modernbert}.get(self._plm_kind, bert)
+        return {"qwen3": qwen3, "modernbert": modernbert, "mpnet": mpnet}.get(self._plm_kind, bert)
 
     def _packed_head_dim(self) -> int:
         """Head dim of the text encoder if it has the forms built on the BERT packed pass (short-sequence groups, bucketed
-        layout, hipGraph capture of the encoder), else 0: BERT geometry only.  A Qwen3 or ModernBERT encoder has none of them
-        whatever its hidden_size // heads is (64 for Qwen3-0.6B, whose head dim is 128, and for every ModernBERT); its plain
-        packed pass is ``_has_packed_pass``."""
+        layout, hipGraph capture of the encoder), else 0: BERT geometry only.  A Qwen3, ModernBERT or MPNet encoder has none of
+        them whatever its hidden_size // heads is (64 for Qwen3-0.6B, whose head dim is 128, for every ModernBERT and for every
+        MPNet); its plain packed pass is ``_has_packed_pass``."""
         cfg = self.plm_encoder.config
         return cfg.hidden_size // cfg.num_attention_heads if self._enc is bert else 0
 
     def _has_packed_pass(self) -> bool:
         """The encoder can run all active nodes as one variable-length packed batch: BERT geometry at a native head dim
-        (``bert.NATIVE_HEAD_DIMS``: 32 / 64 / 96, ``bert.bert_encode_packed``), Qwen3 (``qwen3.qwen3_encode_packed``, head dim 128)
-        and ModernBERT (``modernbert.modernbert_encode_packed``, head dim 64)."""
+        (``bert.NATIVE_HEAD_DIMS``: 32 / 64 / 96, ``bert.bert_encode_packed``), Qwen3 (``qwen3.qwen3_encode_packed``, head dim 128),
+        ModernBERT (``modernbert.modernbert_encode_packed``, head dim 64) and MPNet (``mpnet.mpnet_encode_packed``, head dim 64)."""
         return self._enc is not bert or self._packed_head_dim() in bert.NATIVE_HEAD_DIMS
 
     def graph(self, edge_index: torch.Tensor, num_nodes: int, edge_type=None) -> RelCSR:
@@ -451,7 +451,8 @@ class GraphTextLM(nn.Module):
                     # into attention work items of <= 128 rows (host arithmetic on the host copy of the lengths, ~0.2 ms per
                     # 1,000 sequences, once per batch: all layers, forward and backward, share it)
                     if self._enc is not bert:
-                        encode = qwen3.qwen3_encode_packed if self._enc is qwen3 else modernbert.modernbert_encode_packed
+                        encode = {qwen3: qwen3.qwen3_encode_packed, mpnet: mpnet.mpnet_encode_packed}.get(
+                            self._enc, modernbert.modernbert_encode_packed)
                         hs = encode(self.plm_encoder, tok, pos, cu_all, lmax, cd, self.plm_encoder.training,
                                     self.plm_gradient_checkpointing, weights)
                         plm_embeds = ops.MeanPoolScatter.apply(plm_embeds, hs, None, bi, cu, total)
@@ -466,7 +467,8 @@ class GraphTextLM(nn.Module):
                     plm_embeds = ops.MeanPoolScatter.apply(plm_embeds, hs, None, bi, cu, total)
                 else:
                     ids = tokens.input_ids[bi, :lmax]
-                    encode = {qwen3: qwen3.qwen3_encode, modernbert: modernbert.modernbert_encode}.get(self._enc, bert.bert_encode)
+                    encode = {qwen3: qwen3.qwen3_encode, modernbert: modernbert.modernbert_encode,
+                              mpnet: mpnet.mpnet_encode}.get(self._enc, bert.bert_encode)
                     hs = encode(self.plm_encoder, ids, lens, cd, self.plm_encoder.training, self.plm_gradient_checkpointing, weights)
                     plm_embeds = ops.MeanPoolScatter.apply(plm_embeds, hs, lens, bi)
         return plm_embeds

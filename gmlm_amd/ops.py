@@ -1525,3 +1525,88 @@ def rope_attention_varlen(qkv, cos_sin, pos_ids, cu_seqlens, max_len, num_heads,
     ``max_len``, which also decides whether the band cuts).  ``qkv`` is overwritten with its rotated form."""
     w = int(window) if window_cuts(layer_type, window, max_len) else None
     return _RopeAttention.apply(_own_rows(qkv), cos_sin, None, num_heads, scale, w, pos_ids, cu_seqlens, int(max_len), pair_count, groups)[0]
+
+
+# ---------------------------------------------------------------------------------------------
+# attention with a learned relative-position bias at head dim 64 (MPNet encoders; include/gmlm_hip_relbias.h)
+# ---------------------------------------------------------------------------------------------
+RELBIAS_MAX_LEN = 512      # GMLM_RELBIAS_MAX_LEN
+
+
+class AttentionRelBiasQKV(torch.autograd.Function):
+    """Self-attention on a fused QKV buffer whose scores get ``rel_bias[h, M - 1 + (j - i)]`` (fp32 [h, 2M - 1], M >= the
+    longest sequence), at head dim 64.  Called like ``AttentionQKV``:
+
+    padded mode: qkv [b, l, 3*h*64], kv_len int32 [b] or None.
+    packed mode: qkv [total_rows, 3*h*64], cu_seqlens int32 [b+1], max_len = longest sequence; positions count from the start
+    of each sequence.
+
+    Returns the context; the backward writes dq|dk|dv into ONE buffer of qkv's layout and returns the gradient of ``rel_bias``
+    (fp32, every entry written, fixed summation order).  Dropout is the replayable mask of every other attention kernel."""
+
+    @staticmethod
+    def forward(ctx, qkv, rel_bias, kv_len, h, scale, p, seed, cu_seqlens, max_len):
+        _cuda(qkv, rel_bias)
+        qkv = qkv.contiguous()
+        packed = cu_seqlens is not None
+        if packed:
+            _varlen_args(qkv, cu_seqlens, max_len)
+            l, hd3 = qkv.shape
+            b = cu_seqlens.numel() - 1
+        else:
+            b, l, hd3 = qkv.shape
+        hd = hd3 // 3
+        d = hd // h
+        if rel_bias.dtype != torch.float32 or rel_bias.dim() != 2 or rel_bias.shape[0] != h or rel_bias.shape[1] % 2 != 1:
+            raise ValueError("rel_bias must be an fp32 [heads, 2M - 1] tensor")
+        m = (rel_bias.shape[1] + 1) // 2
+        bias = rel_bias.detach().contiguous()
+        q, k, v = qkv[..., :hd], qkv[..., hd:2 * hd], qkv[..., 2 * hd:]
+        out = torch.empty(qkv.shape[:-1] + (hd,), dtype=qkv.dtype, device=qkv.device)
+        lse = torch.empty((h, l) if packed else (b, h, l), dtype=torch.float32, device=qkv.device)
+        out_lo = torch.empty_like(out) if (qkv.dtype == torch.bfloat16 and (qkv.requires_grad or rel_bias.requires_grad)) else None
+        flops = 4.0 * h * d * (float(max_len) * l if packed else float(b) * l * l)
+        with _span("attn_relbias_fwd_d%d" % d, flops=flops):
+            sd = ctx.sd = _sd()
+            check(lib().gmlm_attention_relbias_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(kv_len), b, h, l, l, d, hd3, hd3, hd3, float(scale),
+                                                   float(p), seed, sd, _ptr(bias), m, _ptr(out), _ptr(out_lo), _ptr(lse), _dt(qkv),
+                                                   _ptr(cu_seqlens), int(max_len), _stream()), "gmlm_attention_relbias_fwd")
+        ctx.save_for_backward(qkv, bias, lse, kv_len, cu_seqlens, out, out_lo)
+        ctx.cfg = (h, float(scale), float(p), seed, int(max_len), b, l, m, flops)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        qkv, bias, lse, kv_len, cu_seqlens, out, out_lo = ctx.saved_tensors
+        h, scale, p, seed, max_len, b, l, m, flops = ctx.cfg
+        hd3 = qkv.shape[-1]
+        hd = hd3 // 3
+        d = hd // h
+        gout = gout.contiguous().to(qkv.dtype)
+        q, k, v = qkv[..., :hd], qkv[..., hd:2 * hd], qkv[..., 2 * hd:]
+        dqkv = torch.empty_like(qkv)
+        dq, dk, dv = dqkv[..., :hd], dqkv[..., hd:2 * hd], dqkv[..., 2 * hd:]
+        dbias = torch.empty_like(bias)
+        ws = _ws(lib().gmlm_attention_relbias_workspace_bytes(b, h, l, max_len if cu_seqlens is not None else 0, m), qkv.device)
+        with _span("attn_relbias_bwd_d%d" % d, flops=3.5 * flops):          # the backward's five GEMMs + two of them again
+            check(lib().gmlm_attention_relbias_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(out_lo), _ptr(gout), _ptr(lse),
+                                                   _ptr(kv_len), b, h, l, l, d, hd3, hd3, hd3, scale, p, seed, ctx.sd, _ptr(bias), m,
+                                                   _ptr(dq), _ptr(dk), _ptr(dv), _ptr(dbias), hd3, hd3, hd3, _dt(qkv),
+                                                   _ptr(cu_seqlens), max_len, ws.data_ptr(), ws.numel(), _stream()),
+                  "gmlm_attention_relbias_bwd")
+        if b == 0 or l == 0:
+            dbias.zero_()                                                    # a call with nothing to do launches nothing
+        return dqkv, dbias, None, None, None, None, None, None, None
+
+
+def attention_relbias_qkv(qkv, rel_bias, kv_len, num_heads, scale, dropout_p=0.0, training=False):
+    """Padded form: qkv [b, l, 3 * h * 64], kv_len int32 [b] or None, rel_bias fp32 [h, 2M - 1] with M >= l."""
+    p = float(dropout_p) if training else 0.0
+    return AttentionRelBiasQKV.apply(qkv, rel_bias, kv_len, num_heads, scale, p, draw_seed() if p > 0 else 0, None, 0)
+
+
+def attention_relbias_qkv_varlen(qkv, rel_bias, cu_seqlens, max_len, num_heads, scale, dropout_p=0.0, training=False):
+    """Packed form: qkv [T, 3 * h * 64], sequences by ``cu_seqlens`` (none longer than ``max_len``), rel_bias fp32 [h, 2M - 1]
+    with M >= max_len."""
+    p = float(dropout_p) if training else 0.0
+    return AttentionRelBiasQKV.apply(qkv, rel_bias, None, num_heads, scale, p, draw_seed() if p > 0 else 0, cu_seqlens, int(max_len))
