@@ -17,10 +17,10 @@ from __future__ import annotations
 from typing import Optional
 
 import torch
-from torch.utils.checkpoint import checkpoint
 
-from . import ops
-from .dense import _mm, _splitk_wgrad, encoder_operands  # noqa: F401  (_splitk_wgrad: tests/test_gpu_model.py imports it from here)
+from . import encoder, ops
+from .dense import _mm, _splitk_wgrad  # noqa: F401  (_splitk_wgrad: tests/test_gpu_model.py imports it from here)
+from .encoder import LayerWeights  # noqa: F401  (the post-LayerNorm layer's weights, shared with mpnet.py)
 from .nn import attention_any_dim
 
 # Head dims the encoder runs on attention kernels of their own, with the fused QKV buffer, the packed pass, the bucketed
@@ -45,42 +45,14 @@ def check_supported(plm) -> None:
         raise NotImplementedError("gmlm_amd text-encoder kernels do not cover this PLM: " + "; ".join(problems))
 
 
-class LayerWeights:
-    """Per-forward view of one BertLayer's parameters: the GEMM operands in the compute dtype (``w*`` / ``bqkv``,
-    no autograd history) next to the fp32 master parameters they were cast from.  Built ONCE per forward and
-    shared by all micro-batches.  The GEMM wrappers below compute with the cached copy and hand the weight /
-    bias gradients straight to the MASTERS in fp32 (the split-K partial sums are fp32 already), so neither the
-    per-weight cast kernels nor their backward casts exist."""
-    __slots__ = ("wqkv", "bqkv", "wo", "wi", "wo2", "m_qkv", "m_wo", "m_wi", "m_wo2", "bo", "bi", "bo2", "ln1w", "ln1b",
-                 "ln2w", "ln2b")
-
-
 def _layer_masters(layer):
     sa, so = layer.attention.self, layer.attention.output
-    return ([sa.query.weight, sa.key.weight, sa.value.weight], [sa.query.bias, sa.key.bias, sa.value.bias],
-            so.dense.weight, layer.intermediate.dense.weight, layer.output.dense.weight)
+    return [sa.query.weight, sa.key.weight, sa.value.weight], [sa.query.bias, sa.key.bias, sa.value.bias], so.dense, so.LayerNorm
 
 
 def prepare_weights(plm, cd, gemm_precision="native"):
-    """One flat buffer in the compute dtype for all layers' GEMM weights, filled by ONE multi-tensor copy
-    (Q/K/V rows land directly in the fused [3P, P] operand, so there is no concatenation either).
-    ``gemm_precision`` "bf16x3" (fp32 only): ``lw.w*`` then hold ``dense.SplitWeight`` objects, the two bf16 three-part forms of
-    the fused fp32 operand, split once here for all micro-batches; ``dense._mm`` picks the GEMM by the operand's type."""
-    out, specs = [], []
-    for i, layer in enumerate(plm.encoder.layer):
-        wq, bq, wo, wi, wo2 = _layer_masters(layer)
-        specs += [((i, "wqkv"), wq, 0), ((i, "bqkv"), bq, 0), ((i, "wo"), [wo], 0), ((i, "wi"), [wi], 0), ((i, "wo2"), [wo2], 0)]
-        so = layer.attention.output
-        lw = LayerWeights()
-        lw.m_qkv, lw.m_wo, lw.m_wi, lw.m_wo2 = tuple(wq) + tuple(bq), (wo,), (wi,), (wo2,)
-        lw.bo, lw.bi, lw.bo2 = so.dense.bias, layer.intermediate.dense.bias, layer.output.dense.bias
-        lw.ln1w, lw.ln1b = so.LayerNorm.weight, so.LayerNorm.bias
-        lw.ln2w, lw.ln2b = layer.output.LayerNorm.weight, layer.output.LayerNorm.bias
-        out.append(lw)
-    operands = encoder_operands(specs, cd, gemm_precision)
-    for i, lw in enumerate(out):
-        lw.wqkv, lw.bqkv, lw.wo, lw.wi, lw.wo2 = (operands[(i, k)] for k in ("wqkv", "bqkv", "wo", "wi", "wo2"))
-    return out
+    """``encoder.prepare_weights`` over the BertLayers."""
+    return encoder.prepare_weights(plm.encoder.layer, _layer_masters, cd, gemm_precision)
 
 
 def _layer(lw, h, lens, heads, training, p_hidden, p_attn, eps, cu=None, max_len=0, pair_count=None, groups=None):
@@ -98,10 +70,7 @@ def _layer(lw, h, lens, heads, training, p_hidden, p_attn, eps, cu=None, max_len
         qkv, h_res = _mm(h, lw.wqkv, lw.bqkv, lw.m_qkv, residual=True)
         ctx = attention_any_dim(qkv[..., :pdim], qkv[..., pdim:2 * pdim], qkv[..., 2 * pdim:], lens, heads, scale, p_attn,
                                 training)
-    a = ops.bias_res_layernorm(_mm(ctx, lw.wo, None, lw.m_wo), lw.bo, h_res, lw.ln1w, lw.ln1b, eps, False, p_hidden, training)
-    m_pre, a_res = _mm(a, lw.wi, None, lw.m_wi, residual=True)
-    m = ops.bias_gelu(m_pre, lw.bi)
-    return ops.bias_res_layernorm(_mm(m, lw.wo2, None, lw.m_wo2), lw.bo2, a_res, lw.ln2w, lw.ln2b, eps, False, p_hidden, training)
+    return encoder.post_ln_tail(lw, ctx, h_res, training, p_hidden, eps)
 
 
 def bert_encode(plm, input_ids: torch.Tensor, lens: torch.Tensor, cd: torch.dtype, training: bool = False,
@@ -121,8 +90,7 @@ def bert_encode(plm, input_ids: torch.Tensor, lens: torch.Tensor, cd: torch.dtyp
 
 def _encode_rows(plm, x, lens, cd, training, gradient_checkpointing, weights, *packed):
     """Embedding LayerNorm and the layers over the embedding rows ``x`` in ``cd`` ([B, L, P] with ``lens``, or [T, P] with
-    ``packed`` = the (cu_seqlens, max_len, pair_count, groups) of ``_layer``); a checkpointed layer is recomputed with the very
-    arguments it ran with."""
+    ``packed`` = the (cu_seqlens, max_len, pair_count, groups) of ``_layer``)."""
     cfg = plm.config
     emb = plm.embeddings
     eps, p_hidden, p_attn = cfg.layer_norm_eps, cfg.hidden_dropout_prob, cfg.attention_probs_dropout_prob
@@ -130,12 +98,8 @@ def _encode_rows(plm, x, lens, cd, training, gradient_checkpointing, weights, *p
     heads = cfg.num_attention_heads
     if weights is None:
         weights = prepare_weights(plm, cd)
-    for lw in weights:
-        if gradient_checkpointing and training and torch.is_grad_enabled():
-            h = checkpoint(_layer, lw, h, lens, heads, training, p_hidden, p_attn, eps, *packed, use_reentrant=False)
-        else:
-            h = _layer(lw, h, lens, heads, training, p_hidden, p_attn, eps, *packed)
-    return h
+    args = (lens, heads, training, p_hidden, p_attn, eps, *packed)
+    return encoder.run_layers(_layer, weights, h, args, training, gradient_checkpointing)
 
 
 def bert_encode_packed(plm, token_ids: torch.Tensor, pos_ids: torch.Tensor, cu_seqlens: torch.Tensor, max_len: int,

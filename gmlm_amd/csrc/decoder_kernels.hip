@@ -1,131 +1,30 @@
 // Row kernels of the pre-norm decoder-style text encoders (Qwen3 geometry, hf:modeling_qwen3.py): residual add + RMSNorm,
 // per-head RMSNorm of Q / K followed by the rotate-half position rotation, and the SwiGLU product.  bf16 or fp32 storage, fp32
 // arithmetic, ONE rounding on store.  HBM-bound streaming kernels; every reduction across rows runs in a fixed order
-// (block partials + rows_sum_kernel, or col_reduce): no atomics, identical calls give identical bits.
-#include "colreduce.hpp"
+// (block partials + rows_sum_kernel, or col_reduce): no atomics, identical calls give identical bits.  The kernel bodies
+// shared with modernbert_kernels.hip are in row_kernels.hpp.
+#include "row_kernels.hpp"
 
 namespace gmlm {
 
-template <int LPR>
-__device__ __forceinline__ float lanes_sum(float v) {
-#pragma unroll
-  for (int o = LPR / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-template <int V>
-__device__ __forceinline__ void load_f32(const float* __restrict__ p, float (&o)[V]) {
-#pragma unroll
-  for (int v = 0; v < V; v += 4) {
-    const float4 t = *reinterpret_cast<const float4*>(p + v);
-    o[v] = t.x; o[v + 1] = t.y; o[v + 2] = t.z; o[v + 3] = t.w;
-  }
-}
-
-// the value a store of `x` as T leaves in memory (the residual stream is read back in T by every later kernel, so the
-// statistics are taken over the ROUNDED sum, as the reference takes them over its bf16 hidden states)
-template <typename T> __device__ __forceinline__ float rounded(float x);
-template <> __device__ __forceinline__ float rounded<float>(float x) { return x; }
-template <> __device__ __forceinline__ float rounded<bf16_t>(float x) { return bf16_to_f32(f32_to_bf16(x)); }
-
-// ------------------------------------------------------------------------------------------------
-// add + RMSNorm.  One wave per row, CH 16-byte chunks per lane (f <= 64 * CH * V), the row stays in registers.
-//   s = a + b (b optional) stored as T;  y = s * rsqrt(mean(s^2) + eps) * w;  rstd[r] saved in fp32
-// ------------------------------------------------------------------------------------------------
+// add + RMSNorm (add_norm_*_body with RmsStat):  s = a + b (b optional) stored as T;  y = s * rsqrt(mean(s^2) + eps) * w;
+// rstd[r] saved in fp32
 template <typename T, int CH>
 __global__ __launch_bounds__(256) void rmsnorm_fwd_kernel(const T* __restrict__ a, const T* __restrict__ b,
                                                            const float* __restrict__ w, int64_t rows, int f, float eps,
                                                            T* __restrict__ s_out, T* __restrict__ y, float* __restrict__ rstd_o) {
-  constexpr int V = Store<T>::kVec;
-  const int lane = threadIdx.x & 63, nch = f / V;
-  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (r >= rows) return;                                   // wave-uniform; no barrier in this kernel
-  float z[CH][V];
-  float sq = 0.f;
-#pragma unroll
-  for (int c = 0; c < CH; ++c) {
-    const int ch = c * 64 + lane;
-    if (ch < nch) {
-      const int64_t off = r * f + (int64_t)ch * V;
-      Store<T>::ldv(a + off, z[c]);
-      if (b) {
-        float t[V];
-        Store<T>::ldv(b + off, t);
-#pragma unroll
-        for (int v = 0; v < V; ++v) z[c][v] = rounded<T>(z[c][v] + t[v]);
-        if (s_out) Store<T>::stv(s_out + off, z[c]);
-      }
-#pragma unroll
-      for (int v = 0; v < V; ++v) sq = fmaf(z[c][v], z[c][v], sq);   // a chain of v_fma_f32 (separate squares pair up into v_pk_mul_f32)
-    }
-  }
-  const float rs = 1.f / sqrtf(lanes_sum<64>(sq) / (float)f + eps);
-  if (lane == 0) rstd_o[r] = rs;
-#pragma unroll
-  for (int c = 0; c < CH; ++c) {
-    const int ch = c * 64 + lane;
-    if (ch < nch) {
-      float wv[V], o[V];
-      load_f32<V>(w + ch * V, wv);
-#pragma unroll
-      for (int v = 0; v < V; ++v) o[v] = z[c][v] * rs * wv[v];
-      Store<T>::stv(y + r * f + (int64_t)ch * V, o);
-    }
-  }
+  add_norm_fwd_body<T, CH, RmsStat>(a, b, w, nullptr, rows, f, eps, s_out, y, nullptr, rstd_o);
 }
 
-// ds = dres (optional: the gradient arriving on the residual stream) + rstd * (g - xhat * mean(g * xhat)),  g = dy * w,
-// xhat = s * rstd.  The gradient of a AND of b is ds.
 template <typename T, int CH>
 __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ dres,
                                                            const T* __restrict__ s, const float* __restrict__ w,
                                                            const float* __restrict__ rstd, int64_t rows, int f,
                                                            T* __restrict__ ds) {
-  constexpr int V = Store<T>::kVec;
-  const int lane = threadIdx.x & 63, nch = f / V;
-  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (r >= rows) return;
-  const float rs = rstd[r];
-  float g[CH][V], xh[CH][V];
-  float dot = 0.f;
-#pragma unroll
-  for (int c = 0; c < CH; ++c) {
-    const int ch = c * 64 + lane;
-    if (ch < nch) {
-      const int64_t off = r * f + (int64_t)ch * V;
-      float wv[V];
-      Store<T>::ldv(dy + off, g[c]);
-      Store<T>::ldv(s + off, xh[c]);
-      load_f32<V>(w + ch * V, wv);
-#pragma unroll
-      for (int v = 0; v < V; ++v) {
-        g[c][v] *= wv[v];
-        xh[c][v] *= rs;
-        dot += g[c][v] * xh[c][v];
-      }
-    }
-  }
-  const float m = lanes_sum<64>(dot) / (float)f;
-#pragma unroll
-  for (int c = 0; c < CH; ++c) {
-    const int ch = c * 64 + lane;
-    if (ch < nch) {
-      const int64_t off = r * f + (int64_t)ch * V;
-      float o[V];
-#pragma unroll
-      for (int v = 0; v < V; ++v) o[v] = rs * (g[c][v] - xh[c][v] * m);
-      if (dres) {
-        float t[V];
-        Store<T>::ldv(dres + off, t);
-#pragma unroll
-        for (int v = 0; v < V; ++v) o[v] += t[v];
-      }
-      Store<T>::stv(ds + off, o);
-    }
-  }
+  add_norm_bwd_body<T, CH, RmsStat>(dy, dres, s, w, nullptr, rstd, rows, f, ds);
 }
 
-// dw[c] = sum_r dy[r, c] * s[r, c] * rstd[r]  (col_reduce: fixed order)
+// dw[c] = sum_r dy[r, c] * s[r, c] * rstd[r]
 template <typename T>
 struct RmsDwFn {
   const T* dy;
@@ -133,29 +32,16 @@ struct RmsDwFn {
   const float* rstd;
   int64_t f;
   __device__ __forceinline__ void operator()(int64_t r, int64_t c, float (&v)[1]) const {
-    v[0] = Store<T>::ld(dy + r * f + c) * (Store<T>::ld(s + r * f + c) * rstd[r]);
+    norm_dw_terms<T, 1, false>(dy, s, nullptr, rstd, f, r, c, v);
   }
 };
 
 // ------------------------------------------------------------------------------------------------
-// Q / K head norm + rotary embedding.  A head row of 128 elements = LPR lanes x 16 bytes (16 lanes bf16, 32 lanes fp32);
-// element i pairs with i + 64, i.e. lane j with lane j ^ (LPR / 2): one cross-lane exchange, no LDS.
+// Q / K head norm + rotary embedding (the rotary pieces: row_kernels.hpp).  A head row of 128 elements = 16 lanes (bf16) or
+// 32 lanes (fp32) x 16 bytes.
 //   n = x * rsqrt(mean(x^2) + eps) * w;   out[i] = n[i] cos[i] - n[i + 64] sin[i],  out[i + 64] = n[i + 64] cos[i] + n[i] sin[i]
-// cs: fp32 [max_len, 2, 64] (cos row, then sin row) of the token's position: row % seq_len (padded [b, seq_len] layout), or,
-// when pos_ids is given (packed rows), pos_ids[row] clamped into [0, max_len) so that no position reads outside the table.
 // ------------------------------------------------------------------------------------------------
 constexpr int kHeadDim = 128;
-
-// pos_ids is a kernel argument: the branch is uniform over the grid
-__device__ __forceinline__ const float* rope_row(const float* __restrict__ cs, int64_t t, int64_t seq_len,
-                                                 const int32_t* __restrict__ pos_ids, int64_t max_len) {
-  if (pos_ids) {
-    int64_t pos = pos_ids[t];
-    pos = pos < 0 ? 0 : (pos >= max_len ? max_len - 1 : pos);
-    return cs + pos * 128;
-  }
-  return cs + (t % seq_len) * 128;
-}
 
 template <typename T>
 __global__ __launch_bounds__(256) void qknorm_rope_fwd_kernel(const T* __restrict__ qkv, int64_t in_stride,
@@ -168,14 +54,14 @@ __global__ __launch_bounds__(256) void qknorm_rope_fwd_kernel(const T* __restric
   const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int lr = (int)(gid % LPR), nh = hq + hkv;
   const int64_t item = gid / LPR;
-  const bool live = item < tokens * nh;                    // whole LPR-lane groups are live or not
-  const int64_t t = live ? item / nh : 0;
-  const int hd = live ? (int)(item % nh) : 0;
+  int64_t t;
+  int hd;
+  const bool live = head_row(item, tokens * nh, nh, t, hd);
   float x[V], wv[V], c[V], sn[V];
   Store<T>::ldv(qkv + t * in_stride + (int64_t)hd * kHeadDim + lr * V, x);
   load_f32<V>((hd < hq ? qw : kw) + lr * V, wv);
   const int col = (lr * V) & 63;
-  const float* csr = rope_row(cs, t, seq_len, pos_ids, max_len);
+  const float* csr = rope_row<kHeadDim>(cs, t, seq_len, pos_ids, max_len);
   load_f32<V>(csr + col, c);
   load_f32<V>(csr + 64 + col, sn);
   float sq = 0.f;
@@ -185,11 +71,7 @@ __global__ __launch_bounds__(256) void qknorm_rope_fwd_kernel(const T* __restric
   const bool upper = lr >= LPR / 2;
   float o[V];
 #pragma unroll
-  for (int v = 0; v < V; ++v) {
-    const float n = x[v] * rs * wv[v];
-    const float other = __shfl_xor(n, LPR / 2, 64);
-    o[v] = upper ? fmaf(other, sn[v], n * c[v]) : fmaf(-other, sn[v], n * c[v]);
-  }
+  for (int v = 0; v < V; ++v) o[v] = rotate_half<LPR, false>(x[v] * rs * wv[v], c[v], sn[v], upper);
   if (live) {
     Store<T>::stv(out + t * out_stride + (int64_t)hd * kHeadDim + lr * V, o);
     if (lr == 0) rstd_o[item] = rs;
@@ -223,7 +105,7 @@ __global__ __launch_bounds__(256) void qknorm_rope_bwd_kernel(T* __restrict__ dq
   const int64_t iters = (items + per_pass - 1) / per_pass;
   for (int64_t it = 0; it < iters; ++it) {
     const int64_t item = (it * gridDim.x + blockIdx.x) * RPB + grp;
-    const bool live = item < items;
+    const bool live = item < items;                        // as head_row has it, for this kernel's own item order
     const int64_t t = live ? item / nh : 0;
     const int hd = live ? (int)(item % nh) : 0;
     const bool is_k = hd >= hq;
@@ -231,15 +113,14 @@ __global__ __launch_bounds__(256) void qknorm_rope_bwd_kernel(T* __restrict__ dq
     T* dptr = dqkv + t * d_stride + (int64_t)hd * kHeadDim + lr * V;
     Store<T>::ldv(dptr, g);
     Store<T>::ldv(qkv + t * in_stride + (int64_t)hd * kHeadDim + lr * V, x);
-    const float* csr = rope_row(cs, t, seq_len, pos_ids, max_len);
+    const float* csr = rope_row<kHeadDim>(cs, t, seq_len, pos_ids, max_len);
     load_f32<V>(csr + col, c);
     load_f32<V>(csr + 64 + col, sn);
     const float rs = rstd[live ? item : 0];
     float dot = 0.f, dn[V], xh[V];
 #pragma unroll
     for (int v = 0; v < V; ++v) {
-      const float other = __shfl_xor(g[v], LPR / 2, 64);
-      dn[v] = upper ? fmaf(-other, sn[v], g[v] * c[v]) : fmaf(other, sn[v], g[v] * c[v]);   // R^T dout
+      dn[v] = rotate_half<LPR, true>(g[v], c[v], sn[v], upper);   // R^T dout
       xh[v] = x[v] * rs;
       if (live) {
         if (is_k) acck[v] += dn[v] * xh[v];
@@ -273,39 +154,13 @@ __global__ __launch_bounds__(256) void qknorm_rope_bwd_kernel(T* __restrict__ dq
 // ------------------------------------------------------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(256) void swiglu_fwd_kernel(const T* __restrict__ gu, int64_t rows, int64_t inter, T* __restrict__ y) {
-  constexpr int V = Store<T>::kVec;
-  const int64_t cpr = inter / V, total = rows * cpr;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const int64_t r = i / cpr, c = (i % cpr) * V;
-    float g[V], u[V], o[V];
-    Store<T>::ldv(gu + r * 2 * inter + c, g);
-    Store<T>::ldv(gu + r * 2 * inter + inter + c, u);
-#pragma unroll
-    for (int v = 0; v < V; ++v) o[v] = g[v] / (1.f + expf(-g[v])) * u[v];
-    Store<T>::stv(y + r * inter + c, o);
-  }
+  glu_fwd_body<T, SiluAct>(gu, rows, inter, y);
 }
 
 template <typename T>
 __global__ __launch_bounds__(256) void swiglu_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ gu, int64_t rows,
                                                           int64_t inter, T* __restrict__ dgu) {
-  constexpr int V = Store<T>::kVec;
-  const int64_t cpr = inter / V, total = rows * cpr;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const int64_t r = i / cpr, c = (i % cpr) * V;
-    float g[V], u[V], d[V], dg[V], du[V];
-    Store<T>::ldv(gu + r * 2 * inter + c, g);
-    Store<T>::ldv(gu + r * 2 * inter + inter + c, u);
-    Store<T>::ldv(dy + r * inter + c, d);
-#pragma unroll
-    for (int v = 0; v < V; ++v) {
-      const float sig = 1.f / (1.f + expf(-g[v]));
-      du[v] = d[v] * g[v] * sig;
-      dg[v] = d[v] * u[v] * sig * (1.f + g[v] * (1.f - sig));
-    }
-    Store<T>::stv(dgu + r * 2 * inter + c, dg);
-    Store<T>::stv(dgu + r * 2 * inter + inter + c, du);
-  }
+  glu_bwd_body<T, SiluAct>(dy, gu, rows, inter, dgu);
 }
 
 // ---- host ----------------------------------------------------------------------------------------
@@ -336,26 +191,7 @@ static int64_t rope_bwd_blocks(int64_t items, int dtype) {
   return nb < 1 ? 1 : (nb > kRopeBwdMaxBlocks ? kRopeBwdMaxBlocks : nb);
 }
 
-// Sizes first, pointers second (rope_ptrs): a call with no token returns GMLM_OK in between, as the other row kernels do for
-// zero rows.  seq_len = 0 is the padded layout [b, 0]: it has no token, and only then is it accepted.
-static int rope_sizes(const char* who, int64_t stride, int64_t other_stride, int64_t min_other, int64_t tokens, int64_t seq_len,
-                      int64_t max_len, int64_t hq, int64_t hkv, int64_t d, int dtype) {
-  GMLM_REQUIRE(dtype == GMLM_F32 || dtype == GMLM_BF16, "%s: unsupported dtype", who);
-  GMLM_REQUIRE(d == 128, "%s: head dim %ld not supported (this entry point takes 128)", who, (long)d);
-  GMLM_REQUIRE(tokens >= 0 && hq > 0 && hkv > 0 && hq + hkv < 4096, "%s: bad sizes", who);
-  GMLM_REQUIRE(max_len > 0, "%s: empty cos / sin table", who);
-  GMLM_REQUIRE(seq_len >= 0 && seq_len <= max_len, "%s: sequence length %ld exceeds the %ld rows of the cos / sin table", who,
-               (long)seq_len, (long)max_len);
-  GMLM_REQUIRE(seq_len > 0 || tokens == 0, "%s: %ld tokens in sequences of length 0", who, (long)tokens);
-  const int v = dtype == GMLM_F32 ? 4 : 8;
-  GMLM_REQUIRE(stride >= (hq + 2 * hkv) * 128 && stride % v == 0, "%s: qkv row stride %ld must be >= %ld and a multiple of %d", who,
-               (long)stride, (long)((hq + 2 * hkv) * 128), v);
-  GMLM_REQUIRE(other_stride >= min_other && other_stride % v == 0, "%s: row stride %ld must be >= %ld and a multiple of %d", who,
-               (long)other_stride, (long)min_other, v);
-  GMLM_REQUIRE(tokens * (hq + hkv) < ((int64_t)1 << 34), "%s: too many head rows", who);
-  return GMLM_OK;
-}
-
+// rope_sizes (row_kernels.hpp) first, pointers second: a call with no token returns GMLM_OK in between
 static int rope_ptrs(const char* who, const void* qkv, const void* other, const float* qw, const float* kw, const float* cs,
                      const float* rstd, bool by_pos, const int32_t* pos_ids) {
   GMLM_REQUIRE(qkv && other && aligned16(qkv) && aligned16(other), "%s: null or not 16-byte aligned pointer", who);
@@ -420,7 +256,7 @@ static int rope_fwd(const char* who, const void* qkv, int64_t qkv_stride, const 
                     const float* cos_sin, int64_t max_len, int64_t tokens, int64_t seq_len, bool by_pos, const int32_t* pos_ids,
                     int64_t hq, int64_t hkv, int64_t d, float eps, void* out, int64_t out_stride, float* rstd, int dtype,
                     gmlm_stream_t stream) {
-  int rc = rope_sizes(who, qkv_stride, out_stride, (hq + hkv) * 128, tokens, seq_len, max_len, hq, hkv, d, dtype);
+  int rc = rope_sizes(who, kHeadDim, qkv_stride, out_stride, (hq + hkv) * 128, tokens, seq_len, by_pos, max_len, hq, hkv, d, dtype);
   if (rc != GMLM_OK) return rc;
   if (tokens == 0) return GMLM_OK;
   if ((rc = rope_ptrs(who, qkv, out, q_weight, k_weight, cos_sin, rstd, by_pos, pos_ids)) != GMLM_OK) return rc;
@@ -460,7 +296,7 @@ static int rope_bwd(const char* who, void* dqkv, int64_t dqkv_stride, const void
                     const float* k_weight, const float* cos_sin, int64_t max_len, const float* rstd, int64_t tokens,
                     int64_t seq_len, bool by_pos, const int32_t* pos_ids, int64_t hq, int64_t hkv, int64_t d, float* dq_weight,
                     float* dk_weight, int dtype, void* workspace, size_t workspace_bytes, gmlm_stream_t stream) {
-  int rc = rope_sizes(who, qkv_stride, dqkv_stride, (hq + hkv) * 128, tokens, seq_len, max_len, hq, hkv, d, dtype);
+  int rc = rope_sizes(who, kHeadDim, qkv_stride, dqkv_stride, (hq + hkv) * 128, tokens, seq_len, by_pos, max_len, hq, hkv, d, dtype);
   if (rc != GMLM_OK) return rc;
   // the one output a call with no token still has: zero weight gradients
   GMLM_REQUIRE(dq_weight && dk_weight && dk_weight == dq_weight + 128, "%s: dq_weight | dk_weight are one fp32 [2, 128] buffer", who);
@@ -506,16 +342,9 @@ extern "C" int gmlm_qknorm_rope_pos_bwd(void* dqkv, int64_t dqkv_stride, const v
                   pos_ids, hq, hkv, d, dq_weight, dk_weight, dtype, workspace, workspace_bytes, stream);
 }
 
-static int swiglu_check(const char* who, int64_t rows, int64_t inter, int dtype) {
-  GMLM_REQUIRE(dtype == GMLM_F32 || dtype == GMLM_BF16, "%s: unsupported dtype", who);
-  const int v = dtype == GMLM_F32 ? 4 : 8;
-  GMLM_REQUIRE(rows >= 0 && inter > 0 && inter % v == 0, "%s: width %ld must be a multiple of %d", who, (long)inter, v);
-  return GMLM_OK;
-}
-
 extern "C" int gmlm_swiglu_fwd(const void* gate_up, int64_t rows, int64_t inter, void* y, int dtype, gmlm_stream_t stream) {
   static const char* who = "swiglu_fwd";
-  int rc = swiglu_check(who, rows, inter, dtype);
+  int rc = glu_check(who, rows, inter, dtype);
   if (rc != GMLM_OK) return rc;
   if (rows == 0) return GMLM_OK;
   GMLM_REQUIRE(gate_up && y && aligned16(gate_up) && aligned16(y), "%s: null or not 16-byte aligned pointer", who);
@@ -531,7 +360,7 @@ extern "C" int gmlm_swiglu_fwd(const void* gate_up, int64_t rows, int64_t inter,
 extern "C" int gmlm_swiglu_bwd(const void* dy, const void* gate_up, int64_t rows, int64_t inter, void* dgate_up, int dtype,
                                gmlm_stream_t stream) {
   static const char* who = "swiglu_bwd";
-  int rc = swiglu_check(who, rows, inter, dtype);
+  int rc = glu_check(who, rows, inter, dtype);
   if (rc != GMLM_OK) return rc;
   if (rows == 0) return GMLM_OK;
   GMLM_REQUIRE(dy && gate_up && dgate_up && aligned16(dy) && aligned16(gate_up) && aligned16(dgate_up),

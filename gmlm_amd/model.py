@@ -27,6 +27,12 @@ from .nn import CrossAttention, GraphNorm, MultiScaleFusion, RGCNConv, compute_d
 
 logger = logging.getLogger(__name__)
 
+# config.model_type -> (module, its padded pass, its packed pass), the passes by name: they are looked up in the module at
+# every call.  Any other model type is held against bert.check_supported.
+_ENCODERS = {"bert": (bert, "bert_encode", "bert_encode_packed"), "qwen3": (qwen3, "qwen3_encode", "qwen3_encode_packed"),
+             "modernbert": (modernbert, "modernbert_encode", "modernbert_encode_packed"),
+             "mpnet": (mpnet, "mpnet_encode", "mpnet_encode_packed")}
+
 # static sizes of a captured text-encoder batch: sequences / tokens / attention work items are padded up to multiples of these
 ENCODER_BUCKET = (64, 2048, 32)
 
@@ -141,7 +147,7 @@ class GraphTextLM(nn.Module):
         # the encoder pass is picked by the PLM's model type: Qwen3 (gmlm_amd.qwen3), ModernBERT (gmlm_amd.modernbert), MPNet
         # (gmlm_amd.mpnet), else BERT geometry (gmlm_amd.bert)
         model_type = getattr(plm_encoder.config, "model_type", None)
-        self._plm_kind = model_type if model_type in ("qwen3", "modernbert", "mpnet") else "bert"
+        self._plm_kind = model_type if model_type in _ENCODERS else "bert"
         self._enc.check_supported(plm_encoder)
         self.plm_encoder = plm_encoder
         self.plm_tokenizer = plm_tokenizer
@@ -195,7 +201,7 @@ class GraphTextLM(nn.Module):
 
     @property
     def _enc(self):
-        return {"qwen3": qwen3, "modernbert": modernbert, "mpnet": mpnet}.get(self._plm_kind, bert)
+        return _ENCODERS[self._plm_kind][0]
 
     def _packed_head_dim(self) -> int:
         """Head dim of the text encoder if it has the forms built on the BERT packed pass (short-sequence groups, bucketed
@@ -451,8 +457,7 @@ class GraphTextLM(nn.Module):
                     # into attention work items of <= 128 rows (host arithmetic on the host copy of the lengths, ~0.2 ms per
                     # 1,000 sequences, once per batch: all layers, forward and backward, share it)
                     if self._enc is not bert:
-                        encode = {qwen3: qwen3.qwen3_encode_packed, mpnet: mpnet.mpnet_encode_packed}.get(
-                            self._enc, modernbert.modernbert_encode_packed)
+                        encode = getattr(self._enc, _ENCODERS[self._plm_kind][2])
                         hs = encode(self.plm_encoder, tok, pos, cu_all, lmax, cd, self.plm_encoder.training,
                                     self.plm_gradient_checkpointing, weights)
                         plm_embeds = ops.MeanPoolScatter.apply(plm_embeds, hs, None, bi, cu, total)
@@ -467,8 +472,7 @@ class GraphTextLM(nn.Module):
                     plm_embeds = ops.MeanPoolScatter.apply(plm_embeds, hs, None, bi, cu, total)
                 else:
                     ids = tokens.input_ids[bi, :lmax]
-                    encode = {qwen3: qwen3.qwen3_encode, modernbert: modernbert.modernbert_encode,
-                              mpnet: mpnet.mpnet_encode}.get(self._enc, bert.bert_encode)
+                    encode = getattr(self._enc, _ENCODERS[self._plm_kind][1])
                     hs = encode(self.plm_encoder, ids, lens, cd, self.plm_encoder.training, self.plm_gradient_checkpointing, weights)
                     plm_embeds = ops.MeanPoolScatter.apply(plm_embeds, hs, lens, bi)
         return plm_embeds

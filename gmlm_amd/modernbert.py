@@ -21,9 +21,8 @@ of the BERT path on the rotated buffer; only a sliding layer that the window act
 from __future__ import annotations
 
 import torch
-from torch.utils.checkpoint import checkpoint
 
-from . import ops
+from . import encoder, ops
 from .dense import _mm, encoder_operands
 
 HEAD_DIM = 64
@@ -76,23 +75,9 @@ def check_supported(plm) -> None:
         raise NotImplementedError("gmlm_amd text-encoder kernels do not cover this PLM: " + "; ".join(problems))
 
 
-_ROPE_TABLES = {}
-
-
 def rope_table(cfg, layer_type: str, max_len: int, device) -> torch.Tensor:
-    """fp32 [>= max_len, 2, 32]: cos and sin of position * inv_freq, computed as ModernBertRotaryEmbedding does for the layer
-    type's theta (default rope type: inv_freq = theta^(-2i/64) in fp32, the products and cos / sin in fp32).  Built ONCE per
-    (device, theta) for ``max_position_embeddings`` rows and kept: no host work and no host-to-device copy per encoder call."""
-    theta = rope_theta(cfg, layer_type)
-    device = torch.device(device)
-    rows = max(int(max_len), int(getattr(cfg, "max_position_embeddings", 0) or 0))
-    key = (device.type, device.index, theta)
-    hit = _ROPE_TABLES.get(key)
-    if hit is None or hit.shape[0] < rows:
-        inv_freq = 1.0 / (theta ** (torch.arange(0, HEAD_DIM, 2, dtype=torch.float) / HEAD_DIM))
-        freqs = torch.arange(rows, dtype=torch.float32)[:, None] * inv_freq[None, :]
-        hit = _ROPE_TABLES[key] = torch.stack([freqs.cos(), freqs.sin()], 1).contiguous().to(device)
-    return hit
+    """fp32 [>= max_len, 2, 32]: ``encoder.rope_table`` for ModernBertRotaryEmbedding's theta of the layer type."""
+    return encoder.rope_table(rope_theta(cfg, layer_type), HEAD_DIM, encoder.table_rows(cfg, max_len), device)
 
 
 class LayerWeights:
@@ -147,18 +132,14 @@ def _embed(plm, ids, cd):
 
 def _encode_rows(plm, x, lens, max_len, cd, training, gradient_checkpointing, weights, *packed):
     """The layers and the final norm over the normalised embedding rows ``x`` ([B, L, P] with ``lens``, or [T, P] with
-    ``packed`` = the one trailing argument of ``_layer``); a checkpointed layer is recomputed with the very arguments it ran with."""
+    ``packed`` = the one trailing argument of ``_layer``)."""
     cfg = plm.config
     heads, eps, scale, window = cfg.num_attention_heads, cfg.norm_eps, HEAD_DIM ** -0.5, int(cfg.sliding_window)
     if weights is None:
         weights = prepare_weights(plm, cd)
     tables = {lt: rope_table(cfg, lt, max_len, x.device) for lt in set(cfg.layer_types)}
-    stream, branch = x, None
-    for lw in weights:
-        if gradient_checkpointing and training and torch.is_grad_enabled():
-            stream, branch = checkpoint(_layer, lw, stream, branch, lens, tables, heads, scale, eps, window, *packed, use_reentrant=False)
-        else:
-            stream, branch = _layer(lw, stream, branch, lens, tables, heads, scale, eps, window, *packed)
+    stream, branch = encoder.run_layers(_layer, weights, (x, None), (lens, tables, heads, scale, eps, window, *packed), training,
+                                        gradient_checkpointing)
     return ops.add_layernorm(stream, branch, plm.final_norm.weight, None, eps)[1]
 
 
@@ -170,8 +151,7 @@ def modernbert_encode(plm, input_ids: torch.Tensor, lens: torch.Tensor, cd: torc
     Rows at or past ``lens[b]`` are computed but never read by the pooling.  ``weights``: optional ``prepare_weights`` result."""
     cfg = plm.config
     b, l = input_ids.shape
-    if l > cfg.max_position_embeddings:
-        raise ValueError(f"sequence length {l} exceeds max_position_embeddings {cfg.max_position_embeddings}")
+    encoder.check_length(cfg, l)
     return _encode_rows(plm, _embed(plm, input_ids, cd), lens, l, cd, training, gradient_checkpointing, weights)
 
 
@@ -184,9 +164,7 @@ def modernbert_encode_packed(plm, tok: torch.Tensor, pos: torch.Tensor, cu_seqle
     embedding reads its table row by ``pos`` and the attention resolves its rows through ``cu_seqlens``."""
     cfg = plm.config
     max_len = int(max_len)
-    if max_len > cfg.max_position_embeddings:
-        raise ValueError(f"sequence length {max_len} exceeds max_position_embeddings {cfg.max_position_embeddings}")
-    if tok.dim() != 1 or pos.shape != tok.shape:
-        raise ValueError("packed token ids and positions must be [T] tensors of one size")
+    encoder.check_length(cfg, max_len)
+    encoder.check_packed(tok, pos)
     x = _embed(plm, tok, cd)
     return _encode_rows(plm, x, None, max_len, cd, training, gradient_checkpointing, weights, (pos.to(torch.int32), cu_seqlens, max_len))

@@ -23,10 +23,10 @@ form of this encoder (DESIGN.md section 4 "MPNet encoder").
 from __future__ import annotations
 
 import torch
-from torch.utils.checkpoint import checkpoint
 
-from . import ops
-from .dense import _mm, encoder_operands
+from . import encoder, ops
+from .dense import _mm
+from .encoder import LayerWeights  # noqa: F401  (an MPNet layer's weights are a BERT layer's)
 
 HEAD_DIM = 64
 NUM_BUCKETS = 32      # hf: compute_position_bias always buckets with 32, whatever relative_attention_num_buckets says
@@ -121,32 +121,14 @@ def bias_table(weight: torch.Tensor, m: int) -> torch.Tensor:
 # ---------------------------------------------------------------------------------------------
 # weights and layers
 # ---------------------------------------------------------------------------------------------
-class LayerWeights:
-    """Per-forward view of one MPNetLayer: the GEMM operands in the compute dtype (``w*`` / ``bqkv``, no autograd history) next
-    to the fp32 masters their gradients go to (``dense._mm``), as ``bert.LayerWeights``."""
-    __slots__ = ("wqkv", "bqkv", "wo", "wi", "wo2", "m_qkv", "m_wo", "m_wi", "m_wo2", "bo", "bi", "bo2", "ln1w", "ln1b",
-                 "ln2w", "ln2b")
+def _layer_masters(layer):
+    sa = layer.attention.attn
+    return [sa.q.weight, sa.k.weight, sa.v.weight], [sa.q.bias, sa.k.bias, sa.v.bias], sa.o, layer.attention.LayerNorm
 
 
 def prepare_weights(plm, cd, gemm_precision="native"):
-    """One flat buffer in the compute dtype for all layers' GEMM weights, filled by ONE multi-tensor copy; q / k / v rows land in
-    one fused [3P, P] operand.  ``gemm_precision`` "bf16x3" (fp32 only): the operands become ``dense.SplitWeight`` objects."""
-    out, specs = [], []
-    for i, layer in enumerate(plm.encoder.layer):
-        sa, att = layer.attention.attn, layer.attention
-        wq, bq = [sa.q.weight, sa.k.weight, sa.v.weight], [sa.q.bias, sa.k.bias, sa.v.bias]
-        wo, wi, wo2 = sa.o.weight, layer.intermediate.dense.weight, layer.output.dense.weight
-        specs += [((i, "wqkv"), wq, 0), ((i, "bqkv"), bq, 0), ((i, "wo"), [wo], 0), ((i, "wi"), [wi], 0), ((i, "wo2"), [wo2], 0)]
-        lw = LayerWeights()
-        lw.m_qkv, lw.m_wo, lw.m_wi, lw.m_wo2 = tuple(wq) + tuple(bq), (wo,), (wi,), (wo2,)
-        lw.bo, lw.bi, lw.bo2 = sa.o.bias, layer.intermediate.dense.bias, layer.output.dense.bias
-        lw.ln1w, lw.ln1b = att.LayerNorm.weight, att.LayerNorm.bias
-        lw.ln2w, lw.ln2b = layer.output.LayerNorm.weight, layer.output.LayerNorm.bias
-        out.append(lw)
-    operands = encoder_operands(specs, cd, gemm_precision)
-    for i, lw in enumerate(out):
-        lw.wqkv, lw.bqkv, lw.wo, lw.wi, lw.wo2 = (operands[(i, k)] for k in ("wqkv", "bqkv", "wo", "wi", "wo2"))
-    return out
+    """``encoder.prepare_weights`` over the MPNetLayers."""
+    return encoder.prepare_weights(plm.encoder.layer, _layer_masters, cd, gemm_precision)
 
 
 def _layer(lw, h, table, lens, heads, training, p_hidden, p_attn, eps, cu=None, max_len=0):
@@ -156,16 +138,12 @@ def _layer(lw, h, table, lens, heads, training, p_hidden, p_attn, eps, cu=None, 
         ctx = ops.attention_relbias_qkv_varlen(qkv, table, cu, max_len, heads, scale, p_attn, training)
     else:
         ctx = ops.attention_relbias_qkv(qkv, table, lens, heads, scale, p_attn, training)
-    a = ops.bias_res_layernorm(_mm(ctx, lw.wo, None, lw.m_wo), lw.bo, h_res, lw.ln1w, lw.ln1b, eps, False, p_hidden, training)
-    m_pre, a_res = _mm(a, lw.wi, None, lw.m_wi, residual=True)
-    m = ops.bias_gelu(m_pre, lw.bi)
-    return ops.bias_res_layernorm(_mm(m, lw.wo2, None, lw.m_wo2), lw.bo2, a_res, lw.ln2w, lw.ln2b, eps, False, p_hidden, training)
+    return encoder.post_ln_tail(lw, ctx, h_res, training, p_hidden, eps)
 
 
 def _encode_rows(plm, x, lens, max_len, cd, training, gradient_checkpointing, weights, *packed):
     """Embedding LayerNorm + dropout and the layers over the embedding rows ``x`` in ``cd`` ([B, L, P] with ``lens``, or [T, P]
-    with ``packed`` = (cu_seqlens, max_len)); all layers read ONE bias table, so its gradient is the sum over the layers; a
-    checkpointed layer is recomputed with the very arguments it ran with."""
+    with ``packed`` = (cu_seqlens, max_len)); all layers read ONE bias table, so its gradient is the sum over the layers."""
     cfg = plm.config
     emb = plm.embeddings
     eps, p_hidden, p_attn = cfg.layer_norm_eps, cfg.hidden_dropout_prob, cfg.attention_probs_dropout_prob
@@ -174,12 +152,8 @@ def _encode_rows(plm, x, lens, max_len, cd, training, gradient_checkpointing, we
     if weights is None:
         weights = prepare_weights(plm, cd)
     table = bias_table(plm.encoder.relative_attention_bias.weight, max(int(max_len), 1))
-    for lw in weights:
-        if gradient_checkpointing and training and torch.is_grad_enabled():
-            h = checkpoint(_layer, lw, h, table, lens, heads, training, p_hidden, p_attn, eps, *packed, use_reentrant=False)
-        else:
-            h = _layer(lw, h, table, lens, heads, training, p_hidden, p_attn, eps, *packed)
-    return h
+    args = (table, lens, heads, training, p_hidden, p_attn, eps, *packed)
+    return encoder.run_layers(_layer, weights, h, args, training, gradient_checkpointing)
 
 
 def position_ids(l: int, padding_idx: int, device=None) -> torch.Tensor:
@@ -210,8 +184,7 @@ def mpnet_encode_packed(plm, tok: torch.Tensor, pos: torch.Tensor, cu_seqlens: t
     emb = plm.embeddings
     max_len = int(max_len)
     _check_length(plm.config, max_len)
-    if tok.dim() != 1 or pos.shape != tok.shape:
-        raise ValueError("packed token ids and positions must be [T] tensors of one size")
+    encoder.check_packed(tok, pos)
     word = emb.word_embeddings.weight
     # word + position rows in one pass (fp32 sum, stored as cd); the kernel's type-0 row is a zero row here
     x = ops.embed_sum(tok, pos.long() + (emb.padding_idx + 1), word, emb.position_embeddings.weight, word.new_zeros(1, word.shape[1]), cd)

@@ -952,12 +952,13 @@ def bias_gelu(x, bias, p=0.0, training=False):
 # ---------------------------------------------------------------------------------------------
 # Pre-norm decoder-style encoder (Qwen3 geometry): add + RMSNorm, Q/K head norm + RoPE, SwiGLU, causal GQA attention
 # ---------------------------------------------------------------------------------------------
-class AddRMSNorm(torch.autograd.Function):
-    """(s, y) with s = a + b in the compute dtype (``b`` None: s is ``a``) and y = s * rsqrt(mean(s^2) + eps) * w.
-    ``s`` is the residual stream handed to the next add; its gradient and y's meet in ONE backward kernel."""
+class _AddNorm(torch.autograd.Function):
+    """(s, y) with s = a + b in the compute dtype (``b`` None: s is ``a``) and y = norm(s) * w (+ ``beta``, may be None).
+    ``s`` is the residual stream handed to the next add; its gradient and y's meet in ONE backward kernel.
+    ``ln``: LayerNorm (gmlm_add_layernorm_*: a row mean is saved beside rstd, ``beta`` is taken), else RMSNorm (gmlm_add_rmsnorm_*)."""
 
     @staticmethod
-    def forward(ctx, a, b, w, eps):
+    def forward(ctx, ln, a, b, w, beta, eps):
         _cuda(a)
         shape = a.shape
         f = shape[-1]
@@ -967,36 +968,48 @@ class AddRMSNorm(torch.autograd.Function):
         wf = _f32c(w)
         s2 = torch.empty_like(a2) if b2 is not None else None
         y = torch.empty_like(a2)
-        rstd = torch.empty(rows, dtype=torch.float32, device=a.device)
-        check(lib().gmlm_add_rmsnorm_fwd(_ptr(a2), _ptr(b2), _ptr(wf), rows, f, float(eps), _ptr(s2), _ptr(y), _ptr(rstd),
-                                         _dt(a2), _stream()), "gmlm_add_rmsnorm_fwd")
+        if ln:
+            bf = None if beta is None else _f32c(beta)
+            stats = torch.empty(2, rows, dtype=torch.float32, device=a.device)          # mean | rstd
+            check(lib().gmlm_add_layernorm_fwd(_ptr(a2), _ptr(b2), _ptr(wf), _ptr(bf), rows, f, float(eps), _ptr(s2), _ptr(y),
+                                               _ptr(stats[0]), _ptr(stats[1]), _dt(a2), _stream()), "gmlm_add_layernorm_fwd")
+        else:
+            stats = torch.empty(rows, dtype=torch.float32, device=a.device)             # rstd
+            check(lib().gmlm_add_rmsnorm_fwd(_ptr(a2), _ptr(b2), _ptr(wf), rows, f, float(eps), _ptr(s2), _ptr(y), _ptr(stats),
+                                             _dt(a2), _stream()), "gmlm_add_rmsnorm_fwd")
         if s2 is None:
             s2 = a2
-        ctx.save_for_backward(s2, wf, rstd)
-        ctx.cfg = (shape, b is not None)
+        ctx.save_for_backward(s2, wf, stats)
+        ctx.cfg = (ln, shape, b is not None, beta is not None)
         return (s2.view(shape) if b is not None else a.view_as(a)), y.view(shape)
 
     @staticmethod
     def backward(ctx, gs, gy):
-        s2, wf, rstd = ctx.saved_tensors
-        shape, has_b = ctx.cfg
+        s2, wf, stats = ctx.saved_tensors
+        ln, shape, has_b, has_beta = ctx.cfg
         rows, f = s2.shape
         if gy is None:
             gy = torch.zeros_like(s2)
         gy2 = gy.contiguous().view(rows, f).to(s2.dtype)
         gs2 = None if gs is None else gs.contiguous().view(rows, f).to(s2.dtype)
         ds = torch.empty_like(s2)
-        dw = torch.empty(f, dtype=torch.float32, device=s2.device)
-        ws = _ws(lib().gmlm_add_rmsnorm_bwd_workspace_bytes(rows, f), s2.device)
-        check(lib().gmlm_add_rmsnorm_bwd(_ptr(gy2), _ptr(gs2), _ptr(s2), _ptr(wf), _ptr(rstd), rows, f, _ptr(ds), _ptr(dw),
-                                         _dt(s2), _ptr(ws), ws.numel(), _stream()), "gmlm_add_rmsnorm_bwd")
+        dw = torch.empty(2 if has_beta else 1, f, dtype=torch.float32, device=s2.device)   # dw (| dbeta): one buffer
+        if ln:
+            ws = _ws(lib().gmlm_add_layernorm_bwd_workspace_bytes(rows, f), s2.device)
+            check(lib().gmlm_add_layernorm_bwd(_ptr(gy2), _ptr(gs2), _ptr(s2), _ptr(wf), _ptr(stats[0]), _ptr(stats[1]), rows, f, _ptr(ds),
+                                               _ptr(dw), _ptr(dw[1]) if has_beta else None, _dt(s2), _ptr(ws), ws.numel(), _stream()),
+                  "gmlm_add_layernorm_bwd")
+        else:
+            ws = _ws(lib().gmlm_add_rmsnorm_bwd_workspace_bytes(rows, f), s2.device)
+            check(lib().gmlm_add_rmsnorm_bwd(_ptr(gy2), _ptr(gs2), _ptr(s2), _ptr(wf), _ptr(stats), rows, f, _ptr(ds), _ptr(dw),
+                                             _dt(s2), _ptr(ws), ws.numel(), _stream()), "gmlm_add_rmsnorm_bwd")
         ds = ds.view(shape)
-        return ds, (ds if has_b else None), dw, None
+        return None, ds, (ds if has_b else None), dw[0], (dw[1] if has_beta else None), None
 
 
 def add_rmsnorm(a, b, w, eps=1e-6):
     """-> (a + b, RMSNorm(a + b) * w); ``b`` may be None."""
-    return AddRMSNorm.apply(a, b, w, eps)
+    return _AddNorm.apply(False, a, b, w, None, eps)
 
 
 def _qkv_rows(qkv: torch.Tensor, width: int):
@@ -1293,33 +1306,36 @@ def rope_causal_attention_varlen(qkv, q_weight, k_weight, cos_sin, pos_ids, cu_s
     return RopeCausalAttentionVarlen.apply(qkv, q_weight, k_weight, cos_sin, pos_ids, cu_seqlens, max_len, hq, hkv, scale, eps)
 
 
-class SwiGLU(torch.autograd.Function):
-    """[..., 2 I] = [gate | up] -> silu(gate) * up [..., I]."""
+class _GLU(torch.autograd.Function):
+    """[..., 2 I] = [gate | up] -> act(gate) * up [..., I]; ``stem``: gmlm_<stem>_fwd / _bwd (swiglu: SiLU, geglu: erf GELU)."""
 
     @staticmethod
-    def forward(ctx, gu):
+    def forward(ctx, stem, gu):
         _cuda(gu)
         shape = gu.shape
         inter = shape[-1] // 2
         g2 = gu.contiguous().view(-1, 2 * inter)
         y = torch.empty(g2.shape[0], inter, dtype=gu.dtype, device=gu.device)
-        check(lib().gmlm_swiglu_fwd(_ptr(g2), g2.shape[0], inter, _ptr(y), _dt(g2), _stream()), "gmlm_swiglu_fwd")
+        name = f"gmlm_{stem}_fwd"
+        check(getattr(lib(), name)(_ptr(g2), g2.shape[0], inter, _ptr(y), _dt(g2), _stream()), name)
         ctx.save_for_backward(g2)
-        ctx.shape = shape
+        ctx.cfg = (stem, shape)
         return y.view(*shape[:-1], inter)
 
     @staticmethod
     def backward(ctx, gy):
         (g2,) = ctx.saved_tensors
+        stem, shape = ctx.cfg
         rows, inter = g2.shape[0], g2.shape[1] // 2
         gy2 = gy.contiguous().view(rows, inter).to(g2.dtype)
         dgu = torch.empty_like(g2)
-        check(lib().gmlm_swiglu_bwd(_ptr(gy2), _ptr(g2), rows, inter, _ptr(dgu), _dt(g2), _stream()), "gmlm_swiglu_bwd")
-        return dgu.view(ctx.shape)
+        name = f"gmlm_{stem}_bwd"
+        check(getattr(lib(), name)(_ptr(gy2), _ptr(g2), rows, inter, _ptr(dgu), _dt(g2), _stream()), name)
+        return None, dgu.view(shape)
 
 
 def swiglu(gate_up):
-    return SwiGLU.apply(gate_up)
+    return _GLU.apply("swiglu", gate_up)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1328,82 +1344,13 @@ def swiglu(gate_up):
 ADD_LAYERNORM_MAX_F = 4096       # GMLM_ADD_LAYERNORM_MAX_F (include/gmlm_hip_modernbert.h)
 
 
-class AddLayerNorm(torch.autograd.Function):
-    """(s, y) with s = a + b in the compute dtype (``b`` None: s is ``a``) and y = LayerNorm(s) * gamma (+ beta, may be None).
-    ``s`` is the residual stream handed to the next add; its gradient and y's meet in ONE backward kernel."""
-
-    @staticmethod
-    def forward(ctx, a, b, gamma, beta, eps):
-        _cuda(a)
-        shape = a.shape
-        f = shape[-1]
-        a2 = a.contiguous().view(-1, f)
-        b2 = None if b is None else b.to(a.dtype).contiguous().view(-1, f)
-        rows = a2.shape[0]
-        gf = _f32c(gamma)
-        bf = None if beta is None else _f32c(beta)
-        s2 = torch.empty_like(a2) if b2 is not None else None
-        y = torch.empty_like(a2)
-        stats = torch.empty(2, rows, dtype=torch.float32, device=a.device)          # mean | rstd
-        check(lib().gmlm_add_layernorm_fwd(_ptr(a2), _ptr(b2), _ptr(gf), _ptr(bf), rows, f, float(eps), _ptr(s2), _ptr(y),
-                                           _ptr(stats[0]), _ptr(stats[1]), _dt(a2), _stream()), "gmlm_add_layernorm_fwd")
-        if s2 is None:
-            s2 = a2
-        ctx.save_for_backward(s2, gf, stats)
-        ctx.cfg = (shape, b is not None, beta is not None)
-        return (s2.view(shape) if b is not None else a.view_as(a)), y.view(shape)
-
-    @staticmethod
-    def backward(ctx, gs, gy):
-        s2, gf, stats = ctx.saved_tensors
-        shape, has_b, has_beta = ctx.cfg
-        rows, f = s2.shape
-        if gy is None:
-            gy = torch.zeros_like(s2)
-        gy2 = gy.contiguous().view(rows, f).to(s2.dtype)
-        gs2 = None if gs is None else gs.contiguous().view(rows, f).to(s2.dtype)
-        ds = torch.empty_like(s2)
-        dw = torch.empty(2 if has_beta else 1, f, dtype=torch.float32, device=s2.device)   # dgamma | dbeta: one buffer
-        ws = _ws(lib().gmlm_add_layernorm_bwd_workspace_bytes(rows, f), s2.device)
-        check(lib().gmlm_add_layernorm_bwd(_ptr(gy2), _ptr(gs2), _ptr(s2), _ptr(gf), _ptr(stats[0]), _ptr(stats[1]), rows, f, _ptr(ds),
-                                           _ptr(dw), _ptr(dw[1]) if has_beta else None, _dt(s2), _ptr(ws), ws.numel(), _stream()),
-              "gmlm_add_layernorm_bwd")
-        ds = ds.view(shape)
-        return ds, (ds if has_b else None), dw[0], (dw[1] if has_beta else None), None
-
-
 def add_layernorm(a, b, gamma, beta=None, eps=1e-5):
     """-> (a + b, LayerNorm(a + b) * gamma + beta); ``b`` and ``beta`` may be None."""
-    return AddLayerNorm.apply(a, b, gamma, beta, eps)
-
-
-class GeGLU(torch.autograd.Function):
-    """[..., 2 I] = [gate | up] -> gelu(gate) * up [..., I] (erf GELU)."""
-
-    @staticmethod
-    def forward(ctx, u):
-        _cuda(u)
-        shape = u.shape
-        inter = shape[-1] // 2
-        u2 = u.contiguous().view(-1, 2 * inter)
-        y = torch.empty(u2.shape[0], inter, dtype=u.dtype, device=u.device)
-        check(lib().gmlm_geglu_fwd(_ptr(u2), u2.shape[0], inter, _ptr(y), _dt(u2), _stream()), "gmlm_geglu_fwd")
-        ctx.save_for_backward(u2)
-        ctx.shape = shape
-        return y.view(*shape[:-1], inter)
-
-    @staticmethod
-    def backward(ctx, gy):
-        (u2,) = ctx.saved_tensors
-        rows, inter = u2.shape[0], u2.shape[1] // 2
-        gy2 = gy.contiguous().view(rows, inter).to(u2.dtype)
-        du = torch.empty_like(u2)
-        check(lib().gmlm_geglu_bwd(_ptr(gy2), _ptr(u2), rows, inter, _ptr(du), _dt(u2), _stream()), "gmlm_geglu_bwd")
-        return du.view(ctx.shape)
+    return _AddNorm.apply(True, a, b, gamma, beta, eps)
 
 
 def geglu(u):
-    return GeGLU.apply(u)
+    return _GLU.apply("geglu", u)
 
 
 def rope64_(qkv, cos_sin, h, seq_len=0, pos_ids=None, inverse=False):

@@ -14,9 +14,8 @@ bucketed, short-sequence or ring form of this encoder (DESIGN.md section 4 "Qwen
 from __future__ import annotations
 
 import torch
-from torch.utils.checkpoint import checkpoint
 
-from . import ops
+from . import encoder, ops
 from .dense import _mm, encoder_operands
 
 
@@ -76,24 +75,9 @@ def check_supported(plm) -> None:
         raise NotImplementedError("gmlm_amd text-encoder kernels do not cover this PLM: " + "; ".join(problems))
 
 
-_ROPE_TABLES = {}
-
-
 def rope_table(cfg, max_len: int, device) -> torch.Tensor:
-    """fp32 [>= max_len, 2, 64]: cos and sin of position * inv_freq, computed as Qwen3RotaryEmbedding does (default rope type:
-    inv_freq = theta^(-2i/d) in fp32, the products and cos / sin in fp32).  Built ONCE per (device, theta, head dim) for
-    ``max_position_embeddings`` rows (a row depends on its position only, so every shorter sequence reads a prefix) and kept:
-    no host work and no host-to-device copy per encoder call."""
-    d, theta = head_dim(cfg), rope_theta(cfg)
-    device = torch.device(device)
-    rows = max(int(max_len), int(getattr(cfg, "max_position_embeddings", 0) or 0))
-    key = (device.type, device.index, theta, d)
-    hit = _ROPE_TABLES.get(key)
-    if hit is None or hit.shape[0] < rows:
-        inv_freq = 1.0 / (theta ** (torch.arange(0, d, 2, dtype=torch.int64).to(dtype=torch.float) / d))
-        freqs = torch.arange(rows, dtype=torch.float32)[:, None] * inv_freq[None, :]
-        hit = _ROPE_TABLES[key] = torch.stack([freqs.cos(), freqs.sin()], 1).contiguous().to(device)
-    return hit
+    """fp32 [>= max_len, 2, 64]: ``encoder.rope_table`` for Qwen3RotaryEmbedding's theta and head dim."""
+    return encoder.rope_table(rope_theta(cfg), head_dim(cfg), encoder.table_rows(cfg, max_len), device)
 
 
 class LayerWeights:
@@ -149,26 +133,21 @@ def qwen3_encode(plm, input_ids: torch.Tensor, lens: torch.Tensor, cd: torch.dty
     ``lens[b]`` are computed but never read by the pooling.  ``weights``: optional ``prepare_weights(plm, cd)`` result."""
     cfg = plm.config
     b, l = input_ids.shape
-    if l > cfg.max_position_embeddings:
-        raise ValueError(f"sequence length {l} exceeds max_position_embeddings {cfg.max_position_embeddings}")
+    encoder.check_length(cfg, l)
     x = torch.nn.functional.embedding(input_ids.long(), plm.embed_tokens.weight).to(cd)   # bit-exact row gather
     return _encode_rows(plm, x, lens, rope_table(cfg, l, x.device), cd, training, gradient_checkpointing, weights)
 
 
 def _encode_rows(plm, x, lens, cs, cd, training, gradient_checkpointing, weights, *packed):
     """The layers and the final norm over the embedding rows ``x`` ([B, L, P] with ``lens``, or [T, P] with ``packed`` = the one
-    trailing argument of ``_layer``); a checkpointed layer is recomputed with the very arguments it ran with."""
+    trailing argument of ``_layer``)."""
     cfg = plm.config
     hq, hkv = cfg.num_attention_heads, cfg.num_key_value_heads
     eps, scale = cfg.rms_norm_eps, head_dim(cfg) ** -0.5
     if weights is None:
         weights = prepare_weights(plm, cd)
-    stream, branch = x, None
-    for lw in weights:
-        if gradient_checkpointing and training and torch.is_grad_enabled():
-            stream, branch = checkpoint(_layer, lw, stream, branch, lens, cs, hq, hkv, scale, eps, *packed, use_reentrant=False)
-        else:
-            stream, branch = _layer(lw, stream, branch, lens, cs, hq, hkv, scale, eps, *packed)
+    stream, branch = encoder.run_layers(_layer, weights, (x, None), (lens, cs, hq, hkv, scale, eps, *packed), training,
+                                        gradient_checkpointing)
     return ops.add_rmsnorm(stream, branch, plm.norm.weight, eps)[1]
 
 
@@ -181,10 +160,8 @@ def qwen3_encode_packed(plm, tok: torch.Tensor, pos: torch.Tensor, cu_seqlens: t
     embedding reads its table row by ``pos`` and the attention resolves its rows through ``cu_seqlens``."""
     cfg = plm.config
     max_len = int(max_len)
-    if max_len > cfg.max_position_embeddings:
-        raise ValueError(f"sequence length {max_len} exceeds max_position_embeddings {cfg.max_position_embeddings}")
-    if tok.dim() != 1 or pos.shape != tok.shape:
-        raise ValueError("packed token ids and positions must be [T] tensors of one size")
+    encoder.check_length(cfg, max_len)
+    encoder.check_packed(tok, pos)
     x = torch.nn.functional.embedding(tok.long(), plm.embed_tokens.weight).to(cd)   # bit-exact row gather
     cs = rope_table(cfg, max_len, x.device)
     return _encode_rows(plm, x, None, cs, cd, training, gradient_checkpointing, weights, (pos.to(torch.int32), cu_seqlens, max_len))

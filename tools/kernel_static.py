@@ -1,6 +1,7 @@
 """Static comparison of the gfx950 kernels of two builds of libgmlm_hip.so (no GPU needed): per kernel the symbol, the
-VGPR count (AGPRs included), LDS bytes, scratch bytes, and the number of v_mfma / scratch_ / packed-fp32 instructions, from
-the code objects' metadata and disassembly.
+VGPR count (AGPRs included), LDS bytes, scratch bytes, the number of v_mfma / scratch_ / packed-fp32 instructions, and
+``body_sha1``: a hash of the disassembled instruction stream (mnemonics and operands; addresses, encodings and symbol offsets
+stripped), from the code objects' metadata and disassembly.  Equal hashes = the same instructions in the same order.
 
     python tools/kernel_static.py --parent PARENT/libgmlm_hip.so --new gmlm_amd/libgmlm_hip.so \
         --match 'attn_|d128::' --added 'causal128::|rmsnorm_|qknorm_rope_|swiglu_' --out profiles/attn_causal_static.json
@@ -64,10 +65,13 @@ def kernels(so):
                 sym, body = m.group(1), m.group(2)
                 if sym not in meta:
                     continue
-                ops = re.findall(r"^\s*(\S+)", re.sub(r"//.*", "", body), re.M)
+                text = re.sub(r"//.*", "", body)                    # the comment holds the address, the encoding and <symbol+offset>
+                ops = re.findall(r"^\s*(\S+)", text, re.M)
+                stream = "\n".join(" ".join(ln.split()) for ln in text.splitlines() if ln.strip())
                 d = dict(meta[sym])
                 d.update(v_mfma=sum(o.startswith("v_mfma") for o in ops), scratch_instr=sum(o.startswith("scratch_") for o in ops),
                          packed_f32=sum(bool(re.match(r"v_pk_\w+_f32", o)) for o in ops), instructions=len(ops),
+                         body_sha1=hashlib.sha1(stream.encode()).hexdigest()[:16],
                          waves_per_simd=min(8, 512 // ((meta[sym]["vgpr"] + 7) // 8 * 8)) if meta[sym]["vgpr"] else 8)
                 res[sym] = d
     names = demangle(list(res))
@@ -87,7 +91,7 @@ def main():
     ap.add_argument("--compact", action="store_true", help="one short line per kernel (unchanged kernels: name and figures once)")
     a = ap.parse_args()
     old, new = kernels(a.parent), kernels(a.new)
-    keys = ("symbol", "vgpr", "lds_bytes", "scratch_bytes", "v_mfma", "scratch_instr", "packed_f32", "instructions")
+    keys = ("symbol", "vgpr", "lds_bytes", "scratch_bytes", "v_mfma", "scratch_instr", "packed_f32", "instructions", "body_sha1")
     rows, bad = [], 0
     for name in sorted(k for k in old if re.search(a.match, k)):
         o, n = old[name], new.get(name)
