@@ -1,5 +1,5 @@
 """ctypes binding of libgmlm_hip.so (C ABI: include/gmlm_hip.h, gmlm_hip_split.h, gmlm_hip_optim.h, gmlm_hip_d32.h,
-gmlm_hip_wide.h, gmlm_hip_modernbert.h and gmlm_hip_relbias.h): one signature table per header, positional argument types only.  Which attention entry point a head dim
+gmlm_hip_wide.h, gmlm_hip_modernbert.h, gmlm_hip_relbias.h and gmlm_hip_disent.h): one signature table per header, positional argument types only.  Which attention entry point a head dim
 takes, and where each ABI puts its arguments by name, is the family table of ops.py (``_ATTN_FAMILIES``).
 
 The product path has NO fallback: if the shared library is missing or a call fails, a Python
@@ -160,7 +160,17 @@ SIGNATURES_RELBIAS = {
 }
 
 # the headers added after the sixth: SIGNATURE_TABLES keeps the six that came with ABI version 1, lib() binds both tuples
-SIGNATURE_TABLES_LATER = (SIGNATURES_RELBIAS,)
+# eighth header, include/gmlm_hip_disent.h (disentangled self-attention at d = 64: DeBERTa-v2 / v3 encoders)
+SIGNATURES_DISENT = {
+    "gmlm_attention_disent_fwd": (C.c_int, [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _f32, _u64, _p,
+                                            _p, _p, _p, _i64, _i64, _p, _p, _p, _i32, _p, _i64, _p]),
+    "gmlm_attention_disent_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
+    "gmlm_attention_disent_bwd": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32,
+                                            _f32, _u64, _p, _p, _p, _p, _i64, _i64, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i32, _p,
+                                            _i64, _p, _sz, _p]),
+}
+
+SIGNATURE_TABLES_LATER = (SIGNATURES_RELBIAS, SIGNATURES_DISENT)
 
 
 class GmlmHipError(RuntimeError):

@@ -9,6 +9,32 @@
 
 namespace gmlm {
 
+// Operands of the DISENT score mode (disentangled attention, attn_disent.hip): two fp32 tables [h, rows, w] with one row of `w`
+// columns per (head, token), rows = all token rows of the call in memory order (what a GEMM batched over the heads writes), and
+// the column table col[2m - 1], col[m - 1 + (i - j)] = the column that query i and key j of one sequence read in BOTH tables.
+// An index past the column table and a column past the row are clamped: whatever the table holds, no load leaves the operands.
+struct DisentTabs {
+  const float* c;        // [h, rows, w]  content-to-position: row of the query
+  const float* pt;       // [h, rows, w]  position-to-content: row of the key
+  const int32_t* col;    // [2m - 1]
+  int m, w;
+};
+__device__ __forceinline__ int disent_col(const DisentTabs& t, int delta) {
+  int idx = t.m - 1 + delta;
+  idx = idx < 0 ? 0 : (idx > 2 * t.m - 2 ? 2 * t.m - 2 : idx);
+  const int c = t.col[idx];
+  return c < 0 ? 0 : (c > t.w - 1 ? t.w - 1 : c);
+}
+// element offset of the table row of head hd and token row `row` (counted over the whole call: qbase + position)
+__device__ __forceinline__ int64_t disent_row(const AttnParams& p, const DisentTabs& t, int64_t hd, int64_t row) {
+  return (hd * (p.cu ? p.lq : p.b * p.lq) + row) * t.w;
+}
+// C[query row][col] + Pt[key row][col]; crow / prow point at the two rows
+__device__ __forceinline__ float disent_term(const DisentTabs& t, const float* crow, const float* prow, int delta) {
+  const int c = disent_col(t, delta);
+  return crow[c] + prow[c];
+}
+
 // ------------------------------------------------------------------------------------------------
 // forward
 // ------------------------------------------------------------------------------------------------
@@ -27,13 +53,21 @@ namespace gmlm {
 //   domain right behind the QK^T chain, s' = s * scale * log2 e + bias * log2 e, and everything after it (running max,
 //   deferral, exponentials) works on s' with a unit factor.  An index past the table (a padded query row or key) is clamped;
 //   such a pair is masked or never stored.
+// DISENT (lq == lk): the score of query i and key j gets C[row i][col[i - j]] + Pt[row j][col[i - j]] BEFORE the scale (struct
+//   DisentTabs above), s' = (s + C + Pt) * scale * log2 e right behind the QK^T chain, and everything after it works on s' as
+//   with BIAS.  The row of a query or key past its sequence is clamped into the sequence; such a pair is masked or never stored.
+//   Dropout: the P V product takes P * (0 or 1) and the keep scale multiplies the output once, with 1 / l (bf16: the scaled
+//   probability is never rounded, so O and the backward's delta = rowsum(dO * O) agree with D * dP to fp32 rounding; a row
+//   with one key, P = 1, then has dS = 0 as it must).
 template <typename T, int D, int NW, bool DROP, int KT, bool DBUF, bool CAUSAL = false, bool GQA = false, bool WINDOW = false,
-          bool BIAS = false>
+          bool BIAS = false, bool DISENT = false>
 __device__ __forceinline__ void attn_fwd_body(const AttnParams& p, int64_t tile, int64_t b, int64_t hd, int64_t o_stride,
                                               int64_t kvh = 0, int64_t window = 0, const float* rel_bias = nullptr,
-                                              int rel_m = 0) {
+                                              int rel_m = 0, const DisentTabs* dt = nullptr) {
   static_assert(!(WINDOW && (CAUSAL || DROP)), "the band mask has no causal or dropout form");
   static_assert(!(BIAS && (CAUSAL || GQA || WINDOW)), "the relative-position bias has no causal, grouped or band form");
+  static_assert(!(DISENT && (CAUSAL || GQA || WINDOW || BIAS)), "the disentangled terms have no causal, grouped, band or bias form");
+  constexpr bool PRE = BIAS || DISENT;       // the scores are in the log2 domain before the running max
   constexpr int KB = KT / 32, NT = NW * 64, PITCH = D + Pad<T>::v, DB = D / 32, NBUF = DBUF ? 2 : 1;
   __shared__ __attribute__((aligned(16))) T ks[NBUF][KT * PITCH];
   __shared__ __attribute__((aligned(16))) T vs[NBUF][KT * PITCH];
@@ -103,6 +137,15 @@ __device__ __forceinline__ void attn_fwd_body(const AttnParams& p, int64_t tile,
           s[kb][i] = fmaf(s[kb][i], sl2, bh[rel] * kLog2e);
         }
       }
+      if constexpr (DISENT) {
+        const float* crow = dt->c + disent_row(p, *dt, hd, qbase + (q_ok ? q_row : 0));
+        const int qi_ = (int)(q_row < (1 << 30) ? q_row : (1 << 30));
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          const int key = (int)kv0 + kb * 32 + acc_row(i, h), kc = key < (int)lk_ ? key : (int)lk_ - 1;   // lk_ > 0 inside the loop
+          s[kb][i] = (s[kb][i] + disent_term(*dt, crow, dt->pt + disent_row(p, *dt, hd, kbase + kc), qi_ - key)) * sl2;
+        }
+      }
     }
     float rmax = -INFINITY;
     // whole tile valid (block-uniform; causal: and below the diagonal; window: and inside the band of all 32 rows of the
@@ -127,7 +170,7 @@ __device__ __forceinline__ void attn_fwd_body(const AttnParams& p, int64_t tile,
     rmax = xhalf_max(rmax);
     // deferred rescale: keep the old reference max while the new one exceeds it by < 2^kDefer (probabilities
     // then stay <= 2^kDefer, harmless in fp32 / bf16); the O and l rescale is skipped for the whole wave then
-    float m_new = fmaxf(m, BIAS ? rmax : rmax * sl2);             // finite: key kv0 is always valid (WINDOW: -inf while the row has seen no key)
+    float m_new = fmaxf(m, PRE ? rmax : rmax * sl2);             // finite: key kv0 is always valid (WINDOW: -inf while the row has seen no key)
     // WINDOW: a row still at -inf that stays there changes nothing (-inf - -inf would be NaN and end the deferral for the wave)
     const bool keep = __all((WINDOW && m_new == -INFINITY) || m_new - m <= kDefer);   // m = -inf (first tile) -> false
     float alpha = 1.f;
@@ -139,12 +182,12 @@ __device__ __forceinline__ void attn_fwd_body(const AttnParams& p, int64_t tile,
     for (int kb = 0; kb < KB; ++kb)
 #pragma unroll
       for (int i = 0; i < 16; i += 2) {
-        const float e0 = fast_exp2(BIAS ? s[kb][i] - m_ref : fmaf(s[kb][i], sl2, -m_ref));       // masked: exp2(-inf) = 0
-        const float e1 = fast_exp2(BIAS ? s[kb][i + 1] - m_ref : fmaf(s[kb][i + 1], sl2, -m_ref));
+        const float e0 = fast_exp2(PRE ? s[kb][i] - m_ref : fmaf(s[kb][i], sl2, -m_ref));       // masked: exp2(-inf) = 0
+        const float e1 = fast_exp2(PRE ? s[kb][i + 1] - m_ref : fmaf(s[kb][i + 1], sl2, -m_ref));
         rsum += e0 + e1;                                               // the normaliser uses the un-dropped probabilities
         if (DROP) {
           float m0, m1;                                // keys (k, k+1): (kv0 + kb*32 + acc_row(i, 0)) >> 1 pairs on from the tile start
-          drop_pair_q(dq_u + ((uint32_t)(t * (KT / 2)) + (uint32_t)((kb * 32 + acc_row(i, 0)) >> 1)) * kDropC2, q_odd, p.drop_thresh, p.keep_scale, m0, m1);
+          drop_pair_q(dq_u + ((uint32_t)(t * (KT / 2)) + (uint32_t)((kb * 32 + acc_row(i, 0)) >> 1)) * kDropC2, q_odd, p.drop_thresh, DISENT ? 1.f : p.keep_scale, m0, m1);
           s[kb][i] = e0 * m0;
           s[kb][i + 1] = e1 * m1;
         } else {
@@ -180,7 +223,7 @@ __device__ __forceinline__ void attn_fwd_body(const AttnParams& p, int64_t tile,
     }
   }
   if (q_ok) {
-    const float inv = l > 0.f ? 1.f / l : 0.f;
+    const float inv = l > 0.f ? (DISENT && DROP ? p.keep_scale : 1.f) / l : 0.f;
     T* og = static_cast<T*>(p.o_w) + (qbase + q_row) * o_stride + hd * D;
 #pragma unroll
     for (int d = 0; d < DB; ++d) store_t<T>(og + d * 32, o[d], inv, h);
@@ -243,13 +286,17 @@ __device__ __forceinline__ void attn_delta_body(const T* __restrict__ o, const T
 // lse = -inf: it is given probability 0 everywhere, like a row past the sequence (dQ = 0).
 // BIAS as in attn_fwd_body: bias * log2 e is added to the exponent (bf16: to what leaves the MFMA chain, where a masked key
 // still sits near -2^100); dQ itself has no bias term.  The gradient of the table is a kernel of its own (attn_relbias.hip).
+// DISENT as in attn_fwd_body: (C + Pt) * scale * log2 e takes the place of bias * log2 e; dQ is the content-content part only,
+// the gradients of the two tables are kernels of their own (attn_disent.hip).
 template <typename T, int D, int NW, bool DROP, int KT, bool DBUF, bool CAUSAL = false, bool GQA = false, bool WINDOW = false,
-          bool BIAS = false>
+          bool BIAS = false, bool DISENT = false>
 __device__ __forceinline__ void attn_dq_body(const AttnParams& p, int64_t tile, int64_t b, int64_t hd, int64_t o_stride,
                                              int64_t kvh = 0, int64_t window = 0, const float* rel_bias = nullptr,
-                                             int rel_m = 0) {
+                                             int rel_m = 0, const DisentTabs* dt = nullptr) {
   static_assert(!(WINDOW && (CAUSAL || DROP)), "the band mask has no causal or dropout form");
   static_assert(!(BIAS && (CAUSAL || GQA || WINDOW)), "the relative-position bias has no causal, grouped or band form");
+  static_assert(!(DISENT && (CAUSAL || GQA || WINDOW || BIAS)), "the disentangled terms have no causal, grouped, band or bias form");
+  constexpr bool PRE = BIAS || DISENT;       // an additive exponent term b0 / b1 per score
   constexpr int KB = KT / 32, NT = NW * 64, PITCH = D + Pad<T>::v, DB = D / 32, NBUF = DBUF ? 2 : 1;
   __shared__ __attribute__((aligned(16))) T ks[NBUF][KT * PITCH];
   __shared__ __attribute__((aligned(16))) T vs[NBUF][KT * PITCH];
@@ -366,14 +413,20 @@ __device__ __forceinline__ void attn_dq_body(const AttnParams& p, int64_t tile, 
           b0 = bh[rel < lo ? lo : (rel > hi ? hi : rel)] * kLog2e;
           b1 = bh[rel + 1 < lo ? lo : (rel + 1 > hi ? hi : rel + 1)] * kLog2e;
         }
+        if constexpr (DISENT) {
+          const float* crow = dt->c + disent_row(p, *dt, hd, qbase + qr);
+          const int key = (int)kv0 + kb * 32 + acc_row(i, h), last = (int)lk_ - 1;   // each key row clamped on its own
+          b0 = disent_term(*dt, crow, dt->pt + disent_row(p, *dt, hd, kbase + (key < last ? key : last)), qi - key) * sl2;
+          b1 = disent_term(*dt, crow, dt->pt + disent_row(p, *dt, hd, kbase + (key + 1 < last ? key + 1 : last)), qi - key - 1) * sl2;
+        }
         if constexpr (FOLD) {
-          p0 = fast_exp2(BIAS ? s[i] + b0 : s[i]);
-          p1 = fast_exp2(BIAS ? s[i + 1] + b1 : s[i + 1]);
+          p0 = fast_exp2(PRE ? s[i] + b0 : s[i]);
+          p1 = fast_exp2(PRE ? s[i + 1] + b1 : s[i + 1]);
         } else {
           const int key = (int)kv0 + kb * 32 + acc_row(i, h);      // even; registers i, i+1 = keys key, key+1
           // a masked key gets exponent -inf through a select (no branch around the exp); whole blocks skip the test;
           // a query row past the sequence has lse = +inf, i.e. probability 0 everywhere
-          float a0 = fmaf(s[i], sl2, BIAS ? b0 - lse2 : -lse2), a1 = fmaf(s[i + 1], sl2, BIAS ? b1 - lse2 : -lse2);
+          float a0 = fmaf(s[i], sl2, PRE ? b0 - lse2 : -lse2), a1 = fmaf(s[i + 1], sl2, PRE ? b1 - lse2 : -lse2);
           if (!full) { a0 = key < kvl ? a0 : -INFINITY; a1 = key + 1 < kvl ? a1 : -INFINITY; }
           p0 = fast_exp2(a0); p1 = fast_exp2(a1);
         }
@@ -439,11 +492,15 @@ __device__ __forceinline__ void attn_dq_body(const AttnParams& p, int64_t tile, 
 // query with lse = -inf (no visible key) is staged with lse = +inf, i.e. probability 0, and adds nothing to dK or dV.
 // BIAS as in attn_dq_body, with the key on the lane: register i holds query q0 + qb * 32 + acc_row(i, h), so the table index
 // falls as i rises.
-template <typename T, int D, int NW, bool DROP, int QT, bool DBUF, bool WINDOW = false, bool BIAS = false>
+// DISENT as in attn_dq_body, with the key on the lane: the Pt row is the lane's own, the C row changes with the register.
+template <typename T, int D, int NW, bool DROP, int QT, bool DBUF, bool WINDOW = false, bool BIAS = false, bool DISENT = false>
 __device__ __forceinline__ void attn_dkv_body(const AttnParams& p, int64_t tile, int64_t b, int64_t hd, int64_t o_stride,
-                                              int64_t window = 0, const float* rel_bias = nullptr, int rel_m = 0) {
+                                              int64_t window = 0, const float* rel_bias = nullptr, int rel_m = 0,
+                                              const DisentTabs* dt = nullptr) {
   static_assert(!(WINDOW && DROP), "the band mask has no dropout form");
   static_assert(!(BIAS && WINDOW), "the relative-position bias has no band form");
+  static_assert(!(DISENT && (WINDOW || BIAS)), "the disentangled terms have no band or bias form");
+  constexpr bool PRE = BIAS || DISENT;       // an additive exponent term per score
   constexpr int NT = NW * 64, PITCH = D + Pad<T>::v, DB = D / 32, NBUF = DBUF ? 2 : 1;
   __shared__ __attribute__((aligned(16))) T qs[NBUF][QT * PITCH];
   __shared__ __attribute__((aligned(16))) T dos[NBUF][QT * PITCH];
@@ -583,7 +640,12 @@ __device__ __forceinline__ void attn_dkv_body(const AttnParams& p, int64_t tile,
               rel = rel < 1 - rel_m ? 1 - rel_m : (rel > rel_m - 1 ? rel_m - 1 : rel);
               bi = bh[rel] * kLog2e;
             }
-            float pr = fast_exp2(BIAS ? s[i] + bi : s[i]);
+            if constexpr (DISENT) {
+              const int qq = (int)q0 + qb * 32 + acc_row(i, h), last = (int)lq_ - 1;
+              bi = disent_term(*dt, dt->c + disent_row(p, *dt, hd, qbase + (qq < last ? qq : last)),
+                               dt->pt + disent_row(p, *dt, hd, kbase + kr_), qq - ki) * sl2;
+            }
+            float pr = fast_exp2(PRE ? s[i] + bi : s[i]);
             if constexpr (WINDOW) {
               if (edge) {                                      // a select, not a product: see attn_dq_body
                 const int qq = (int)q0 + qb * 32 + acc_row(i, h), wi = (int)window;
@@ -612,8 +674,14 @@ __device__ __forceinline__ void attn_dkv_body(const AttnParams& p, int64_t tile,
               b0 = bh[rel < lo ? lo : (rel > hi ? hi : rel)] * kLog2e;
               b1 = bh[rel - 1 < lo ? lo : (rel - 1 > hi ? hi : rel - 1)] * kLog2e;
             }
-            float p0 = FOLD ? fast_exp2(BIAS ? s[i] + b0 : s[i]) : fast_exp2(key_ok ? fmaf(s[i], sl2, BIAS ? b0 - lv[j] : -lv[j]) : -INFINITY);
-            float p1 = FOLD ? fast_exp2(BIAS ? s[i + 1] + b1 : s[i + 1]) : fast_exp2(key_ok ? fmaf(s[i + 1], sl2, BIAS ? b1 - lv[j + 1] : -lv[j + 1]) : -INFINITY);
+            if constexpr (DISENT) {
+              const int qq = (int)q0 + q4 + j, last = (int)lq_ - 1;       // each query row clamped on its own
+              const float* prow = dt->pt + disent_row(p, *dt, hd, kbase + kr_);
+              b0 = disent_term(*dt, dt->c + disent_row(p, *dt, hd, qbase + (qq < last ? qq : last)), prow, qq - ki) * sl2;
+              b1 = disent_term(*dt, dt->c + disent_row(p, *dt, hd, qbase + (qq + 1 < last ? qq + 1 : last)), prow, qq + 1 - ki) * sl2;
+            }
+            float p0 = FOLD ? fast_exp2(PRE ? s[i] + b0 : s[i]) : fast_exp2(key_ok ? fmaf(s[i], sl2, PRE ? b0 - lv[j] : -lv[j]) : -INFINITY);
+            float p1 = FOLD ? fast_exp2(PRE ? s[i + 1] + b1 : s[i + 1]) : fast_exp2(key_ok ? fmaf(s[i + 1], sl2, PRE ? b1 - lv[j + 1] : -lv[j + 1]) : -INFINITY);
             if constexpr (WINDOW) {
               if (edge) {
                 const int qq = (int)q0 + q4 + j, wi = (int)window;

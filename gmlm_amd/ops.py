@@ -1557,3 +1557,96 @@ def attention_relbias_qkv_varlen(qkv, rel_bias, cu_seqlens, max_len, num_heads, 
     with M >= max_len."""
     p = float(dropout_p) if training else 0.0
     return AttentionRelBiasQKV.apply(qkv, rel_bias, None, num_heads, scale, p, draw_seed() if p > 0 else 0, cu_seqlens, int(max_len))
+
+
+# ---------------------------------------------------------------------------------------------
+# disentangled self-attention at head dim 64 (DeBERTa-v2 / v3 encoders; include/gmlm_hip_disent.h)
+# ---------------------------------------------------------------------------------------------
+DISENT_MAX_LEN = 512      # GMLM_DISENT_MAX_LEN
+
+
+class AttentionDisentQKV(torch.autograd.Function):
+    """Self-attention on a fused QKV buffer whose scores are ``(q_i . k_j + c2p[i, h, c] + p2c[j, h, c]) * scale`` with
+    ``c = col[M - 1 + (i - j)]``, at head dim 64: c2p / p2c fp32 [h, rows of qkv, W], col int32 [2M - 1] with values in [0, W),
+    monotone, M >= the longest sequence.  Called like ``AttentionRelBiasQKV``:
+
+    padded mode: qkv [b, l, 3*h*64], tables [h, b * l, W], kv_len int32 [b] or None.
+    packed mode: qkv [total_rows, 3*h*64], tables [h, total_rows, W], cu_seqlens int32 [b+1], max_len = longest sequence.
+
+    Returns the context; the backward writes dq|dk|dv (the content-content parts) into ONE buffer of qkv's layout and returns the
+    gradients of the two tables (fp32, every entry written, fixed summation order)."""
+
+    @staticmethod
+    def forward(ctx, qkv, c2p, p2c, col, kv_len, h, scale, p, seed, cu_seqlens, max_len):
+        _cuda(qkv, c2p, p2c, col)
+        qkv = qkv.contiguous()
+        packed = cu_seqlens is not None
+        if packed:
+            _varlen_args(qkv, cu_seqlens, max_len)
+            l, hd3 = qkv.shape
+            b = cu_seqlens.numel() - 1
+        else:
+            b, l, hd3 = qkv.shape
+        hd = hd3 // 3
+        d = hd // h
+        if col.dtype != torch.int32 or col.dim() != 1 or col.numel() % 2 != 1:
+            raise ValueError("col must be an int32 [2M - 1] tensor")
+        m = (col.numel() + 1) // 2
+        want = (h, qkv.numel() // hd3 if hd3 else 0)
+        for name, t in (("c2p", c2p), ("p2c", p2c)):
+            if t.dtype != torch.float32 or t.dim() != 3 or tuple(t.shape[:2]) != want or t.shape != c2p.shape:
+                raise ValueError(f"{name} must be an fp32 [heads, rows, W] = {list(want)} + [W] tensor, one shape for both tables")
+        wcols = c2p.shape[-1]
+        c2p, p2c, col = c2p.detach().contiguous(), p2c.detach().contiguous(), col.contiguous()
+        q, k, v = qkv[..., :hd], qkv[..., hd:2 * hd], qkv[..., 2 * hd:]
+        out = torch.empty(qkv.shape[:-1] + (hd,), dtype=qkv.dtype, device=qkv.device)
+        lse = torch.empty((h, l) if packed else (b, h, l), dtype=torch.float32, device=qkv.device)
+        need_grad = any(ctx.needs_input_grad[:3])
+        out_lo = torch.empty_like(out) if (qkv.dtype == torch.bfloat16 and need_grad) else None
+        flops = 4.0 * h * d * (float(max_len) * l if packed else float(b) * l * l)
+        with _span("attn_disent_fwd_d%d" % d, flops=flops):
+            sd = ctx.sd = _sd()
+            check(lib().gmlm_attention_disent_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(kv_len), b, h, l, l, d, hd3, hd3, hd3, float(scale),
+                                                  float(p), seed, sd, _ptr(c2p), _ptr(p2c), _ptr(col), m, wcols, _ptr(out),
+                                                  _ptr(out_lo), _ptr(lse), _dt(qkv), _ptr(cu_seqlens), int(max_len), _stream()),
+                  "gmlm_attention_disent_fwd")
+        ctx.save_for_backward(qkv, c2p, p2c, col, lse, kv_len, cu_seqlens, out, out_lo)
+        ctx.cfg = (h, float(scale), float(p), seed, int(max_len), b, l, m, wcols, flops)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        qkv, c2p, p2c, col, lse, kv_len, cu_seqlens, out, out_lo = ctx.saved_tensors
+        h, scale, p, seed, max_len, b, l, m, wcols, flops = ctx.cfg
+        hd3 = qkv.shape[-1]
+        hd = hd3 // 3
+        d = hd // h
+        gout = gout.contiguous().to(qkv.dtype)
+        q, k, v = qkv[..., :hd], qkv[..., hd:2 * hd], qkv[..., 2 * hd:]
+        dqkv = torch.empty_like(qkv)
+        dq, dk, dv = dqkv[..., :hd], dqkv[..., hd:2 * hd], dqkv[..., 2 * hd:]
+        dc2p, dp2c = torch.empty_like(c2p), torch.empty_like(p2c)
+        ws = _ws(lib().gmlm_attention_disent_workspace_bytes(b, h, l, max_len if cu_seqlens is not None else 0), qkv.device)
+        with _span("attn_disent_bwd_d%d" % d, flops=4.5 * flops):          # the backward's five GEMMs + two of them twice again
+            check(lib().gmlm_attention_disent_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(out_lo), _ptr(gout), _ptr(lse),
+                                                  _ptr(kv_len), b, h, l, l, d, hd3, hd3, hd3, scale, p, seed, ctx.sd, _ptr(c2p),
+                                                  _ptr(p2c), _ptr(col), m, wcols, _ptr(dq), _ptr(dk), _ptr(dv), _ptr(dc2p),
+                                                  _ptr(dp2c), hd3, hd3, hd3, _dt(qkv), _ptr(cu_seqlens), max_len, ws.data_ptr(),
+                                                  ws.numel(), _stream()), "gmlm_attention_disent_bwd")
+        if b == 0 or l == 0:
+            dc2p.zero_()                                                     # a call with nothing to do launches nothing
+            dp2c.zero_()
+        return dqkv, dc2p, dp2c, None, None, None, None, None, None, None, None
+
+
+def attention_disent_qkv(qkv, c2p, p2c, col, kv_len, num_heads, scale, dropout_p=0.0, training=False):
+    """Padded form: qkv [b, l, 3 * h * 64], c2p / p2c fp32 [h, b * l, W], col int32 [2M - 1] with M >= l, kv_len int32 [b] or None."""
+    p = float(dropout_p) if training else 0.0
+    return AttentionDisentQKV.apply(qkv, c2p, p2c, col, kv_len, num_heads, scale, p, draw_seed() if p > 0 else 0, None, 0)
+
+
+def attention_disent_qkv_varlen(qkv, c2p, p2c, col, cu_seqlens, max_len, num_heads, scale, dropout_p=0.0, training=False):
+    """Packed form: qkv [T, 3 * h * 64], c2p / p2c fp32 [h, T, W], sequences by ``cu_seqlens`` (none longer than ``max_len``),
+    col int32 [2M - 1] with M >= max_len."""
+    p = float(dropout_p) if training else 0.0
+    return AttentionDisentQKV.apply(qkv, c2p, p2c, col, None, num_heads, scale, p, draw_seed() if p > 0 else 0, cu_seqlens, int(max_len))
