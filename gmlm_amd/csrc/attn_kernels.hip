@@ -181,12 +181,15 @@ extern "C" int gmlm_attention_bwd(const void* q, const void* k, const void* v, c
   if ((rc = attn_check_bwd_operands(who, p, h * d, h * d, dtype, workspace_bytes, attn_delta_bytes(nb, h, lq))) != GMLM_OK) return rc;
   hipStream_t st = as_stream(stream);
   const int64_t rows_q = cu_seqlens ? max_len : lq, rows_k = cu_seqlens ? max_len : lk;
-  if (dtype == GMLM_BF16 && d == 64 && rows_q <= 128 && rows_k <= 128 && b * h >= 512) {
-    // short sequences, enough of them to fill the chip: one fused launch (delta + dQ + dK/dV), no workspace, O is not read
+  if (dtype == GMLM_BF16 && d == 64 && rows_q <= 128 && rows_k <= 128 && b * h >= 512 && !out_lo) {
+    // short sequences, enough of them to fill the chip: one fused launch (delta + dQ + dK/dV), no workspace, O is not read.
+    // The kernel forms delta = sum_k P dP over ITS OWN keys, which equals rowsum(dO * O) only when `lse` is the log-sum-exp of
+    // exactly these keys.  A caller that hands in out_lo asks for delta = rowsum(dO * (out + out_lo)) - a ring block's `lse`
+    // and `out` are those of all keys (gmlm_hip.h) - and gets the streaming kernels below at any shape.
     const int64_t rmax = rows_q > rows_k ? rows_q : rows_k;
     return attn_short_bwd_launch(p, seq_groups ? 128 : rmax, seq_groups ? num_groups : b, dbias, st);
   }
-  GMLM_REQUIRE(!dbias, "%s: the fused bias-gradient sums exist only on the short-sequence path (bf16, d = 64, <= 128 rows, b*h >= 512)", who);
+  GMLM_REQUIRE(!dbias, "%s: the fused bias-gradient sums exist only on the short-sequence path (bf16, d = 64, <= 128 rows, b*h >= 512, no out_lo)", who);
   const int64_t rows = nb * lq * h;
   const int cpr = (int)d / (dtype == GMLM_BF16 ? 8 : 4);
   GMLM_ATTN_DELTA_LAUNCH(attn_delta_kernel, p, rows, cpr <= 8 ? 8 : (cpr <= 16 ? 16 : 32), st, (int)d, lq, h);

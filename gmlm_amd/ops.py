@@ -490,7 +490,8 @@ def _rows_view(t: torch.Tensor, h: int, d: int):
 
 def _short_path(dtype, d: int, rows: int, pairs: int) -> bool:
     """Same condition as the C entries: bf16, d = 64, every sequence <= 128 rows, >= 512 (sequence, head) pairs -> the
-    LDS-resident short-sequence kernels (their backward forms delta itself and needs neither ``out`` nor ``out_lo``)."""
+    LDS-resident short-sequence kernels (their backward forms delta itself and needs neither ``out`` nor ``out_lo``; the C
+    backward takes that path only when ``out_lo`` is NULL, which ``Attention`` / ``AttentionQKV`` pass there)."""
     return dtype == torch.bfloat16 and d == 64 and rows <= 128 and pairs >= 512
 
 
@@ -690,7 +691,13 @@ class AttentionQKV(torch.autograd.Function):
 class AttentionBlock:
     """Per-block arithmetic of the ring K|V exchange (gmlm_amd.dist._RingAttention) on the HIP kernels, outside
     autograd: ``fwd`` returns the block's normalised output and its log-sum-exp; ``bwd`` evaluates the block's share of
-    dQ / dK / dV from the GLOBAL output and log-sum-exp (P is recomputed as exp(S - lse_global), delta = rowsum(dO * O))."""
+    dQ / dK / dV from the GLOBAL output and log-sum-exp (P is recomputed as exp(S - lse_global), delta = rowsum(dO * O)).
+
+    Contract of ``bwd`` (gmlm_hip.h, "Foreign lse / out"): every path that forms delta from ``out`` accepts an ``lse`` and an
+    ``out`` that are not its own forward's - ``lse`` >= the block's own, ``out`` the output of all keys.  The short-sequence
+    path (bf16, d = 64, <= 128 rows, b*h >= 512) sums delta over the block's own keys and ASSUMES the block's own ``lse``; it
+    is selected only without ``out_lo``.  A bf16 ring block therefore always passes ``out_lo`` (``_RingAttention`` does);
+    without it the call is the plain backward of ``fwd``'s own ``out`` and ``lse``."""
 
     def __init__(self, num_heads: int, scale: float, dropout_p: float = 0.0):
         self.h, self.scale, self.p = num_heads, float(scale), float(dropout_p)

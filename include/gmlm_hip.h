@@ -238,9 +238,15 @@ int gmlm_bias_res_layernorm_bwd(const void* dy, const void* x, const float* bias
  * nn.Dropout on `attn` in main.py:161 / hf eager attention; the mask is hash(seed, (b,h,q,key)) and
  * is regenerated, not stored, by the backward pass when given the same seed.
  * Short sequences: bf16, d = 64, every sequence <= 128 rows (lq, lk <= 128, or max_len <= 128 in packed mode) and
- * b*h >= 512 runs with Q / K / V (/ dO) of a work item resident in LDS; the backward is ONE launch (delta + dQ + dK/dV)
- * that forms delta = sum_k P dP from its own fp32 P, dP (it does not read `out`); everything else runs the streaming
- * forward and three backward launches (delta = rowsum(dO * O), dQ, dK/dV).
+ * b*h >= 512 runs with Q / K / V (/ dO) of a work item resident in LDS; the backward - selected only when out_lo is NULL -
+ * is ONE launch (delta + dQ + dK/dV) that forms delta = sum_k P dP from its own fp32 P, dP (it does not read `out`);
+ * everything else runs the streaming forward and three backward launches (delta = rowsum(dO * O), dQ, dK/dV).
+ * Foreign lse / out (ring blocks, ops.AttentionBlock): on every backward path that forms delta from `out`, lse and out need
+ * not be this call's own forward's.  lse may be any value >= the log-sum-exp of the keys given and out (+ out_lo) the output
+ * of ALL keys, of which k / v are a part: P = exp(S - lse) is then the global softmax restricted to these keys, and dq / dk /
+ * dv are their share of the gradients.  The short-sequence backward sums delta over its own keys and therefore ASSUMES its own
+ * lse; with another it returns finite, wrong dq / dk.  A caller with a foreign lse passes out_lo (bf16), which keeps the call
+ * on the streaming kernels at any shape; in fp32 no short-sequence path exists.
  * seq_groups (packed mode, optional; int32 [num_groups + 1], device): work item g of the short-sequence kernels is the run
  * of sequences [seq_groups[g], seq_groups[g+1]) - at most 13 sequences and 128 rows in total (the caller guarantees both;
  * rows past 128 would be ignored) - attended block-diagonally.  Ignored by the streaming kernels.  With dropout, a work
@@ -254,7 +260,8 @@ int gmlm_bias_res_layernorm_bwd(const void* dy, const void* x, const float* bias
  * out_lo (bf16 only, optional): the forward also stores lo = bf16(O - bf16(O)); handed to the backward, delta is formed
  * from out + out_lo, i.e. with fp32-like accuracy.  With `out` alone delta carries the 2^-9 rounding of the stored
  * output, which does NOT cancel in dS = P (dP - delta) and dominates the query / key gradients whenever those are small
- * against |dO||O| (deep encoder layers).  The short-sequence kernels neither write nor need it.
+ * against |dO||O| (deep encoder layers).  The short-sequence kernels neither write nor need it; handing it
+ * to the backward at a short-sequence shape selects the streaming kernels (above), so dbias is then refused.
  * ------------------------------------------------------------------------------------------- */
 int gmlm_attention_fwd(const void* q, const void* k, const void* v, const int32_t* kv_len, int64_t b, int64_t h,
                        int64_t lq, int64_t lk, int64_t d, int64_t q_stride, int64_t k_stride, int64_t v_stride,

@@ -236,6 +236,7 @@ row("gmlm_bias_res_layernorm_bwd", dict(rows=1, f=8, act=1, dropout_p=0.0, seed=
 # ---- attention, d = 64 / 96
 _PACKED = dict(cu_seqlens=ADDR(60), kv_len=None, max_len=1)
 _SHORT = dict(b=512, lq=16, lk=16)                                    # bf16, d = 64, <= 128 rows, b*h >= 512: the LDS-resident kernels
+_SHORT_RING = dict(b=64, h=8, lq=64, lk=64, **{k + "_stride": 512 for k in ("q", "k", "v", "dq", "dk", "dv")})   # a ring block's shape
 
 
 def _strides(names, width, big=1 << 24):
@@ -270,7 +271,15 @@ row("gmlm_attention_bwd", dict(_ATT_BASE, dq_stride=64, dk_stride=64, dv_stride=
     null_at_base=("cu_seqlens", "seq_groups", "dbias_partial", "dbias"), null_msg=b"null or", align="q k v dq dk dv out dout", align_msg=b"aligned",
     cases=_ATT_COMMON + _strides("q_stride k_stride v_stride dq_stride dk_stride dv_stride", 64)
     + [(dict(dbias=ADDR(63)), EINVAL, b"come together"), (dict(dbias_partial=ADDR(64)), EINVAL, b"come together"),
-       (dict(dbias=ADDR(63), dbias_partial=ADDR(64)), EINVAL, b"short-sequence path"), (dict(_SHORT, dbias=ADDR(63), dbias_partial=ADDR(64)), ELAUNCH, None),
+       (dict(dbias=ADDR(63), dbias_partial=ADDR(64)), EINVAL, b"short-sequence path"),
+       # the short-sequence backward sums delta over its own keys (it assumes its own lse), so it is selected only without out_lo:
+       # out_lo with the bias sums is refused with the streaming path's message, which shows that path was chosen
+       (dict(_SHORT, out_lo=None, dbias=ADDR(63), dbias_partial=ADDR(64)), ELAUNCH, None),
+       (dict(_SHORT, dbias=ADDR(63), dbias_partial=ADDR(64)), EINVAL, b"only on the short-sequence path"),
+       (dict(_SHORT_RING, dbias=ADDR(63), dbias_partial=ADDR(64)), EINVAL, b"only on the short-sequence path"),
+       (_SHORT_RING, ELAUNCH, None), (dict(_SHORT_RING, out_lo=None), ELAUNCH, None),
+       (dict(_SHORT_RING, out_lo=None, dbias=ADDR(63), dbias_partial=ADDR(64)), ELAUNCH, None),
+       (dict(_SHORT_RING, out_lo=None, workspace_bytes=0), EWORKSPACE, b"workspace"),
        (dict(lq=0), EINVAL, b"empty query or key"), (dict(lk=0), EINVAL, b"empty query or key"),
        (dict({k + "_stride": 96 for k in ("q", "k", "v", "dq", "dk", "dv")}, d=96), ELAUNCH, None), (dict(d=96), EINVAL, b"row stride")],
     ws=("gmlm_attention_bwd_workspace_bytes", "b h lq lk d", {}),

@@ -266,6 +266,30 @@ def test_attention_block(rec, d, dtype):
         assert_call(bwd, "gmlm_attention_bwd", want)
 
 
+def test_attention_block_forwards_out_lo_at_the_short_geometry(rec):
+    """bf16, d = 64, 64 rows, b * h = 512: the shape of the short-sequence kernels.  AttentionBlock decides nothing itself: the
+    caller's out_lo reaches gmlm_attention_bwd untouched (its presence is what keeps a ring block, whose lse and out are those of
+    all keys, off the short-sequence backward), and no out_lo stays NULL (the plain backward of the block's own forward)."""
+    b, h, l, hd = 64, 8, 64, 8 * 64
+    kvbuf = torch.zeros(b, l, 2 * hd, dtype=torch.bfloat16)
+    q, k, v = torch.zeros(b, l, hd, dtype=torch.bfloat16), kvbuf[..., :hd], kvbuf[..., hd:]
+    assert ops._short_path(q.dtype, 64, l, b * h)
+    kv_len = torch.full((b,), 33, dtype=torch.int32)
+    blk = ops.AttentionBlock(h, 0.125, 0.1)
+    out, lse = blk.fwd(q, k, v, kv_len, 7)
+    want = common(q, k, v, kv_len, b, h, l, l, 64, (hd, 2 * hd, 2 * hd), 0.125, 0.1, 7, torch.bfloat16, out=ptr(out), out_lo=None,
+                  lse=ptr(lse))
+    fwd, = rec.take()
+    assert_call(fwd, "gmlm_attention_fwd", want)
+    dout, out_lo = torch.ones_like(out), torch.zeros_like(out)
+    for lo in (out_lo, None):
+        dq, dk, dv = blk.bwd(q, k, v, out, dout, lse, kv_len, 7, out_lo=lo) if lo is not None else blk.bwd(q, k, v, out, dout, lse, kv_len, 7)
+        want.update(dout=ptr(dout), dq=ptr(dq), dk=ptr(dk), dv=ptr(dv), dq_stride=hd, dk_stride=hd, dv_stride=hd, out_lo=ptr(lo))
+        ws, bwd = rec.take()
+        assert_ws_call(ws, 64, b=b, h=h, lq=l, lk=l, d=64)
+        assert_call(bwd, "gmlm_attention_bwd", want)
+
+
 def test_attention_block_refusals(rec):
     blk = ops.AttentionBlock(2, 1.0)
     for d in (32, 128):
