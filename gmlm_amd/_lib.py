@@ -1,5 +1,5 @@
 """ctypes binding of libgmlm_hip.so (C ABI: include/gmlm_hip.h, gmlm_hip_split.h, gmlm_hip_optim.h, gmlm_hip_d32.h,
-gmlm_hip_wide.h, gmlm_hip_modernbert.h, gmlm_hip_relbias.h and gmlm_hip_disent.h): one signature table per header, positional argument types only.  Which attention entry point a head dim
+gmlm_hip_wide.h, gmlm_hip_modernbert.h, gmlm_hip_relbias.h, gmlm_hip_disent.h and gmlm_hip_gqa.h): one signature table per header, positional argument types only.  Which attention entry point a head dim
 takes, and where each ABI puts its arguments by name, is the family table of ops.py (``_ATTN_FAMILIES``).
 
 The product path has NO fallback: if the shared library is missing or a call fails, a Python
@@ -170,7 +170,17 @@ SIGNATURES_DISENT = {
                                             _i64, _p, _sz, _p]),
 }
 
-SIGNATURE_TABLES_LATER = (SIGNATURES_RELBIAS, SIGNATURES_DISENT)
+# ninth header, include/gmlm_hip_gqa.h (Llama / Qwen2 / Mistral encoders: rotary embedding over head rows at d = 64 / 128, causal
+# GQA attention at d = 64); the attention six take the argument lists of their gmlm_attention_causal_d128_* namesakes
+_D128 = "gmlm_attention_causal_d128"
+SIGNATURES_GQA = {
+    "gmlm_rope_heads_fwd": (C.c_int, [_p, _i64, _p, _i64, _i64, _i64, _p, _i64, _i64, _i32, _p]),
+    "gmlm_rope_heads_bwd": (C.c_int, [_p, _i64, _p, _i64, _i64, _i64, _p, _i64, _i64, _i32, _p]),
+    **{"gmlm_attention_causal_d64" + tail: SIGNATURES[_D128 + tail]
+       for tail in ("_fwd", "_workspace_bytes", "_bwd", "_varlen_fwd", "_varlen_workspace_bytes", "_varlen_bwd")},
+}
+
+SIGNATURE_TABLES_LATER = (SIGNATURES_RELBIAS, SIGNATURES_GQA, SIGNATURES_DISENT)
 
 
 class GmlmHipError(RuntimeError):

@@ -20,7 +20,7 @@ import torch
 import torch.nn as nn
 from torch.utils.checkpoint import checkpoint
 
-from . import bert, deberta, modernbert, mpnet, ops, qwen3
+from . import bert, deberta, llama, modernbert, mpnet, ops, qwen3
 from .dense import SPLITK_ROW_QUANTUM, _linear, check_gemm_precision, linear_specs, shadow_params, use_shadow
 from .graph import GraphCache, RelCSR
 from .nn import CrossAttention, GraphNorm, MultiScaleFusion, RGCNConv, compute_dtype, cross_attention_specs
@@ -32,7 +32,8 @@ logger = logging.getLogger(__name__)
 _ENCODERS = {"bert": (bert, "bert_encode", "bert_encode_packed"), "qwen3": (qwen3, "qwen3_encode", "qwen3_encode_packed"),
              "modernbert": (modernbert, "modernbert_encode", "modernbert_encode_packed"),
              "mpnet": (mpnet, "mpnet_encode", "mpnet_encode_packed"),
-             "deberta-v2": (deberta, "deberta_encode", "deberta_encode_packed")}
+             "deberta-v2": (deberta, "deberta_encode", "deberta_encode_packed"),
+             **{kind: (llama, "llama_encode", "llama_encode_packed") for kind in llama.MODEL_TYPES}}
 
 # static sizes of a captured text-encoder batch: sequences / tokens / attention work items are padded up to multiples of these
 ENCODER_BUCKET = (64, 2048, 32)
@@ -146,7 +147,8 @@ class GraphTextLM(nn.Module):
             if plm_tokenizer is None:
                 plm_tokenizer = AutoTokenizer.from_pretrained(model_name, trust_remote_code=True)
         # the encoder pass is picked by the PLM's model type: Qwen3 (gmlm_amd.qwen3), ModernBERT (gmlm_amd.modernbert), MPNet
-        # (gmlm_amd.mpnet), DeBERTa-v2 / v3 (gmlm_amd.deberta), else BERT geometry (gmlm_amd.bert)
+        # (gmlm_amd.mpnet), DeBERTa-v2 / v3 (gmlm_amd.deberta), Llama / Qwen2 / Mistral (gmlm_amd.llama), else BERT geometry
+        # (gmlm_amd.bert)
         model_type = getattr(plm_encoder.config, "model_type", None)
         self._plm_kind = model_type if model_type in _ENCODERS else "bert"
         self._enc.check_supported(plm_encoder)
@@ -215,8 +217,9 @@ class GraphTextLM(nn.Module):
     def _has_packed_pass(self) -> bool:
         """The encoder can run all active nodes as one variable-length packed batch: BERT geometry at a native head dim
         (``bert.NATIVE_HEAD_DIMS``: 32 / 64 / 96, ``bert.bert_encode_packed``), Qwen3 (``qwen3.qwen3_encode_packed``, head dim 128),
-        ModernBERT (``modernbert.modernbert_encode_packed``, head dim 64), MPNet (``mpnet.mpnet_encode_packed``, head dim 64) and
-        DeBERTa-v2 / v3 (``deberta.deberta_encode_packed``, head dim 64)."""
+        ModernBERT (``modernbert.modernbert_encode_packed``, head dim 64), MPNet (``mpnet.mpnet_encode_packed``, head dim 64),
+        DeBERTa-v2 / v3 (``deberta.deberta_encode_packed``, head dim 64) and Llama / Qwen2 / Mistral
+        (``llama.llama_encode_packed``, head dim 64 or 128)."""
         return self._enc is not bert or self._packed_head_dim() in bert.NATIVE_HEAD_DIMS
 
     def graph(self, edge_index: torch.Tensor, num_nodes: int, edge_type=None) -> RelCSR:

@@ -1112,59 +1112,59 @@ def qknorm_rope(qkv, q_weight, k_weight, cos_sin, hq, hkv, eps=1e-6, pos_ids=Non
     return QKNormRope.apply(qkv, q_weight, k_weight, cos_sin, hq, hkv, eps, pos_ids)
 
 
-def _causal_fwd(q, k, v, kv_len, hq, hkv, scale, want_lo):
+def _causal_fwd(q, k, v, kv_len, hq, hkv, scale, want_lo, d=128):
+    """``d``: 128 (gmlm_attention_causal_d128_*) or 64 (gmlm_attention_causal_d64_*, include/gmlm_hip_gqa.h): one argument list."""
     b, l = q.shape[0], q.shape[1]
-    qs, ks, vs = _rows_view(q, hq, 128), _rows_view(k, hkv, 128), _rows_view(v, hkv, 128)
-    out = torch.empty(b, l, hq * 128, dtype=q.dtype, device=q.device)
+    qs, ks, vs = _rows_view(q, hq, d), _rows_view(k, hkv, d), _rows_view(v, hkv, d)
+    out = torch.empty(b, l, hq * d, dtype=q.dtype, device=q.device)
     lse = torch.empty(b, hq, l, dtype=torch.float32, device=q.device)
     out_lo = torch.empty_like(out) if want_lo else None
-    with _span("attn_causal_fwd_d128", flops=2.0 * b * hq * l * l * 128):
-        check(lib().gmlm_attention_causal_d128_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(kv_len), b, hq, hkv, l, k.shape[1], 128, qs, ks, vs,
-                                                   float(scale), 0.0, _ptr(out), _ptr(out_lo), _ptr(lse), _dt(q), _stream()),
-              "gmlm_attention_causal_d128_fwd")
+    name = f"gmlm_attention_causal_d{d}_fwd"
+    with _span(f"attn_causal_fwd_d{d}", flops=2.0 * b * hq * l * l * d):
+        check(getattr(lib(), name)(_ptr(q), _ptr(k), _ptr(v), _ptr(kv_len), b, hq, hkv, l, k.shape[1], d, qs, ks, vs, float(scale), 0.0,
+                                   _ptr(out), _ptr(out_lo), _ptr(lse), _dt(q), _stream()), name)
     return out, out_lo, lse
 
 
-def _causal_bwd(q, k, v, out, out_lo, gout, lse, kv_len, hq, hkv, scale, dq, dk, dv):
+def _causal_bwd(q, k, v, out, out_lo, gout, lse, kv_len, hq, hkv, scale, dq, dk, dv, d=128):
     b, l = q.shape[0], q.shape[1]
     gout = gout.contiguous().to(q.dtype)
-    ws = _ws(lib().gmlm_attention_causal_d128_workspace_bytes(b, hq, l), q.device)
-    with _span("attn_causal_bwd_d128", flops=5.0 * b * hq * l * l * 128):
-        check(lib().gmlm_attention_causal_d128_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(out_lo), _ptr(gout), _ptr(lse),
-                                                   _ptr(kv_len), b, hq, hkv, l, k.shape[1], 128, q.stride(1), k.stride(1), v.stride(1),
-                                                   float(scale), 0.0, _ptr(dq), _ptr(dk), _ptr(dv), dq.stride(1), dk.stride(1),
-                                                   dv.stride(1), _dt(q), _ptr(ws), ws.numel(), _stream()),
-              "gmlm_attention_causal_d128_bwd")
+    ws = _ws(getattr(lib(), f"gmlm_attention_causal_d{d}_workspace_bytes")(b, hq, l), q.device)
+    name = f"gmlm_attention_causal_d{d}_bwd"
+    with _span(f"attn_causal_bwd_d{d}", flops=5.0 * b * hq * l * l * d):
+        check(getattr(lib(), name)(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(out_lo), _ptr(gout), _ptr(lse), _ptr(kv_len), b, hq, hkv, l,
+                                   k.shape[1], d, q.stride(1), k.stride(1), v.stride(1), float(scale), 0.0, _ptr(dq), _ptr(dk), _ptr(dv),
+                                   dq.stride(1), dk.stride(1), dv.stride(1), _dt(q), _ptr(ws), ws.numel(), _stream()), name)
 
 
 class CausalAttention(torch.autograd.Function):
-    """out[b, l, hq*128] = softmax(causal + key-padding mask(q k^T * scale)) v with hq query heads sharing hkv KV heads.
-    q [b, l, hq*128], k / v [b, l, hkv*128] (strided slices of a fused buffer are fine); kv_len int32 [b] or None.
-    The three gradients are views of ONE fused [b, l, (hq + 2 hkv) * 128] buffer."""
+    """out[b, l, hq*d] = softmax(causal + key-padding mask(q k^T * scale)) v with hq query heads sharing hkv KV heads, head dim
+    d = 128 (or 64: the gmlm_attention_causal_d64_* family).  q [b, l, hq*d], k / v [b, l, hkv*d] (strided slices of a fused
+    buffer are fine); kv_len int32 [b] or None.  The three gradients are views of ONE fused [b, l, (hq + 2 hkv) * d] buffer."""
 
     @staticmethod
-    def forward(ctx, q, k, v, kv_len, hq, hkv, scale):
+    def forward(ctx, q, k, v, kv_len, hq, hkv, scale, d=128):
         _cuda(q, k, v)
         want_lo = q.dtype == torch.bfloat16 and any(t.requires_grad for t in (q, k, v))
-        out, out_lo, lse = _causal_fwd(q, k, v, kv_len, hq, hkv, scale, want_lo)
+        out, out_lo, lse = _causal_fwd(q, k, v, kv_len, hq, hkv, scale, want_lo, d)
         ctx.save_for_backward(q, k, v, out, lse, kv_len, out_lo)
-        ctx.cfg = (hq, hkv, float(scale))
+        ctx.cfg = (hq, hkv, float(scale), d)
         return out
 
     @staticmethod
     def backward(ctx, gout):
         q, k, v, out, lse, kv_len, out_lo = ctx.saved_tensors
-        hq, hkv, scale = ctx.cfg
+        hq, hkv, scale, d = ctx.cfg
         b, l = q.shape[0], q.shape[1]
-        nq, nk = hq * 128, hkv * 128
+        nq, nk = hq * d, hkv * d
         dqkv = torch.empty(b, l, nq + 2 * nk, dtype=q.dtype, device=q.device)
         dq, dk, dv = dqkv[..., :nq], dqkv[..., nq:nq + nk], dqkv[..., nq + nk:]
-        _causal_bwd(q, k, v, out, out_lo, gout, lse, kv_len, hq, hkv, scale, dq, dk, dv)
-        return dq, dk, dv, None, None, None, None
+        _causal_bwd(q, k, v, out, out_lo, gout, lse, kv_len, hq, hkv, scale, dq, dk, dv, d)
+        return dq, dk, dv, None, None, None, None, None
 
 
-def causal_attention(q, k, v, kv_len, hq, hkv, scale):
-    return CausalAttention.apply(q, k, v, kv_len, hq, hkv, scale)
+def causal_attention(q, k, v, kv_len, hq, hkv, scale, d=128):
+    return CausalAttention.apply(q, k, v, kv_len, hq, hkv, scale, d)
 
 
 class RopeCausalAttention(torch.autograd.Function):
@@ -1212,68 +1212,67 @@ def _varlen_args(rows, cu_seqlens, max_len):
     return cu_seqlens.numel() - 1, int(max_len)
 
 
-def _packed_stride(t: torch.Tensor, h: int):
-    if t.dim() != 2 or t.stride(-1) != 1 or t.shape[-1] != h * 128:
-        raise ValueError("packed attention operands must be [tokens, heads * 128] with a contiguous last dim")
+def _packed_stride(t: torch.Tensor, h: int, d: int = 128):
+    if t.dim() != 2 or t.stride(-1) != 1 or t.shape[-1] != h * d:
+        raise ValueError(f"packed attention operands must be [tokens, heads * {d}] with a contiguous last dim")
     return t.stride(0)
 
 
-def _causal_varlen_fwd(q, k, v, cu, s, max_len, hq, hkv, scale, want_lo):
+def _causal_varlen_fwd(q, k, v, cu, s, max_len, hq, hkv, scale, want_lo, d=128):
     t = q.shape[0]
-    qs, ks, vs = _packed_stride(q, hq), _packed_stride(k, hkv), _packed_stride(v, hkv)
+    qs, ks, vs = _packed_stride(q, hq, d), _packed_stride(k, hkv, d), _packed_stride(v, hkv, d)
     if k.shape[0] != t or v.shape[0] != t:
         raise ValueError("packed q, k and v must have the same number of rows")
-    out = torch.empty(t, hq * 128, dtype=q.dtype, device=q.device)
+    out = torch.empty(t, hq * d, dtype=q.dtype, device=q.device)
     lse = torch.empty(hq, t, dtype=torch.float32, device=q.device)
     out_lo = torch.empty_like(out) if want_lo else None
-    with _span("attn_causal_varlen_fwd_d128", flops=2.0 * s * hq * max_len * max_len * 128):
-        check(lib().gmlm_attention_causal_d128_varlen_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(cu), s, max_len, t, hq, hkv, 128, qs, ks, vs,
-                                                          float(scale), 0.0, _ptr(out), _ptr(out_lo), _ptr(lse), _dt(q), _stream()),
-              "gmlm_attention_causal_d128_varlen_fwd")
+    name = f"gmlm_attention_causal_d{d}_varlen_fwd"
+    with _span(f"attn_causal_varlen_fwd_d{d}", flops=2.0 * s * hq * max_len * max_len * d):
+        check(getattr(lib(), name)(_ptr(q), _ptr(k), _ptr(v), _ptr(cu), s, max_len, t, hq, hkv, d, qs, ks, vs, float(scale), 0.0,
+                                   _ptr(out), _ptr(out_lo), _ptr(lse), _dt(q), _stream()), name)
     return out, out_lo, lse
 
 
-def _causal_varlen_bwd(q, k, v, out, out_lo, gout, lse, cu, s, max_len, hq, hkv, scale, dq, dk, dv):
+def _causal_varlen_bwd(q, k, v, out, out_lo, gout, lse, cu, s, max_len, hq, hkv, scale, dq, dk, dv, d=128):
     t = q.shape[0]
     gout = gout.contiguous().to(q.dtype)
-    ws = _ws(lib().gmlm_attention_causal_d128_varlen_workspace_bytes(t, hq), q.device)
-    with _span("attn_causal_varlen_bwd_d128", flops=5.0 * s * hq * max_len * max_len * 128):
-        check(lib().gmlm_attention_causal_d128_varlen_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(out_lo), _ptr(gout), _ptr(lse),
-                                                          _ptr(cu), s, max_len, t, hq, hkv, 128, q.stride(0), k.stride(0),
-                                                          v.stride(0), float(scale), 0.0, _ptr(dq), _ptr(dk), _ptr(dv),
-                                                          dq.stride(0), dk.stride(0), dv.stride(0), _dt(q), _ptr(ws), ws.numel(),
-                                                          _stream()), "gmlm_attention_causal_d128_varlen_bwd")
+    ws = _ws(getattr(lib(), f"gmlm_attention_causal_d{d}_varlen_workspace_bytes")(t, hq), q.device)
+    name = f"gmlm_attention_causal_d{d}_varlen_bwd"
+    with _span(f"attn_causal_varlen_bwd_d{d}", flops=5.0 * s * hq * max_len * max_len * d):
+        check(getattr(lib(), name)(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(out_lo), _ptr(gout), _ptr(lse), _ptr(cu), s, max_len, t, hq,
+                                   hkv, d, q.stride(0), k.stride(0), v.stride(0), float(scale), 0.0, _ptr(dq), _ptr(dk), _ptr(dv),
+                                   dq.stride(0), dk.stride(0), dv.stride(0), _dt(q), _ptr(ws), ws.numel(), _stream()), name)
 
 
 class CausalAttentionVarlen(torch.autograd.Function):
-    """``CausalAttention`` on a packed batch: q [T, hq*128], k / v [T, hkv*128] (strided slices of a fused buffer are fine),
+    """``CausalAttention`` on a packed batch: q [T, hq*d], k / v [T, hkv*d] (strided slices of a fused buffer are fine),
     sequence i = rows [cu_seqlens[i], cu_seqlens[i+1]) (int32 [S + 1]; a sequence may be empty, none is longer than
     ``max_len``), query i of a sequence sees its keys 0..i.  The sequences cover all T rows: a row that belongs to none is
-    neither read nor written, so its output and gradient rows would be uninitialised.  The three gradients are views of ONE fused [T, (hq + 2 hkv) * 128] buffer."""
+    neither read nor written, so its output and gradient rows would be uninitialised.  The three gradients are views of ONE fused [T, (hq + 2 hkv) * d] buffer."""
 
     @staticmethod
-    def forward(ctx, q, k, v, cu_seqlens, max_len, hq, hkv, scale):
+    def forward(ctx, q, k, v, cu_seqlens, max_len, hq, hkv, scale, d=128):
         _cuda(q, k, v)
         s, max_len = _varlen_args(q, cu_seqlens, max_len)
         want_lo = q.dtype == torch.bfloat16 and any(t.requires_grad for t in (q, k, v))
-        out, out_lo, lse = _causal_varlen_fwd(q, k, v, cu_seqlens, s, max_len, hq, hkv, scale, want_lo)
+        out, out_lo, lse = _causal_varlen_fwd(q, k, v, cu_seqlens, s, max_len, hq, hkv, scale, want_lo, d)
         ctx.save_for_backward(q, k, v, out, lse, cu_seqlens, out_lo)
-        ctx.cfg = (s, max_len, hq, hkv, float(scale))
+        ctx.cfg = (s, max_len, hq, hkv, float(scale), d)
         return out
 
     @staticmethod
     def backward(ctx, gout):
         q, k, v, out, lse, cu, out_lo = ctx.saved_tensors
-        s, max_len, hq, hkv, scale = ctx.cfg
-        nq, nk = hq * 128, hkv * 128
+        s, max_len, hq, hkv, scale, d = ctx.cfg
+        nq, nk = hq * d, hkv * d
         dqkv = torch.empty(q.shape[0], nq + 2 * nk, dtype=q.dtype, device=q.device)
         dq, dk, dv = dqkv[:, :nq], dqkv[:, nq:nq + nk], dqkv[:, nq + nk:]
-        _causal_varlen_bwd(q, k, v, out, out_lo, gout, lse, cu, s, max_len, hq, hkv, scale, dq, dk, dv)
-        return dq, dk, dv, None, None, None, None, None
+        _causal_varlen_bwd(q, k, v, out, out_lo, gout, lse, cu, s, max_len, hq, hkv, scale, dq, dk, dv, d)
+        return dq, dk, dv, None, None, None, None, None, None
 
 
-def causal_attention_varlen(q, k, v, cu_seqlens, max_len, hq, hkv, scale):
-    return CausalAttentionVarlen.apply(q, k, v, cu_seqlens, max_len, hq, hkv, scale)
+def causal_attention_varlen(q, k, v, cu_seqlens, max_len, hq, hkv, scale, d=128):
+    return CausalAttentionVarlen.apply(q, k, v, cu_seqlens, max_len, hq, hkv, scale, d)
 
 
 class RopeCausalAttentionVarlen(torch.autograd.Function):
@@ -1479,6 +1478,89 @@ def rope_attention_varlen(qkv, cos_sin, pos_ids, cu_seqlens, max_len, num_heads,
     ``max_len``, which also decides whether the band cuts).  ``qkv`` is overwritten with its rotated form."""
     w = int(window) if window_cuts(layer_type, window, max_len) else None
     return _RopeAttention.apply(_own_rows(qkv), cos_sin, None, num_heads, scale, w, pos_ids, cu_seqlens, int(max_len), pair_count, groups)[0]
+
+
+# ---------------------------------------------------------------------------------------------
+# Llama / Qwen2 / Mistral encoders: rotary embedding over the Q | K head rows in place + causal GQA attention at d = 64 / 128
+# (include/gmlm_hip_gqa.h)
+# ---------------------------------------------------------------------------------------------
+GQA_HEAD_DIMS = (64, 128)        # gmlm_rope_heads_*; causal attention: gmlm_attention_causal_d64_* / _d128_*
+
+
+def rope_heads_(qkv, cos_sin, heads, d, seq_len=0, pos_ids=None, inverse=False):
+    """Rotate (``inverse``: rotate back) the first ``heads`` = hq + hkv head rows of ``d`` (64 or 128) elements of every fused
+    [.., >= heads * d] row IN PLACE; what follows them (V) is not touched.  Positions are row % seq_len, or ``pos_ids`` (int32
+    [tokens]) when given.  Outside autograd: the building block of ``_RopeCausalGQA``."""
+    tokens, stride = _qkv_rows(qkv, heads * d)
+    if cos_sin.dtype != torch.float32 or cos_sin.dim() != 3 or tuple(cos_sin.shape[1:]) != (2, d // 2) or not cos_sin.is_contiguous():
+        raise ValueError(f"cos / sin table must be a contiguous fp32 [max_len, 2, {d // 2}] tensor")
+    name = "gmlm_rope_heads_bwd" if inverse else "gmlm_rope_heads_fwd"
+    check(getattr(lib(), name)(_ptr(qkv), stride, _ptr(cos_sin), cos_sin.shape[0], tokens, int(seq_len), _ptr(pos_ids), heads, d,
+                               _dt(qkv), _stream()), name)
+    return qkv
+
+
+class _RopeCausalGQA(torch.autograd.Function):
+    """Rotary embedding IN PLACE on the Q | K columns of a fused [.., (hq + 2 hkv) * d] projection output (marked dirty and
+    returned beside the context), then causal attention with grouped KV heads on the rotated buffer (d = 64:
+    gmlm_attention_causal_d64_*, d = 128: gmlm_attention_causal_d128_*), in one autograd node.  Padded ([b, l, .] with
+    ``kv_len``) or packed ([T, .] with ``pos_ids``, ``cu_seqlens``, ``max_len``).  The backward runs the attention backward into
+    ONE dqkv buffer, then the inverse rotation in place on it: a single data-gradient GEMM follows."""
+
+    @staticmethod
+    def forward(ctx, qkv, cs, kv_len, hq, hkv, d, scale, pos_ids, cu_seqlens, max_len):
+        _cuda(qkv)
+        if d not in GQA_HEAD_DIMS:
+            raise ValueError(f"head dim {d}: the rotary / causal GQA kernels take {GQA_HEAD_DIMS}")
+        if not qkv.is_contiguous() or qkv.shape[-1] != (hq + 2 * hkv) * d:
+            raise ValueError("fused projection output must be contiguous [.., (hq + 2 hkv) * d] rows")
+        packed = cu_seqlens is not None
+        if packed:
+            pos_ids = _pos_arg(qkv, pos_ids)
+            s, max_len = _varlen_args(qkv, cu_seqlens, max_len)
+        elif qkv.dim() != 3:
+            raise ValueError("padded fused projection output must be [b, l, (hq + 2 hkv) * d]")
+        seq_len = 0 if packed else qkv.shape[1]
+        pos = pos_ids if packed else None
+        rope_heads_(qkv, cs, hq + hkv, d, seq_len, pos)
+        ctx.mark_dirty(qkv)
+        nq, nk = hq * d, hkv * d
+        q, k, v = qkv[..., :nq], qkv[..., nq:nq + nk], qkv[..., nq + nk:]
+        want_lo = qkv.dtype == torch.bfloat16 and qkv.requires_grad
+        if packed:
+            out, out_lo, lse = _causal_varlen_fwd(q, k, v, cu_seqlens, s, max_len, hq, hkv, scale, want_lo, d)
+        else:
+            out, out_lo, lse = _causal_fwd(q, k, v, kv_len, hq, hkv, scale, want_lo, d)
+        ctx.save_for_backward(qkv, cs, out, out_lo, lse, kv_len, cu_seqlens, pos)
+        ctx.cfg = (hq, hkv, d, float(scale), seq_len, int(max_len))
+        return out, qkv
+
+    @staticmethod
+    def backward(ctx, gout, _gqkv):
+        qkv, cs, out, out_lo, lse, kv_len, cu, pos = ctx.saved_tensors
+        hq, hkv, d, scale, seq_len, max_len = ctx.cfg
+        nq, nk = hq * d, hkv * d
+        q, k, v = qkv[..., :nq], qkv[..., nq:nq + nk], qkv[..., nq + nk:]
+        dqkv = torch.empty_like(qkv)
+        dq, dk, dv = dqkv[..., :nq], dqkv[..., nq:nq + nk], dqkv[..., nq + nk:]
+        if cu is not None:
+            _causal_varlen_bwd(q, k, v, out, out_lo, gout, lse, cu, cu.numel() - 1, max_len, hq, hkv, scale, dq, dk, dv, d)
+        else:
+            _causal_bwd(q, k, v, out, out_lo, gout, lse, kv_len, hq, hkv, scale, dq, dk, dv, d)
+        rope_heads_(dqkv, cs, hq + hkv, d, seq_len, pos, inverse=True)
+        return (dqkv,) + (None,) * 9
+
+
+def rope_causal_gqa(qkv, cos_sin, kv_len, hq, hkv, d, scale):
+    """Padded layout: rotary embedding in place on ``qkv`` [b, l, (hq + 2 hkv) * d] (positions 0..l-1), then causal GQA
+    attention; ``kv_len`` int32 [b] or None.  ``qkv`` is overwritten with its rotated form (a view is copied first: ``_own_rows``)."""
+    return _RopeCausalGQA.apply(_own_rows(qkv), cos_sin, kv_len, hq, hkv, d, scale, None, None, 0)[0]
+
+
+def rope_causal_gqa_varlen(qkv, cos_sin, pos_ids, cu_seqlens, max_len, hq, hkv, d, scale):
+    """Packed layout: ``qkv`` [T, (hq + 2 hkv) * d] rows at positions ``pos_ids``, sequences by ``cu_seqlens`` (none longer than
+    ``max_len``).  ``qkv`` is overwritten with its rotated form."""
+    return _RopeCausalGQA.apply(_own_rows(qkv), cos_sin, None, hq, hkv, d, scale, pos_ids, cu_seqlens, int(max_len))[0]
 
 
 # ---------------------------------------------------------------------------------------------
