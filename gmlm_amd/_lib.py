@@ -1,5 +1,5 @@
 """ctypes binding of libgmlm_hip.so (C ABI: include/gmlm_hip.h, gmlm_hip_split.h, gmlm_hip_optim.h, gmlm_hip_d32.h,
-gmlm_hip_wide.h, gmlm_hip_modernbert.h, gmlm_hip_relbias.h, gmlm_hip_disent.h and gmlm_hip_gqa.h): one signature table per header, positional argument types only.  Which attention entry point a head dim
+gmlm_hip_wide.h, gmlm_hip_modernbert.h, gmlm_hip_relbias.h, gmlm_hip_disent.h, gmlm_hip_gqa.h and gmlm_hip_bidir.h): one signature table per header, positional argument types only.  Which attention entry point a head dim
 takes, and where each ABI puts its arguments by name, is the family table of ops.py (``_ATTN_FAMILIES``).
 
 The product path has NO fallback: if the shared library is missing or a call fails, a Python
@@ -180,7 +180,12 @@ SIGNATURES_GQA = {
        for tail in ("_fwd", "_workspace_bytes", "_bwd", "_varlen_fwd", "_varlen_workspace_bytes", "_varlen_bwd")},
 }
 
-SIGNATURE_TABLES_LATER = (SIGNATURES_RELBIAS, SIGNATURES_GQA, SIGNATURES_DISENT)
+# tenth header, include/gmlm_hip_bidir.h (EuroBERT encoders: bidirectional GQA attention at d = 64 / 128); the argument lists of
+# the gmlm_attention_causal_d64_* namesakes
+SIGNATURES_BIDIR = {"gmlm_attention_bidir_gqa" + tail: SIGNATURES[_D128 + tail]
+                    for tail in ("_fwd", "_workspace_bytes", "_bwd", "_varlen_fwd", "_varlen_workspace_bytes", "_varlen_bwd")}
+
+SIGNATURE_TABLES_LATER = (SIGNATURES_RELBIAS, SIGNATURES_GQA, SIGNATURES_BIDIR, SIGNATURES_DISENT)
 
 
 class GmlmHipError(RuntimeError):

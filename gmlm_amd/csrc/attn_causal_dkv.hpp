@@ -1,10 +1,11 @@
-// dK / dV of causal attention with grouped KV heads: the loop nest shared by causal128::dkv_kernel (attn_causal.hip, D = 128) and
-// gqa::causal64_dkv_kernel (attn_gqa.hip, D = 64).  One text for both head dims, as the streaming bodies of attn_stream.hpp are.
+// dK / dV of attention with grouped KV heads: the loop nest shared by causal128::dkv_kernel (attn_causal.hip, D = 128),
+// gqa::causal64_dkv_kernel (attn_gqa.hip, D = 64) and, with CAUSAL = false, bidir::gqa_dkv_kernel (attn_bidir.hip, D = 64 / 128).
+// One text for both head dims and both masks, as the streaming bodies of attn_stream.hpp are.
 // A workgroup owns NW * 32 keys (32 per wave) of one (sequence, KV head); for each query head of the group, in order, it walks
-// the query tiles of 32 from the one holding its first key to the end of the sequence and accumulates into the same
-// registers: no atomics, no expanded K / V or dK / dV in HBM, every sum in a fixed order.  Every wave reaches every barrier: a
-// wave whose keys lie past kv_len still stages Q / dO.  bf16: lse, delta and the kv_len mask ride in one extra contraction
-// step; the causal mask is not rank-1, so the diagonal block selects P = 0 explicitly before dS.
+// the query tiles of 32 from the one holding its first key (CAUSAL = false: from the first) to the end of the sequence and
+// accumulates into the same registers: no atomics, no expanded K / V or dK / dV in HBM, every sum in a fixed order.  Every wave
+// reaches every barrier: a wave whose keys lie past kv_len still stages Q / dO.  bf16: lse, delta and the kv_len mask ride in
+// one extra contraction step; the causal mask is not rank-1, so the diagonal block selects P = 0 explicitly before dS.
 #pragma once
 #include "attn_common.hpp"
 
@@ -23,7 +24,7 @@ __device__ __forceinline__ CausalKeyTile causal_key_tile(const AttnParams& p, in
 
 // p.h = query heads; `group` = query heads per KV head; dout_stride = row stride of dO; kvlen = the sequence's kv_len clamped
 // into [0, it.l] by the caller
-template <typename T, int D, int NW, int QT, bool DBUF>
+template <typename T, int D, int NW, int QT, bool DBUF, bool CAUSAL = true>
 __device__ __forceinline__ void causal_dkv_body(const AttnParams& p, int64_t dout_stride, int group, const CausalKeyTile& it,
                                                 int64_t kvlen) {
   constexpr int NT = NW * 64, BQ = NW * 32;
@@ -69,7 +70,7 @@ __device__ __forceinline__ void causal_dkv_body(const AttnParams& p, int64_t dou
 #pragma unroll
     for (int i = 0; i < 16; ++i) { dk[d][i] = 0.f; dv[d][i] = 0.f; }
   if (k_tile0 < kvlen) {                                     // block-uniform: else nothing to accumulate
-    const int t0 = (int)(k_tile0 / QT), ntiles = (int)((l_ + QT - 1) / QT);    // t0 < ntiles since k_tile0 < l_
+    const int t0 = CAUSAL ? (int)(k_tile0 / QT) : 0, ntiles = (int)((l_ + QT - 1) / QT);    // t0 < ntiles since k_tile0 < l_
     TileRegs<T, D, QT, NT> qr, dor;
     qr.init(p.q_stride, tid);
     dor.init(dout_stride, tid);
@@ -124,9 +125,9 @@ __device__ __forceinline__ void causal_dkv_body(const AttnParams& p, int64_t dou
           dor.load(dog, dout_stride, q0 + QT, l_, tid);
           load_small(q0 + QT);
         }
-        // query blocks before this wave's keys are fully masked for it (q0 and k_wave0 are multiples of 32)
-        if (wave_live && q0 >= k_wave0) {
-          const bool diag = q0 == k_wave0;                    // wave-uniform
+        // CAUSAL: query blocks before this wave's keys are fully masked for it (q0 and k_wave0 are multiples of 32)
+        if (wave_live && (!CAUSAL || q0 >= k_wave0)) {
+          const bool diag = CAUSAL && q0 == k_wave0;          // wave-uniform
           f32x16 s, dp;
 #pragma unroll
           for (int i = 0; i < 16; ++i) { s[i] = 0.f; dp[i] = 0.f; }

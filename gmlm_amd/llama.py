@@ -47,18 +47,23 @@ def check_window(cfg, longest: int) -> None:
 
 
 def check_supported(plm) -> None:
-    cfg = plm.config
+    check_config(plm.config, MODEL_TYPES, "Llama, Qwen2 and Mistral", "causal")
+
+
+def check_config(cfg, model_types, names: str, mask: str) -> None:
+    """Every way in which ``cfg`` is not a Llama-layer encoder that the kernels cover, at once.  ``model_types`` / ``names``: what
+    the calling module takes; ``mask``: how it names its attention kernels ("causal"; eurobert.py: "grouped")."""
     problems = []
-    if getattr(cfg, "model_type", None) not in MODEL_TYPES:
-        problems.append(f"model_type={getattr(cfg, 'model_type', None)!r} (this module takes Llama, Qwen2 and Mistral encoders)")
+    if getattr(cfg, "model_type", None) not in model_types:
+        problems.append(f"model_type={getattr(cfg, 'model_type', None)!r} (this module takes {names} encoders)")
     if getattr(cfg, "hidden_act", "silu") != "silu":
         problems.append(f"hidden_act={cfg.hidden_act!r}")
     if head_dim(cfg) not in ops.GQA_HEAD_DIMS:
-        problems.append(f"head_dim={head_dim(cfg)} (the rotary and causal attention kernels take 64 or 128)")
+        problems.append(f"head_dim={head_dim(cfg)} (the rotary and {mask} attention kernels take 64 or 128)")
     if getattr(cfg, "mlp_bias", False):
         problems.append("mlp_bias")
     if float(getattr(cfg, "attention_dropout", 0.0) or 0.0) != 0.0:
-        problems.append(f"attention_dropout={cfg.attention_dropout} (no probability dropout in the causal kernels)")
+        problems.append(f"attention_dropout={cfg.attention_dropout} (no probability dropout in the {mask} kernels)")
     if int(getattr(cfg, "pretraining_tp", 1) or 1) > 1:
         problems.append(f"pretraining_tp={cfg.pretraining_tp}")
     heads, kv = getattr(cfg, "num_attention_heads", 0), getattr(cfg, "num_key_value_heads", 0)
@@ -140,15 +145,15 @@ def _layer(lw, stream, branch, lens, cs, hq, hkv, d, scale, eps, packed=None):
     return s2, _mm(m, lw.wdown, None, lw.m_down)
 
 
-def _encode_rows(plm, x, lens, cs, cd, training, gradient_checkpointing, weights, *packed):
+def _encode_rows(plm, x, lens, cs, cd, training, gradient_checkpointing, weights, *packed, layer=None):
     """The layers and the final norm over the embedding rows ``x`` ([B, L, P] with ``lens``, or [T, P] with ``packed`` = the one
-    trailing argument of ``_layer``)."""
+    trailing argument of ``_layer``).  ``layer``: a layer function with ``_layer``'s arguments (eurobert.py: another attention)."""
     cfg = plm.config
     hq, hkv, d = cfg.num_attention_heads, cfg.num_key_value_heads, head_dim(cfg)
     eps, scale = cfg.rms_norm_eps, d ** -0.5
     if weights is None:
         weights = prepare_weights(plm, cd)
-    stream, branch = encoder.run_layers(_layer, weights, (x, None), (lens, cs, hq, hkv, d, scale, eps, *packed), training,
+    stream, branch = encoder.run_layers(layer or _layer, weights, (x, None), (lens, cs, hq, hkv, d, scale, eps, *packed), training,
                                         gradient_checkpointing)
     return ops.add_rmsnorm(stream, branch, plm.norm.weight, eps)[1]
 

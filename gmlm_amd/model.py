@@ -20,7 +20,7 @@ import torch
 import torch.nn as nn
 from torch.utils.checkpoint import checkpoint
 
-from . import bert, deberta, llama, modernbert, mpnet, ops, qwen3
+from . import bert, deberta, eurobert, llama, modernbert, mpnet, nomic_bert, ops, qwen3
 from .dense import SPLITK_ROW_QUANTUM, _linear, check_gemm_precision, linear_specs, shadow_params, use_shadow
 from .graph import GraphCache, RelCSR
 from .nn import CrossAttention, GraphNorm, MultiScaleFusion, RGCNConv, compute_dtype, cross_attention_specs
@@ -33,6 +33,8 @@ _ENCODERS = {"bert": (bert, "bert_encode", "bert_encode_packed"), "qwen3": (qwen
              "modernbert": (modernbert, "modernbert_encode", "modernbert_encode_packed"),
              "mpnet": (mpnet, "mpnet_encode", "mpnet_encode_packed"),
              "deberta-v2": (deberta, "deberta_encode", "deberta_encode_packed"),
+             "eurobert": (eurobert, "eurobert_encode", "eurobert_encode_packed"),
+             "nomic_bert": (nomic_bert, "nomic_bert_encode", "nomic_bert_encode_packed"),
              **{kind: (llama, "llama_encode", "llama_encode_packed") for kind in llama.MODEL_TYPES}}
 
 # static sizes of a captured text-encoder batch: sequences / tokens / attention work items are padded up to multiples of these
@@ -147,8 +149,8 @@ class GraphTextLM(nn.Module):
             if plm_tokenizer is None:
                 plm_tokenizer = AutoTokenizer.from_pretrained(model_name, trust_remote_code=True)
         # the encoder pass is picked by the PLM's model type: Qwen3 (gmlm_amd.qwen3), ModernBERT (gmlm_amd.modernbert), MPNet
-        # (gmlm_amd.mpnet), DeBERTa-v2 / v3 (gmlm_amd.deberta), Llama / Qwen2 / Mistral (gmlm_amd.llama), else BERT geometry
-        # (gmlm_amd.bert)
+        # (gmlm_amd.mpnet), DeBERTa-v2 / v3 (gmlm_amd.deberta), Llama / Qwen2 / Mistral (gmlm_amd.llama), EuroBERT
+        # (gmlm_amd.eurobert), NomicBERT (gmlm_amd.nomic_bert), else BERT geometry (gmlm_amd.bert)
         model_type = getattr(plm_encoder.config, "model_type", None)
         self._plm_kind = model_type if model_type in _ENCODERS else "bert"
         self._enc.check_supported(plm_encoder)
@@ -208,9 +210,10 @@ class GraphTextLM(nn.Module):
 
     def _packed_head_dim(self) -> int:
         """Head dim of the text encoder if it has the forms built on the BERT packed pass (short-sequence groups, bucketed
-        layout, hipGraph capture of the encoder), else 0: BERT geometry only.  A Qwen3, ModernBERT, MPNet or DeBERTa encoder has
-        none of them whatever its hidden_size // heads is (64 for Qwen3-0.6B, whose head dim is 128, for every ModernBERT, every
-        MPNet and every DeBERTa-v3); its plain packed pass is ``_has_packed_pass``."""
+        layout, hipGraph capture of the encoder), else 0: BERT geometry only.  A Qwen3, ModernBERT, MPNet, DeBERTa, Llama-family,
+        EuroBERT or NomicBERT encoder has none of them whatever its hidden_size // heads is (64 for Qwen3-0.6B, whose head dim is
+        128, for every ModernBERT, every MPNet, every DeBERTa-v3 and every NomicBERT); its plain packed pass is
+        ``_has_packed_pass``."""
         cfg = self.plm_encoder.config
         return cfg.hidden_size // cfg.num_attention_heads if self._enc is bert else 0
 
@@ -218,8 +221,9 @@ class GraphTextLM(nn.Module):
         """The encoder can run all active nodes as one variable-length packed batch: BERT geometry at a native head dim
         (``bert.NATIVE_HEAD_DIMS``: 32 / 64 / 96, ``bert.bert_encode_packed``), Qwen3 (``qwen3.qwen3_encode_packed``, head dim 128),
         ModernBERT (``modernbert.modernbert_encode_packed``, head dim 64), MPNet (``mpnet.mpnet_encode_packed``, head dim 64),
-        DeBERTa-v2 / v3 (``deberta.deberta_encode_packed``, head dim 64) and Llama / Qwen2 / Mistral
-        (``llama.llama_encode_packed``, head dim 64 or 128)."""
+        DeBERTa-v2 / v3 (``deberta.deberta_encode_packed``, head dim 64), Llama / Qwen2 / Mistral
+        (``llama.llama_encode_packed``, head dim 64 or 128), EuroBERT (``eurobert.eurobert_encode_packed``, head dim 64 or 128)
+        and NomicBERT (``nomic_bert.nomic_bert_encode_packed``, head dim 64)."""
         return self._enc is not bert or self._packed_head_dim() in bert.NATIVE_HEAD_DIMS
 
     def graph(self, edge_index: torch.Tensor, num_nodes: int, edge_type=None) -> RelCSR:

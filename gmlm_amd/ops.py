@@ -1112,26 +1112,34 @@ def qknorm_rope(qkv, q_weight, k_weight, cos_sin, hq, hkv, eps=1e-6, pos_ids=Non
     return QKNormRope.apply(qkv, q_weight, k_weight, cos_sin, hq, hkv, eps, pos_ids)
 
 
-def _causal_fwd(q, k, v, kv_len, hq, hkv, scale, want_lo, d=128):
-    """``d``: 128 (gmlm_attention_causal_d128_*) or 64 (gmlm_attention_causal_d64_*, include/gmlm_hip_gqa.h): one argument list."""
+def _gqa_entry(d, bidir):
+    """(entry-point stem, span stem) of a grouped-KV attention family: causal at d = 128 (gmlm_attention_causal_d128_*) or 64
+    (gmlm_attention_causal_d64_*, include/gmlm_hip_gqa.h), or ``bidir``: no causal mask, d = 64 / 128 (gmlm_attention_bidir_gqa_*,
+    include/gmlm_hip_bidir.h).  One argument list for all of them."""
+    return ("gmlm_attention_bidir_gqa", "attn_bidir") if bidir else (f"gmlm_attention_causal_d{d}", "attn_causal")
+
+
+def _causal_fwd(q, k, v, kv_len, hq, hkv, scale, want_lo, d=128, bidir=False):
+    stem, tag = _gqa_entry(d, bidir)
     b, l = q.shape[0], q.shape[1]
     qs, ks, vs = _rows_view(q, hq, d), _rows_view(k, hkv, d), _rows_view(v, hkv, d)
     out = torch.empty(b, l, hq * d, dtype=q.dtype, device=q.device)
     lse = torch.empty(b, hq, l, dtype=torch.float32, device=q.device)
     out_lo = torch.empty_like(out) if want_lo else None
-    name = f"gmlm_attention_causal_d{d}_fwd"
-    with _span(f"attn_causal_fwd_d{d}", flops=2.0 * b * hq * l * l * d):
+    name = stem + "_fwd"
+    with _span(f"{tag}_fwd_d{d}", flops=(4.0 if bidir else 2.0) * b * hq * l * l * d):
         check(getattr(lib(), name)(_ptr(q), _ptr(k), _ptr(v), _ptr(kv_len), b, hq, hkv, l, k.shape[1], d, qs, ks, vs, float(scale), 0.0,
                                    _ptr(out), _ptr(out_lo), _ptr(lse), _dt(q), _stream()), name)
     return out, out_lo, lse
 
 
-def _causal_bwd(q, k, v, out, out_lo, gout, lse, kv_len, hq, hkv, scale, dq, dk, dv, d=128):
+def _causal_bwd(q, k, v, out, out_lo, gout, lse, kv_len, hq, hkv, scale, dq, dk, dv, d=128, bidir=False):
+    stem, tag = _gqa_entry(d, bidir)
     b, l = q.shape[0], q.shape[1]
     gout = gout.contiguous().to(q.dtype)
-    ws = _ws(getattr(lib(), f"gmlm_attention_causal_d{d}_workspace_bytes")(b, hq, l), q.device)
-    name = f"gmlm_attention_causal_d{d}_bwd"
-    with _span(f"attn_causal_bwd_d{d}", flops=5.0 * b * hq * l * l * d):
+    ws = _ws(getattr(lib(), stem + "_workspace_bytes")(b, hq, l), q.device)
+    name = stem + "_bwd"
+    with _span(f"{tag}_bwd_d{d}", flops=(10.0 if bidir else 5.0) * b * hq * l * l * d):
         check(getattr(lib(), name)(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(out_lo), _ptr(gout), _ptr(lse), _ptr(kv_len), b, hq, hkv, l,
                                    k.shape[1], d, q.stride(1), k.stride(1), v.stride(1), float(scale), 0.0, _ptr(dq), _ptr(dk), _ptr(dv),
                                    dq.stride(1), dk.stride(1), dv.stride(1), _dt(q), _ptr(ws), ws.numel(), _stream()), name)
@@ -1140,31 +1148,32 @@ def _causal_bwd(q, k, v, out, out_lo, gout, lse, kv_len, hq, hkv, scale, dq, dk,
 class CausalAttention(torch.autograd.Function):
     """out[b, l, hq*d] = softmax(causal + key-padding mask(q k^T * scale)) v with hq query heads sharing hkv KV heads, head dim
     d = 128 (or 64: the gmlm_attention_causal_d64_* family).  q [b, l, hq*d], k / v [b, l, hkv*d] (strided slices of a fused
-    buffer are fine); kv_len int32 [b] or None.  The three gradients are views of ONE fused [b, l, (hq + 2 hkv) * d] buffer."""
+    buffer are fine); kv_len int32 [b] or None.  The three gradients are views of ONE fused [b, l, (hq + 2 hkv) * d] buffer.
+    ``bidir``: the key-padding mask alone (gmlm_attention_bidir_gqa_*, d = 64 or 128)."""
 
     @staticmethod
-    def forward(ctx, q, k, v, kv_len, hq, hkv, scale, d=128):
+    def forward(ctx, q, k, v, kv_len, hq, hkv, scale, d=128, bidir=False):
         _cuda(q, k, v)
         want_lo = q.dtype == torch.bfloat16 and any(t.requires_grad for t in (q, k, v))
-        out, out_lo, lse = _causal_fwd(q, k, v, kv_len, hq, hkv, scale, want_lo, d)
+        out, out_lo, lse = _causal_fwd(q, k, v, kv_len, hq, hkv, scale, want_lo, d, bidir)
         ctx.save_for_backward(q, k, v, out, lse, kv_len, out_lo)
-        ctx.cfg = (hq, hkv, float(scale), d)
+        ctx.cfg = (hq, hkv, float(scale), d, bidir)
         return out
 
     @staticmethod
     def backward(ctx, gout):
         q, k, v, out, lse, kv_len, out_lo = ctx.saved_tensors
-        hq, hkv, scale, d = ctx.cfg
+        hq, hkv, scale, d, bidir = ctx.cfg
         b, l = q.shape[0], q.shape[1]
         nq, nk = hq * d, hkv * d
         dqkv = torch.empty(b, l, nq + 2 * nk, dtype=q.dtype, device=q.device)
         dq, dk, dv = dqkv[..., :nq], dqkv[..., nq:nq + nk], dqkv[..., nq + nk:]
-        _causal_bwd(q, k, v, out, out_lo, gout, lse, kv_len, hq, hkv, scale, dq, dk, dv, d)
-        return dq, dk, dv, None, None, None, None, None
+        _causal_bwd(q, k, v, out, out_lo, gout, lse, kv_len, hq, hkv, scale, dq, dk, dv, d, bidir)
+        return dq, dk, dv, None, None, None, None, None, None
 
 
 def causal_attention(q, k, v, kv_len, hq, hkv, scale, d=128):
-    return CausalAttention.apply(q, k, v, kv_len, hq, hkv, scale, d)
+    return CausalAttention.apply(q, k, v, kv_len, hq, hkv, scale, d, False)
 
 
 class RopeCausalAttention(torch.autograd.Function):
@@ -1218,7 +1227,8 @@ def _packed_stride(t: torch.Tensor, h: int, d: int = 128):
     return t.stride(0)
 
 
-def _causal_varlen_fwd(q, k, v, cu, s, max_len, hq, hkv, scale, want_lo, d=128):
+def _causal_varlen_fwd(q, k, v, cu, s, max_len, hq, hkv, scale, want_lo, d=128, bidir=False):
+    stem, tag = _gqa_entry(d, bidir)
     t = q.shape[0]
     qs, ks, vs = _packed_stride(q, hq, d), _packed_stride(k, hkv, d), _packed_stride(v, hkv, d)
     if k.shape[0] != t or v.shape[0] != t:
@@ -1226,19 +1236,20 @@ def _causal_varlen_fwd(q, k, v, cu, s, max_len, hq, hkv, scale, want_lo, d=128):
     out = torch.empty(t, hq * d, dtype=q.dtype, device=q.device)
     lse = torch.empty(hq, t, dtype=torch.float32, device=q.device)
     out_lo = torch.empty_like(out) if want_lo else None
-    name = f"gmlm_attention_causal_d{d}_varlen_fwd"
-    with _span(f"attn_causal_varlen_fwd_d{d}", flops=2.0 * s * hq * max_len * max_len * d):
+    name = stem + "_varlen_fwd"
+    with _span(f"{tag}_varlen_fwd_d{d}", flops=(4.0 if bidir else 2.0) * s * hq * max_len * max_len * d):
         check(getattr(lib(), name)(_ptr(q), _ptr(k), _ptr(v), _ptr(cu), s, max_len, t, hq, hkv, d, qs, ks, vs, float(scale), 0.0,
                                    _ptr(out), _ptr(out_lo), _ptr(lse), _dt(q), _stream()), name)
     return out, out_lo, lse
 
 
-def _causal_varlen_bwd(q, k, v, out, out_lo, gout, lse, cu, s, max_len, hq, hkv, scale, dq, dk, dv, d=128):
+def _causal_varlen_bwd(q, k, v, out, out_lo, gout, lse, cu, s, max_len, hq, hkv, scale, dq, dk, dv, d=128, bidir=False):
+    stem, tag = _gqa_entry(d, bidir)
     t = q.shape[0]
     gout = gout.contiguous().to(q.dtype)
-    ws = _ws(getattr(lib(), f"gmlm_attention_causal_d{d}_varlen_workspace_bytes")(t, hq), q.device)
-    name = f"gmlm_attention_causal_d{d}_varlen_bwd"
-    with _span(f"attn_causal_varlen_bwd_d{d}", flops=5.0 * s * hq * max_len * max_len * d):
+    ws = _ws(getattr(lib(), stem + "_varlen_workspace_bytes")(t, hq), q.device)
+    name = stem + "_varlen_bwd"
+    with _span(f"{tag}_varlen_bwd_d{d}", flops=(10.0 if bidir else 5.0) * s * hq * max_len * max_len * d):
         check(getattr(lib(), name)(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(out_lo), _ptr(gout), _ptr(lse), _ptr(cu), s, max_len, t, hq,
                                    hkv, d, q.stride(0), k.stride(0), v.stride(0), float(scale), 0.0, _ptr(dq), _ptr(dk), _ptr(dv),
                                    dq.stride(0), dk.stride(0), dv.stride(0), _dt(q), _ptr(ws), ws.numel(), _stream()), name)
@@ -1251,28 +1262,28 @@ class CausalAttentionVarlen(torch.autograd.Function):
     neither read nor written, so its output and gradient rows would be uninitialised.  The three gradients are views of ONE fused [T, (hq + 2 hkv) * d] buffer."""
 
     @staticmethod
-    def forward(ctx, q, k, v, cu_seqlens, max_len, hq, hkv, scale, d=128):
+    def forward(ctx, q, k, v, cu_seqlens, max_len, hq, hkv, scale, d=128, bidir=False):
         _cuda(q, k, v)
         s, max_len = _varlen_args(q, cu_seqlens, max_len)
         want_lo = q.dtype == torch.bfloat16 and any(t.requires_grad for t in (q, k, v))
-        out, out_lo, lse = _causal_varlen_fwd(q, k, v, cu_seqlens, s, max_len, hq, hkv, scale, want_lo, d)
+        out, out_lo, lse = _causal_varlen_fwd(q, k, v, cu_seqlens, s, max_len, hq, hkv, scale, want_lo, d, bidir)
         ctx.save_for_backward(q, k, v, out, lse, cu_seqlens, out_lo)
-        ctx.cfg = (s, max_len, hq, hkv, float(scale), d)
+        ctx.cfg = (s, max_len, hq, hkv, float(scale), d, bidir)
         return out
 
     @staticmethod
     def backward(ctx, gout):
         q, k, v, out, lse, cu, out_lo = ctx.saved_tensors
-        s, max_len, hq, hkv, scale, d = ctx.cfg
+        s, max_len, hq, hkv, scale, d, bidir = ctx.cfg
         nq, nk = hq * d, hkv * d
         dqkv = torch.empty(q.shape[0], nq + 2 * nk, dtype=q.dtype, device=q.device)
         dq, dk, dv = dqkv[:, :nq], dqkv[:, nq:nq + nk], dqkv[:, nq + nk:]
-        _causal_varlen_bwd(q, k, v, out, out_lo, gout, lse, cu, s, max_len, hq, hkv, scale, dq, dk, dv, d)
-        return dq, dk, dv, None, None, None, None, None, None
+        _causal_varlen_bwd(q, k, v, out, out_lo, gout, lse, cu, s, max_len, hq, hkv, scale, dq, dk, dv, d, bidir)
+        return dq, dk, dv, None, None, None, None, None, None, None
 
 
 def causal_attention_varlen(q, k, v, cu_seqlens, max_len, hq, hkv, scale, d=128):
-    return CausalAttentionVarlen.apply(q, k, v, cu_seqlens, max_len, hq, hkv, scale, d)
+    return CausalAttentionVarlen.apply(q, k, v, cu_seqlens, max_len, hq, hkv, scale, d, False)
 
 
 class RopeCausalAttentionVarlen(torch.autograd.Function):
@@ -1482,7 +1493,7 @@ def rope_attention_varlen(qkv, cos_sin, pos_ids, cu_seqlens, max_len, num_heads,
 
 # ---------------------------------------------------------------------------------------------
 # Llama / Qwen2 / Mistral encoders: rotary embedding over the Q | K head rows in place + causal GQA attention at d = 64 / 128
-# (include/gmlm_hip_gqa.h)
+# (include/gmlm_hip_gqa.h); EuroBERT encoders: the same with bidirectional GQA attention (include/gmlm_hip_bidir.h)
 # ---------------------------------------------------------------------------------------------
 GQA_HEAD_DIMS = (64, 128)        # gmlm_rope_heads_*; causal attention: gmlm_attention_causal_d64_* / _d128_*
 
@@ -1503,15 +1514,16 @@ def rope_heads_(qkv, cos_sin, heads, d, seq_len=0, pos_ids=None, inverse=False):
 class _RopeCausalGQA(torch.autograd.Function):
     """Rotary embedding IN PLACE on the Q | K columns of a fused [.., (hq + 2 hkv) * d] projection output (marked dirty and
     returned beside the context), then causal attention with grouped KV heads on the rotated buffer (d = 64:
-    gmlm_attention_causal_d64_*, d = 128: gmlm_attention_causal_d128_*), in one autograd node.  Padded ([b, l, .] with
+    gmlm_attention_causal_d64_*, d = 128: gmlm_attention_causal_d128_*; ``bidir``: without the causal mask,
+    gmlm_attention_bidir_gqa_* at either head dim), in one autograd node.  Padded ([b, l, .] with
     ``kv_len``) or packed ([T, .] with ``pos_ids``, ``cu_seqlens``, ``max_len``).  The backward runs the attention backward into
     ONE dqkv buffer, then the inverse rotation in place on it: a single data-gradient GEMM follows."""
 
     @staticmethod
-    def forward(ctx, qkv, cs, kv_len, hq, hkv, d, scale, pos_ids, cu_seqlens, max_len):
+    def forward(ctx, qkv, cs, kv_len, hq, hkv, d, scale, pos_ids, cu_seqlens, max_len, bidir):
         _cuda(qkv)
         if d not in GQA_HEAD_DIMS:
-            raise ValueError(f"head dim {d}: the rotary / causal GQA kernels take {GQA_HEAD_DIMS}")
+            raise ValueError(f"head dim {d}: the rotary / grouped-KV attention kernels take {GQA_HEAD_DIMS}")
         if not qkv.is_contiguous() or qkv.shape[-1] != (hq + 2 * hkv) * d:
             raise ValueError("fused projection output must be contiguous [.., (hq + 2 hkv) * d] rows")
         packed = cu_seqlens is not None
@@ -1528,39 +1540,60 @@ class _RopeCausalGQA(torch.autograd.Function):
         q, k, v = qkv[..., :nq], qkv[..., nq:nq + nk], qkv[..., nq + nk:]
         want_lo = qkv.dtype == torch.bfloat16 and qkv.requires_grad
         if packed:
-            out, out_lo, lse = _causal_varlen_fwd(q, k, v, cu_seqlens, s, max_len, hq, hkv, scale, want_lo, d)
+            out, out_lo, lse = _causal_varlen_fwd(q, k, v, cu_seqlens, s, max_len, hq, hkv, scale, want_lo, d, bidir)
         else:
-            out, out_lo, lse = _causal_fwd(q, k, v, kv_len, hq, hkv, scale, want_lo, d)
+            out, out_lo, lse = _causal_fwd(q, k, v, kv_len, hq, hkv, scale, want_lo, d, bidir)
         ctx.save_for_backward(qkv, cs, out, out_lo, lse, kv_len, cu_seqlens, pos)
-        ctx.cfg = (hq, hkv, d, float(scale), seq_len, int(max_len))
+        ctx.cfg = (hq, hkv, d, float(scale), seq_len, int(max_len), bidir)
         return out, qkv
 
     @staticmethod
     def backward(ctx, gout, _gqkv):
         qkv, cs, out, out_lo, lse, kv_len, cu, pos = ctx.saved_tensors
-        hq, hkv, d, scale, seq_len, max_len = ctx.cfg
+        hq, hkv, d, scale, seq_len, max_len, bidir = ctx.cfg
         nq, nk = hq * d, hkv * d
         q, k, v = qkv[..., :nq], qkv[..., nq:nq + nk], qkv[..., nq + nk:]
         dqkv = torch.empty_like(qkv)
         dq, dk, dv = dqkv[..., :nq], dqkv[..., nq:nq + nk], dqkv[..., nq + nk:]
         if cu is not None:
-            _causal_varlen_bwd(q, k, v, out, out_lo, gout, lse, cu, cu.numel() - 1, max_len, hq, hkv, scale, dq, dk, dv, d)
+            _causal_varlen_bwd(q, k, v, out, out_lo, gout, lse, cu, cu.numel() - 1, max_len, hq, hkv, scale, dq, dk, dv, d, bidir)
         else:
-            _causal_bwd(q, k, v, out, out_lo, gout, lse, kv_len, hq, hkv, scale, dq, dk, dv, d)
+            _causal_bwd(q, k, v, out, out_lo, gout, lse, kv_len, hq, hkv, scale, dq, dk, dv, d, bidir)
         rope_heads_(dqkv, cs, hq + hkv, d, seq_len, pos, inverse=True)
-        return (dqkv,) + (None,) * 9
+        return (dqkv,) + (None,) * 10
 
 
 def rope_causal_gqa(qkv, cos_sin, kv_len, hq, hkv, d, scale):
     """Padded layout: rotary embedding in place on ``qkv`` [b, l, (hq + 2 hkv) * d] (positions 0..l-1), then causal GQA
     attention; ``kv_len`` int32 [b] or None.  ``qkv`` is overwritten with its rotated form (a view is copied first: ``_own_rows``)."""
-    return _RopeCausalGQA.apply(_own_rows(qkv), cos_sin, kv_len, hq, hkv, d, scale, None, None, 0)[0]
+    return _RopeCausalGQA.apply(_own_rows(qkv), cos_sin, kv_len, hq, hkv, d, scale, None, None, 0, False)[0]
 
 
 def rope_causal_gqa_varlen(qkv, cos_sin, pos_ids, cu_seqlens, max_len, hq, hkv, d, scale):
     """Packed layout: ``qkv`` [T, (hq + 2 hkv) * d] rows at positions ``pos_ids``, sequences by ``cu_seqlens`` (none longer than
     ``max_len``).  ``qkv`` is overwritten with its rotated form."""
-    return _RopeCausalGQA.apply(_own_rows(qkv), cos_sin, None, hq, hkv, d, scale, pos_ids, cu_seqlens, int(max_len))[0]
+    return _RopeCausalGQA.apply(_own_rows(qkv), cos_sin, None, hq, hkv, d, scale, pos_ids, cu_seqlens, int(max_len), False)[0]
+
+
+# EuroBERT encoders: the same node and the same two attention nodes without the causal mask (include/gmlm_hip_bidir.h)
+def bidir_gqa_attention(q, k, v, kv_len, hq, hkv, scale, d):
+    """``causal_attention`` without the causal mask: query i sees every key of its sequence below ``kv_len``; d = 64 or 128."""
+    return CausalAttention.apply(q, k, v, kv_len, hq, hkv, scale, d, True)
+
+
+def bidir_gqa_attention_varlen(q, k, v, cu_seqlens, max_len, hq, hkv, scale, d):
+    return CausalAttentionVarlen.apply(q, k, v, cu_seqlens, max_len, hq, hkv, scale, d, True)
+
+
+def rope_bidir_gqa(qkv, cos_sin, kv_len, hq, hkv, d, scale):
+    """``rope_causal_gqa`` with bidirectional attention: rotary embedding in place on ``qkv`` [b, l, (hq + 2 hkv) * d], then
+    grouped-KV attention over all keys below ``kv_len`` (int32 [b] or None).  ``qkv`` is overwritten with its rotated form."""
+    return _RopeCausalGQA.apply(_own_rows(qkv), cos_sin, kv_len, hq, hkv, d, scale, None, None, 0, True)[0]
+
+
+def rope_bidir_gqa_varlen(qkv, cos_sin, pos_ids, cu_seqlens, max_len, hq, hkv, d, scale):
+    """``rope_causal_gqa_varlen`` with bidirectional attention on packed ``qkv`` [T, (hq + 2 hkv) * d] rows."""
+    return _RopeCausalGQA.apply(_own_rows(qkv), cos_sin, None, hq, hkv, d, scale, pos_ids, cu_seqlens, int(max_len), True)[0]
 
 
 # ---------------------------------------------------------------------------------------------
