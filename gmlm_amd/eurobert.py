@@ -14,8 +14,8 @@ sees every key of its own sequence.  Which kernels run it:
   bidirectional grouped-KV kernels (attn_bidir.hip, include/gmlm_hip_bidir.h).
 
 Weights, rotary table (rope types default, linear and llama3) and head dim are llama.py's.  Two layouts: padded
-(``eurobert_encode``) and packed / varlen (``eurobert_encode_packed``).  There is no hipGraph, bucketed, short-sequence or ring
-form of this encoder (DESIGN.md section 4 "EuroBERT and NomicBERT encoders").
+(``eurobert_encode``) and packed / varlen (``eurobert_encode_packed``; with ``groups`` the grouped route at head dim 64 takes the
+short-sequence kernels of attn_gqa_short.hip).  There is no hipGraph, bucketed or ring form of this encoder (DESIGN.md section 4 "EuroBERT and NomicBERT encoders").
 """
 from __future__ import annotations
 
@@ -33,14 +33,15 @@ def check_supported(plm) -> None:
 
 
 def _layer(lw, stream, branch, lens, cs, hq, hkv, d, scale, eps, packed=None):
-    """``llama._layer`` with bidirectional attention; ``packed`` = (pos_ids, cu_seqlens, max_len)."""
+    """``llama._layer`` with bidirectional attention; ``packed`` = (pos_ids, cu_seqlens, max_len[, groups]); ``groups`` reaches
+    the grouped route only."""
     s1, y1 = ops.add_rmsnorm(stream, branch, lw.ln1, eps)
     qkv = _mm(y1, lw.wqkv, lw.bqkv, lw.m_qkv)
     if hq == hkv and d == 64:
-        ctx = ops.rope_attention_varlen(qkv, cs, *packed, hq, scale) if packed is not None else \
+        ctx = ops.rope_attention_varlen(qkv, cs, *packed[:3], hq, scale) if packed is not None else \
             ops.rope_attention(qkv, cs, lens, hq, scale)
     elif packed is not None:
-        ctx = ops.rope_bidir_gqa_varlen(qkv, cs, *packed, hq, hkv, d, scale)
+        ctx = ops.rope_bidir_gqa_varlen(qkv, cs, *packed[:3], hq, hkv, d, scale, groups=packed[3] if len(packed) > 3 else None)
     else:
         ctx = ops.rope_bidir_gqa(qkv, cs, lens, hq, hkv, d, scale)
     s2, y2 = ops.add_rmsnorm(s1, _mm(ctx, lw.wo, lw.bo, lw.m_wo), lw.ln2, eps)
@@ -61,13 +62,15 @@ def eurobert_encode(plm, input_ids: torch.Tensor, lens: torch.Tensor, cd: torch.
 
 
 def eurobert_encode_packed(plm, tok: torch.Tensor, pos: torch.Tensor, cu_seqlens: torch.Tensor, max_len: int, cd: torch.dtype,
-                           training: bool = False, gradient_checkpointing: bool = False, weights=None) -> torch.Tensor:
+                           training: bool = False, gradient_checkpointing: bool = False, weights=None, groups=None) -> torch.Tensor:
     """Packed (varlen) pass: tok / pos int [T] (token id and position of every row, the sequences back to back), cu_seqlens
-    int32 [S + 1] (sequence i = rows [cu[i], cu[i+1]), covering all T rows), max_len >= the longest sequence -> [T, P] in ``cd``."""
+    int32 [S + 1] (sequence i = rows [cu[i], cu[i+1]), covering all T rows), max_len >= the longest sequence -> [T, P] in ``cd``.
+    ``groups``: optional ``ops.pack_sequence_groups`` of the sequence lengths; with grouped KV heads at head dim 64, bf16,
+    max_len <= 128 and >= 512 (sequence, query head) pairs the attention runs on the short-sequence kernels."""
     max_len = int(max_len)
     encoder.check_length(plm.config, max_len)
     encoder.check_packed(tok, pos)
     x = torch.nn.functional.embedding(tok.long(), plm.embed_tokens.weight).to(cd)   # bit-exact row gather
     cs = rope_table(plm, max_len, x.device)
     return llama._encode_rows(plm, x, None, cs, cd, training, gradient_checkpointing, weights,
-                              (pos.to(torch.int32), cu_seqlens, max_len), layer=_layer)
+                              (pos.to(torch.int32), cu_seqlens, max_len, groups), layer=_layer)

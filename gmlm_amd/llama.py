@@ -133,11 +133,12 @@ def prepare_weights(plm, cd, gemm_precision="native"):
 
 def _layer(lw, stream, branch, lens, cs, hq, hkv, d, scale, eps, packed=None):
     """(residual stream, last branch output) of the previous layer -> the same pair after this layer; the add that joins them
-    is fused into the next RMSNorm.  ``packed`` = (pos_ids, cu_seqlens, max_len): the rows are [T, .] packed sequences."""
+    is fused into the next RMSNorm.  ``packed`` = (pos_ids, cu_seqlens, max_len[, groups]): the rows are [T, .] packed sequences;
+    ``groups`` (``ops.pack_sequence_groups``, optional) lets the attention take the short-sequence kernels."""
     s1, y1 = ops.add_rmsnorm(stream, branch, lw.ln1, eps)
     qkv = _mm(y1, lw.wqkv, lw.bqkv, lw.m_qkv)
     if packed is not None:
-        ctx = ops.rope_causal_gqa_varlen(qkv, cs, *packed, hq, hkv, d, scale)
+        ctx = ops.rope_causal_gqa_varlen(qkv, cs, *packed[:3], hq, hkv, d, scale, groups=packed[3] if len(packed) > 3 else None)
     else:
         ctx = ops.rope_causal_gqa(qkv, cs, lens, hq, hkv, d, scale)
     s2, y2 = ops.add_rmsnorm(s1, _mm(ctx, lw.wo, lw.bo, lw.m_wo), lw.ln2, eps)
@@ -173,9 +174,11 @@ def llama_encode(plm, input_ids: torch.Tensor, lens: torch.Tensor, cd: torch.dty
 
 
 def llama_encode_packed(plm, tok: torch.Tensor, pos: torch.Tensor, cu_seqlens: torch.Tensor, max_len: int, cd: torch.dtype,
-                        training: bool = False, gradient_checkpointing: bool = False, weights=None) -> torch.Tensor:
+                        training: bool = False, gradient_checkpointing: bool = False, weights=None, groups=None) -> torch.Tensor:
     """Packed (varlen) pass: tok / pos int [T] (token id and position of every row, the sequences back to back), cu_seqlens
-    int32 [S + 1] (sequence i = rows [cu[i], cu[i+1]), covering all T rows), max_len >= the longest sequence -> [T, P] in ``cd``."""
+    int32 [S + 1] (sequence i = rows [cu[i], cu[i+1]), covering all T rows), max_len >= the longest sequence -> [T, P] in ``cd``.
+    ``groups``: optional ``ops.pack_sequence_groups`` of the sequence lengths (int32 [G + 1] on the device): at head dim 64, bf16,
+    max_len <= 128 and >= 512 (sequence, query head) pairs the attention runs on the short-sequence kernels."""
     cfg = plm.config
     max_len = int(max_len)
     encoder.check_length(cfg, max_len)
@@ -183,4 +186,4 @@ def llama_encode_packed(plm, tok: torch.Tensor, pos: torch.Tensor, cu_seqlens: t
     encoder.check_packed(tok, pos)
     x = torch.nn.functional.embedding(tok.long(), plm.embed_tokens.weight).to(cd)   # bit-exact row gather
     cs = rope_table(plm, max_len, x.device)
-    return _encode_rows(plm, x, None, cs, cd, training, gradient_checkpointing, weights, (pos.to(torch.int32), cu_seqlens, max_len))
+    return _encode_rows(plm, x, None, cs, cd, training, gradient_checkpointing, weights, (pos.to(torch.int32), cu_seqlens, max_len, groups))

@@ -37,6 +37,10 @@ _ENCODERS = {"bert": (bert, "bert_encode", "bert_encode_packed"), "qwen3": (qwen
              "nomic_bert": (nomic_bert, "nomic_bert_encode", "nomic_bert_encode_packed"),
              **{kind: (llama, "llama_encode", "llama_encode_packed") for kind in llama.MODEL_TYPES}}
 
+# encoder modules whose packed pass takes ``groups`` (ops.pack_sequence_groups): grouped-KV attention at head dim 64 on the
+# short-sequence kernels (DESIGN.md section 4 "Short-sequence grouped attention" has the measurements behind each entry)
+GQA_SHORT_ENCODERS = (llama, eurobert)
+
 # static sizes of a captured text-encoder batch: sequences / tokens / attention work items are padded up to multiples of these
 ENCODER_BUCKET = (64, 2048, 32)
 
@@ -207,6 +211,17 @@ class GraphTextLM(nn.Module):
     @property
     def _enc(self):
         return _ENCODERS[self._plm_kind][0]
+
+    def _gqa_short_head_dim(self) -> int:
+        """Head dim of a Llama-family or EuroBERT encoder on its grouped-KV attention route, else 0 (a EuroBERT with one KV head
+        per query head at head dim 64 runs the BERT attention family, which has no ``groups`` on this pass)."""
+        cfg = self.plm_encoder.config
+        if self._enc not in (llama, eurobert):
+            return 0
+        d = llama.head_dim(cfg)
+        if self._enc is eurobert and cfg.num_attention_heads == cfg.num_key_value_heads and d == 64:
+            return 0
+        return d
 
     def _packed_head_dim(self) -> int:
         """Head dim of the text encoder if it has the forms built on the BERT packed pass (short-sequence groups, bucketed
@@ -465,14 +480,20 @@ class GraphTextLM(nn.Module):
                     # short sequences (the reference tokenises to <= 128 tokens, main.py:340): consecutive sequences are packed
                     # into attention work items of <= 128 rows (host arithmetic on the host copy of the lengths, ~0.2 ms per
                     # 1,000 sequences, once per batch: all layers, forward and backward, share it)
+                    n_seq = bi.numel() + (1 if pad else 0)
                     if self._enc is not bert:
                         encode = getattr(self._enc, _ENCODERS[self._plm_kind][2])
+                        more = {}
+                        if self._enc in GQA_SHORT_ENCODERS and self._gqa_short_head_dim() == 64 and cd == torch.bfloat16 \
+                                and lmax <= 128 and n_seq * heads >= 512:
+                            # grouped-KV encoders at head dim 64: the same groups (the dummy pad sequence included) put their
+                            # attention on the short-sequence kernels of attn_gqa_short.hip (ops._gqa_short_path)
+                            more["groups"] = to_dev(ops.pack_sequence_groups(lh.tolist() + ([pad] if pad else [])))
                         hs = encode(self.plm_encoder, tok, pos, cu_all, lmax, cd, self.plm_encoder.training,
-                                    self.plm_gradient_checkpointing, weights)
+                                    self.plm_gradient_checkpointing, weights, **more)
                         plm_embeds = ops.MeanPoolScatter.apply(plm_embeds, hs, None, bi, cu, total)
                         continue
                     groups = None
-                    n_seq = bi.numel() + (1 if pad else 0)
                     if cd == torch.bfloat16 and self._packed_head_dim() == 64 and lmax <= 128 and n_seq * heads >= 512:
                         groups = to_dev(ops.pack_sequence_groups(lh.tolist() + ([pad] if pad else [])))
                     hs = bert.bert_encode_packed(self.plm_encoder, tok, pos, cu_all, lmax, cd, self.plm_encoder.training,

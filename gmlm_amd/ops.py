@@ -495,6 +495,22 @@ def _short_path(dtype, d: int, rows: int, pairs: int) -> bool:
     return dtype == torch.bfloat16 and d == 64 and rows <= 128 and pairs >= 512
 
 
+def _gqa_short_path(groups, dtype, d: int, max_len: int, seqs: int, hq: int) -> bool:
+    """The one rule for the grouped-KV families (causal d = 64, bidirectional): the LDS-resident short-sequence entry points
+    (gmlm_attention_gqa_short_*, include/gmlm_hip_gqa_short.h) run iff the caller gave ``groups`` (packed layout only) and
+    ``_short_path`` holds for (sequences x query heads) pairs.  The 512 is the threshold measured for the K5 short kernels;
+    whether it is the right one for the grouped kernels has not been measured."""
+    return groups is not None and _short_path(dtype, d, max_len, seqs * hq)
+
+
+def _groups_arg(groups, cu_seqlens):
+    """``groups``: int32 [G + 1] on the device of ``cu_seqlens`` (``pack_sequence_groups``); -> G."""
+    if groups.dtype != torch.int32 or groups.dim() != 1 or groups.numel() < 1 or not groups.is_contiguous() \
+            or groups.device != cu_seqlens.device:
+        raise ValueError("groups must be a contiguous int32 [groups + 1] tensor on the device of cu_seqlens")
+    return groups.numel() - 1
+
+
 # A head-dim family of non-causal attention entry points: names, and getters that put arguments named as in the headers in ABI
 # order.  The orders are where families differ: out_lo last or after `out`, packed mode, seq_groups and dbias (`short`) or not.
 _AttnFamily = namedtuple("_AttnFamily", "fwd bwd ws fwd_args bwd_args ws_args packed short")
@@ -1227,7 +1243,8 @@ def _packed_stride(t: torch.Tensor, h: int, d: int = 128):
     return t.stride(0)
 
 
-def _causal_varlen_fwd(q, k, v, cu, s, max_len, hq, hkv, scale, want_lo, d=128, bidir=False):
+def _causal_varlen_fwd(q, k, v, cu, s, max_len, hq, hkv, scale, want_lo, d=128, bidir=False, groups=None):
+    """``groups`` set = the caller decided for the short-sequence route (``_gqa_short_path``): no out_lo comes back."""
     stem, tag = _gqa_entry(d, bidir)
     t = q.shape[0]
     qs, ks, vs = _packed_stride(q, hq, d), _packed_stride(k, hkv, d), _packed_stride(v, hkv, d)
@@ -1235,6 +1252,13 @@ def _causal_varlen_fwd(q, k, v, cu, s, max_len, hq, hkv, scale, want_lo, d=128, 
         raise ValueError("packed q, k and v must have the same number of rows")
     out = torch.empty(t, hq * d, dtype=q.dtype, device=q.device)
     lse = torch.empty(hq, t, dtype=torch.float32, device=q.device)
+    if groups is not None:
+        name = "gmlm_attention_gqa_short_fwd"
+        with _span(f"{tag}_short_fwd_d{d}", flops=(4.0 if bidir else 2.0) * s * hq * max_len * max_len * d):
+            check(getattr(lib(), name)(_ptr(q), _ptr(k), _ptr(v), _ptr(cu), s, max_len, t, hq, hkv, d, qs, ks, vs, float(scale), 0.0,
+                                       0 if bidir else 1, _ptr(groups), _groups_arg(groups, cu), _ptr(out), _ptr(lse), _dt(q),
+                                       _stream()), name)
+        return out, None, lse
     out_lo = torch.empty_like(out) if want_lo else None
     name = stem + "_varlen_fwd"
     with _span(f"{tag}_varlen_fwd_d{d}", flops=(4.0 if bidir else 2.0) * s * hq * max_len * max_len * d):
@@ -1243,10 +1267,18 @@ def _causal_varlen_fwd(q, k, v, cu, s, max_len, hq, hkv, scale, want_lo, d=128, 
     return out, out_lo, lse
 
 
-def _causal_varlen_bwd(q, k, v, out, out_lo, gout, lse, cu, s, max_len, hq, hkv, scale, dq, dk, dv, d=128, bidir=False):
+def _causal_varlen_bwd(q, k, v, out, out_lo, gout, lse, cu, s, max_len, hq, hkv, scale, dq, dk, dv, d=128, bidir=False, groups=None):
     stem, tag = _gqa_entry(d, bidir)
     t = q.shape[0]
     gout = gout.contiguous().to(q.dtype)
+    if groups is not None:                  # the short-sequence route: delta is formed in the kernel, no out / out_lo / workspace
+        name = "gmlm_attention_gqa_short_bwd"
+        with _span(f"{tag}_short_bwd_d{d}", flops=(10.0 if bidir else 5.0) * s * hq * max_len * max_len * d):
+            check(getattr(lib(), name)(_ptr(q), _ptr(k), _ptr(v), _ptr(gout), _ptr(lse), _ptr(cu), s, max_len, t, hq, hkv, d,
+                                       q.stride(0), k.stride(0), v.stride(0), float(scale), 0.0, 0 if bidir else 1, _ptr(groups),
+                                       _groups_arg(groups, cu), _ptr(dq), _ptr(dk), _ptr(dv), dq.stride(0), dk.stride(0),
+                                       dv.stride(0), _dt(q), _stream()), name)
+        return
     ws = _ws(getattr(lib(), stem + "_varlen_workspace_bytes")(t, hq), q.device)
     name = stem + "_varlen_bwd"
     with _span(f"{tag}_varlen_bwd_d{d}", flops=(10.0 if bidir else 5.0) * s * hq * max_len * max_len * d):
@@ -1259,31 +1291,35 @@ class CausalAttentionVarlen(torch.autograd.Function):
     """``CausalAttention`` on a packed batch: q [T, hq*d], k / v [T, hkv*d] (strided slices of a fused buffer are fine),
     sequence i = rows [cu_seqlens[i], cu_seqlens[i+1]) (int32 [S + 1]; a sequence may be empty, none is longer than
     ``max_len``), query i of a sequence sees its keys 0..i.  The sequences cover all T rows: a row that belongs to none is
-    neither read nor written, so its output and gradient rows would be uninitialised.  The three gradients are views of ONE fused [T, (hq + 2 hkv) * d] buffer."""
+    neither read nor written, so its output and gradient rows would be uninitialised.  The three gradients are views of ONE fused [T, (hq + 2 hkv) * d] buffer.
+    ``groups`` (int32 [G + 1], ``pack_sequence_groups``): where ``_gqa_short_path`` holds, the short-sequence kernels run, work
+    item g = sequences [groups[g], groups[g+1]); the node then saves neither ``out`` nor ``out_lo``.  Otherwise it is ignored."""
 
     @staticmethod
-    def forward(ctx, q, k, v, cu_seqlens, max_len, hq, hkv, scale, d=128, bidir=False):
+    def forward(ctx, q, k, v, cu_seqlens, max_len, hq, hkv, scale, d=128, bidir=False, groups=None):
         _cuda(q, k, v)
         s, max_len = _varlen_args(q, cu_seqlens, max_len)
-        want_lo = q.dtype == torch.bfloat16 and any(t.requires_grad for t in (q, k, v))
-        out, out_lo, lse = _causal_varlen_fwd(q, k, v, cu_seqlens, s, max_len, hq, hkv, scale, want_lo, d, bidir)
-        ctx.save_for_backward(q, k, v, out, lse, cu_seqlens, out_lo)
+        if not _gqa_short_path(groups, q.dtype, d, max_len, s, hq):
+            groups = None
+        want_lo = groups is None and q.dtype == torch.bfloat16 and any(t.requires_grad for t in (q, k, v))
+        out, out_lo, lse = _causal_varlen_fwd(q, k, v, cu_seqlens, s, max_len, hq, hkv, scale, want_lo, d, bidir, groups)
+        ctx.save_for_backward(q, k, v, out if groups is None else None, lse, cu_seqlens, out_lo, groups)
         ctx.cfg = (s, max_len, hq, hkv, float(scale), d, bidir)
         return out
 
     @staticmethod
     def backward(ctx, gout):
-        q, k, v, out, lse, cu, out_lo = ctx.saved_tensors
+        q, k, v, out, lse, cu, out_lo, groups = ctx.saved_tensors
         s, max_len, hq, hkv, scale, d, bidir = ctx.cfg
         nq, nk = hq * d, hkv * d
         dqkv = torch.empty(q.shape[0], nq + 2 * nk, dtype=q.dtype, device=q.device)
         dq, dk, dv = dqkv[:, :nq], dqkv[:, nq:nq + nk], dqkv[:, nq + nk:]
-        _causal_varlen_bwd(q, k, v, out, out_lo, gout, lse, cu, s, max_len, hq, hkv, scale, dq, dk, dv, d, bidir)
-        return dq, dk, dv, None, None, None, None, None, None, None
+        _causal_varlen_bwd(q, k, v, out, out_lo, gout, lse, cu, s, max_len, hq, hkv, scale, dq, dk, dv, d, bidir, groups)
+        return dq, dk, dv, None, None, None, None, None, None, None, None
 
 
-def causal_attention_varlen(q, k, v, cu_seqlens, max_len, hq, hkv, scale, d=128):
-    return CausalAttentionVarlen.apply(q, k, v, cu_seqlens, max_len, hq, hkv, scale, d, False)
+def causal_attention_varlen(q, k, v, cu_seqlens, max_len, hq, hkv, scale, d=128, groups=None):
+    return CausalAttentionVarlen.apply(q, k, v, cu_seqlens, max_len, hq, hkv, scale, d, False, groups)
 
 
 class RopeCausalAttentionVarlen(torch.autograd.Function):
@@ -1520,7 +1556,7 @@ class _RopeCausalGQA(torch.autograd.Function):
     ONE dqkv buffer, then the inverse rotation in place on it: a single data-gradient GEMM follows."""
 
     @staticmethod
-    def forward(ctx, qkv, cs, kv_len, hq, hkv, d, scale, pos_ids, cu_seqlens, max_len, bidir):
+    def forward(ctx, qkv, cs, kv_len, hq, hkv, d, scale, pos_ids, cu_seqlens, max_len, bidir, groups=None):
         _cuda(qkv)
         if d not in GQA_HEAD_DIMS:
             raise ValueError(f"head dim {d}: the rotary / grouped-KV attention kernels take {GQA_HEAD_DIMS}")
@@ -1538,29 +1574,32 @@ class _RopeCausalGQA(torch.autograd.Function):
         ctx.mark_dirty(qkv)
         nq, nk = hq * d, hkv * d
         q, k, v = qkv[..., :nq], qkv[..., nq:nq + nk], qkv[..., nq + nk:]
-        want_lo = qkv.dtype == torch.bfloat16 and qkv.requires_grad
+        if not (packed and _gqa_short_path(groups, qkv.dtype, d, max_len, s, hq)):
+            groups = None                                       # only the packed short-sequence kernels take groups
+        want_lo = groups is None and qkv.dtype == torch.bfloat16 and qkv.requires_grad
         if packed:
-            out, out_lo, lse = _causal_varlen_fwd(q, k, v, cu_seqlens, s, max_len, hq, hkv, scale, want_lo, d, bidir)
+            out, out_lo, lse = _causal_varlen_fwd(q, k, v, cu_seqlens, s, max_len, hq, hkv, scale, want_lo, d, bidir, groups)
         else:
             out, out_lo, lse = _causal_fwd(q, k, v, kv_len, hq, hkv, scale, want_lo, d, bidir)
-        ctx.save_for_backward(qkv, cs, out, out_lo, lse, kv_len, cu_seqlens, pos)
+        # the short-sequence backward reads neither the forward output nor its residual
+        ctx.save_for_backward(qkv, cs, out if groups is None else None, out_lo, lse, kv_len, cu_seqlens, pos, groups)
         ctx.cfg = (hq, hkv, d, float(scale), seq_len, int(max_len), bidir)
         return out, qkv
 
     @staticmethod
     def backward(ctx, gout, _gqkv):
-        qkv, cs, out, out_lo, lse, kv_len, cu, pos = ctx.saved_tensors
+        qkv, cs, out, out_lo, lse, kv_len, cu, pos, groups = ctx.saved_tensors
         hq, hkv, d, scale, seq_len, max_len, bidir = ctx.cfg
         nq, nk = hq * d, hkv * d
         q, k, v = qkv[..., :nq], qkv[..., nq:nq + nk], qkv[..., nq + nk:]
         dqkv = torch.empty_like(qkv)
         dq, dk, dv = dqkv[..., :nq], dqkv[..., nq:nq + nk], dqkv[..., nq + nk:]
         if cu is not None:
-            _causal_varlen_bwd(q, k, v, out, out_lo, gout, lse, cu, cu.numel() - 1, max_len, hq, hkv, scale, dq, dk, dv, d, bidir)
+            _causal_varlen_bwd(q, k, v, out, out_lo, gout, lse, cu, cu.numel() - 1, max_len, hq, hkv, scale, dq, dk, dv, d, bidir, groups)
         else:
             _causal_bwd(q, k, v, out, out_lo, gout, lse, kv_len, hq, hkv, scale, dq, dk, dv, d, bidir)
         rope_heads_(dqkv, cs, hq + hkv, d, seq_len, pos, inverse=True)
-        return (dqkv,) + (None,) * 10
+        return (dqkv,) + (None,) * 11
 
 
 def rope_causal_gqa(qkv, cos_sin, kv_len, hq, hkv, d, scale):
@@ -1569,10 +1608,11 @@ def rope_causal_gqa(qkv, cos_sin, kv_len, hq, hkv, d, scale):
     return _RopeCausalGQA.apply(_own_rows(qkv), cos_sin, kv_len, hq, hkv, d, scale, None, None, 0, False)[0]
 
 
-def rope_causal_gqa_varlen(qkv, cos_sin, pos_ids, cu_seqlens, max_len, hq, hkv, d, scale):
+def rope_causal_gqa_varlen(qkv, cos_sin, pos_ids, cu_seqlens, max_len, hq, hkv, d, scale, groups=None):
     """Packed layout: ``qkv`` [T, (hq + 2 hkv) * d] rows at positions ``pos_ids``, sequences by ``cu_seqlens`` (none longer than
-    ``max_len``).  ``qkv`` is overwritten with its rotated form."""
-    return _RopeCausalGQA.apply(_own_rows(qkv), cos_sin, None, hq, hkv, d, scale, pos_ids, cu_seqlens, int(max_len), False)[0]
+    ``max_len``).  ``qkv`` is overwritten with its rotated form.  ``groups`` (``pack_sequence_groups``): the short-sequence
+    kernels where ``_gqa_short_path`` holds."""
+    return _RopeCausalGQA.apply(_own_rows(qkv), cos_sin, None, hq, hkv, d, scale, pos_ids, cu_seqlens, int(max_len), False, groups)[0]
 
 
 # EuroBERT encoders: the same node and the same two attention nodes without the causal mask (include/gmlm_hip_bidir.h)
@@ -1581,8 +1621,8 @@ def bidir_gqa_attention(q, k, v, kv_len, hq, hkv, scale, d):
     return CausalAttention.apply(q, k, v, kv_len, hq, hkv, scale, d, True)
 
 
-def bidir_gqa_attention_varlen(q, k, v, cu_seqlens, max_len, hq, hkv, scale, d):
-    return CausalAttentionVarlen.apply(q, k, v, cu_seqlens, max_len, hq, hkv, scale, d, True)
+def bidir_gqa_attention_varlen(q, k, v, cu_seqlens, max_len, hq, hkv, scale, d, groups=None):
+    return CausalAttentionVarlen.apply(q, k, v, cu_seqlens, max_len, hq, hkv, scale, d, True, groups)
 
 
 def rope_bidir_gqa(qkv, cos_sin, kv_len, hq, hkv, d, scale):
@@ -1591,9 +1631,9 @@ def rope_bidir_gqa(qkv, cos_sin, kv_len, hq, hkv, d, scale):
     return _RopeCausalGQA.apply(_own_rows(qkv), cos_sin, kv_len, hq, hkv, d, scale, None, None, 0, True)[0]
 
 
-def rope_bidir_gqa_varlen(qkv, cos_sin, pos_ids, cu_seqlens, max_len, hq, hkv, d, scale):
+def rope_bidir_gqa_varlen(qkv, cos_sin, pos_ids, cu_seqlens, max_len, hq, hkv, d, scale, groups=None):
     """``rope_causal_gqa_varlen`` with bidirectional attention on packed ``qkv`` [T, (hq + 2 hkv) * d] rows."""
-    return _RopeCausalGQA.apply(_own_rows(qkv), cos_sin, None, hq, hkv, d, scale, pos_ids, cu_seqlens, int(max_len), True)[0]
+    return _RopeCausalGQA.apply(_own_rows(qkv), cos_sin, None, hq, hkv, d, scale, pos_ids, cu_seqlens, int(max_len), True, groups)[0]
 
 
 # ---------------------------------------------------------------------------------------------
