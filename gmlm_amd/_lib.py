@@ -1,5 +1,5 @@
 """ctypes binding of libgmlm_hip.so (C ABI: include/gmlm_hip.h, gmlm_hip_split.h, gmlm_hip_optim.h, gmlm_hip_d32.h,
-gmlm_hip_wide.h, gmlm_hip_modernbert.h, gmlm_hip_relbias.h, gmlm_hip_disent.h, gmlm_hip_gqa.h, gmlm_hip_bidir.h and gmlm_hip_gqa_short.h): one signature table per header, positional argument types only.  Which attention entry point a head dim
+gmlm_hip_wide.h, gmlm_hip_modernbert.h, gmlm_hip_relbias.h, gmlm_hip_disent.h, gmlm_hip_gqa.h, gmlm_hip_bidir.h, gmlm_hip_gqa_short.h and gmlm_hip_d32_short.h): one signature table per header, positional argument types only.  Which attention entry point a head dim
 takes, and where each ABI puts its arguments by name, is the family table of ops.py (``_ATTN_FAMILIES``).
 
 The product path has NO fallback: if the shared library is missing or a call fails, a Python
@@ -194,7 +194,17 @@ SIGNATURES_GQA_SHORT = {
                                                _f32, _i32, _p, _i64, _p, _p, _p, _i64, _i64, _i64, _i32, _p]),
 }
 
-SIGNATURE_TABLES_LATER = (SIGNATURES_RELBIAS, SIGNATURES_GQA, SIGNATURES_BIDIR, SIGNATURES_GQA_SHORT, SIGNATURES_DISENT)
+# twelfth header, include/gmlm_hip_d32_short.h (LDS-resident short-sequence attention at head dim 32, packed layout with seq_groups:
+# one h, dropout seed arguments, optional fused bias sums; no out_lo and no workspace)
+SIGNATURES_D32_SHORT = {
+    "gmlm_attention_d32_short_fwd": (C.c_int, [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _f32, _u64, _p,
+                                               _p, _i64, _p, _p, _i32, _p]),
+    "gmlm_attention_d32_short_bwd": (C.c_int, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _f32,
+                                               _u64, _p, _p, _i64, _p, _p, _p, _i64, _i64, _i64, _p, _p, _i32, _p]),
+}
+
+SIGNATURE_TABLES_LATER = (SIGNATURES_RELBIAS, SIGNATURES_GQA, SIGNATURES_BIDIR, SIGNATURES_GQA_SHORT, SIGNATURES_D32_SHORT,
+                          SIGNATURES_DISENT)
 
 
 class GmlmHipError(RuntimeError):

@@ -384,7 +384,7 @@ class GraphTextLM(nn.Module):
         lens_h = tokens.lens_host[idx_h]
         order = torch.argsort(lens_h, descending=True, stable=True)   # long sequences first: fuller attention work items
         cap = int(tokens.lens_host.max())
-        short = cd == torch.bfloat16 and self._packed_head_dim() == 64 and cap <= 128
+        short = cd == torch.bfloat16 and self._packed_head_dim() in (32, 64) and cap <= 128
         lens_all, s_b, t_b, groups_h = bucketed_layout(lens_h[order].tolist(), cap, short)
         short = short and s_b * heads >= 512
         bi_h = torch.full((s_b,), n, dtype=torch.long)
@@ -494,7 +494,7 @@ class GraphTextLM(nn.Module):
                         plm_embeds = ops.MeanPoolScatter.apply(plm_embeds, hs, None, bi, cu, total)
                         continue
                     groups = None
-                    if cd == torch.bfloat16 and self._packed_head_dim() == 64 and lmax <= 128 and n_seq * heads >= 512:
+                    if cd == torch.bfloat16 and self._packed_head_dim() in (32, 64) and lmax <= 128 and n_seq * heads >= 512:
                         groups = to_dev(ops.pack_sequence_groups(lh.tolist() + ([pad] if pad else [])))
                     hs = bert.bert_encode_packed(self.plm_encoder, tok, pos, cu_all, lmax, cd, self.plm_encoder.training,
                                                  self.plm_gradient_checkpointing, weights,

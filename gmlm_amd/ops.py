@@ -503,6 +503,26 @@ def _gqa_short_path(groups, dtype, d: int, max_len: int, seqs: int, hq: int) -> 
     return groups is not None and _short_path(dtype, d, max_len, seqs * hq)
 
 
+D32_SHORT_MIN_PAIRS = 96     # measured: the new route is not slower from the smallest count probed on (8 sequences x 12 heads)
+
+
+def _d32_short_path(groups, dtype, d: int, max_len: int, seqs: int, h: int) -> bool:
+    """The one rule for head dim 32: the LDS-resident short-sequence entry points (gmlm_attention_d32_short_*,
+    include/gmlm_hip_d32_short.h) run iff the caller gave ``groups`` (packed layout only), the dtype is bf16, ``d == 32``, no
+    sequence is longer than 128 rows, ``h`` is even (a work item is a pair of adjacent heads; the entry points refuse an odd
+    ``h``, which stays on the streaming ``gmlm_attention_d32_*`` kernels) and there are at least ``D32_SHORT_MIN_PAIRS``
+    (sequence, head) pairs: 96, the smallest count measured, where the one-launch backward already wins on launches alone (DESIGN.md
+    section 5 "Head dim 32, short sequences" has the table).  ``GraphTextLM`` builds ``groups`` from 512 pairs on, as at head dim 64."""
+    return groups is not None and dtype == torch.bfloat16 and d == 32 and max_len <= 128 and h % 2 == 0 \
+        and seqs * h >= D32_SHORT_MIN_PAIRS
+
+
+def _d32_short_common(q, k, v, cu_seqlens, b, max_len, l, h, hd3, scale, p, seed, sd, groups):
+    """Arguments both gmlm_attention_d32_short_* calls share, in header order: (head ..., seq_groups, num_groups)."""
+    return ((_ptr(cu_seqlens), b, int(max_len), l, h, 32, hd3, hd3, hd3, float(scale), float(p), seed, sd),
+            (_ptr(groups), _groups_arg(groups, cu_seqlens)))
+
+
 def _groups_arg(groups, cu_seqlens):
     """``groups``: int32 [G + 1] on the device of ``cu_seqlens`` (``pack_sequence_groups``); -> G."""
     if groups.dtype != torch.int32 or groups.dim() != 1 or groups.numel() < 1 or not groups.is_contiguous() \
@@ -643,7 +663,8 @@ class AttentionQKV(torch.autograd.Function):
         # packed: exact sum of len^2 when the caller knows it (host copy of the lengths), else the bound max_len * rows
         flops = 4.0 * h * d * ((float(pair_count) if pair_count else float(max_len) * l) if packed else float(b) * l * l)
         rows = int(max_len) if packed else l
-        short = _short_path(qkv.dtype, d, rows, b * h)
+        d32s = packed and _d32_short_path(groups, qkv.dtype, d, rows, b, h)     # head dim 32: its own short-sequence entry points
+        short = _short_path(qkv.dtype, d, rows, b * h) or d32s
         if groups is not None and not (packed and short):
             groups = None                                       # only the short-sequence kernels pack sequences into work items
         n_groups = 0 if groups is None else groups.numel() - 1
@@ -651,15 +672,20 @@ class AttentionQKV(torch.autograd.Function):
         nb = out.numel() * out.element_size()                   # one of q, k, v, o
         with _span("attn_fwd_d%d" % d, flops=flops, bytes=(4 + (1 if out_lo is not None else 0)) * nb):
             sd = ctx.sd = _sd()
-            _attention_fwd(True, q=_ptr(q), k=_ptr(k), v=_ptr(v), kv_len=_ptr(kv_len), b=b, h=h, lq=l, lk=l, d=d, q_stride=hd3,
-                           k_stride=hd3, v_stride=hd3, scale=float(scale), dropout_p=float(p), seed=seed, seed_dev=sd, out=_ptr(out),
-                           out_lo=_ptr(out_lo), lse=_ptr(lse), dtype=_dt(qkv), cu_seqlens=_ptr(cu_seqlens), max_len=int(max_len),
-                           seq_groups=_ptr(groups), num_groups=n_groups)
+            if d32s:
+                head, tail = _d32_short_common(q, k, v, cu_seqlens, b, max_len, l, h, hd3, scale, p, seed, sd, groups)
+                name = "gmlm_attention_d32_short_fwd"
+                check(getattr(lib(), name)(_ptr(q), _ptr(k), _ptr(v), *head, *tail, _ptr(out), _ptr(lse), _dt(qkv), _stream()), name)
+            else:
+                _attention_fwd(True, q=_ptr(q), k=_ptr(k), v=_ptr(v), kv_len=_ptr(kv_len), b=b, h=h, lq=l, lk=l, d=d, q_stride=hd3,
+                               k_stride=hd3, v_stride=hd3, scale=float(scale), dropout_p=float(p), seed=seed, seed_dev=sd, out=_ptr(out),
+                               out_lo=_ptr(out_lo), lse=_ptr(lse), dtype=_dt(qkv), cu_seqlens=_ptr(cu_seqlens), max_len=int(max_len),
+                               seq_groups=_ptr(groups), num_groups=n_groups)
         if short:
             ctx.save_for_backward(qkv, lse, kv_len, cu_seqlens, groups)        # the fused backward never reads the forward output
         else:
             ctx.save_for_backward(qkv, lse, kv_len, cu_seqlens, groups, out, out_lo)
-        ctx.short = short
+        ctx.short, ctx.d32s = short, d32s
         ctx.cfg = (h, float(scale), float(p), seed, int(max_len), b, l, flops)
         ctx.bias_shapes = [(m.shape[0], m.dtype) for m in bias_masters]
         return out
@@ -690,11 +716,17 @@ class AttentionQKV(torch.autograd.Function):
             db = torch.empty(hd3, dtype=torch.float32, device=qkv.device)
         # q, k, v, dO in; dq, dk, dv out (+ o, o_lo on the streaming path, which forms delta from them)
         with _span("attn_bwd_d%d" % d, flops=2.5 * flops, bytes=(7 + (0 if ctx.short else 2)) * qkv.numel() // 3 * qkv.element_size()):
-            _attention_bwd(qkv.device, True, q=_ptr(q), k=_ptr(k), v=_ptr(v), out=_ptr(out), out_lo=_ptr(out_lo), dout=_ptr(gout),
-                           lse=_ptr(lse), kv_len=_ptr(kv_len), b=b, h=h, lq=l, lk=l, d=d, q_stride=hd3, k_stride=hd3, v_stride=hd3,
-                           scale=scale, dropout_p=p, seed=seed, seed_dev=ctx.sd, dq=_ptr(dq), dk=_ptr(dk), dv=_ptr(dv), dq_stride=hd3,
-                           dk_stride=hd3, dv_stride=hd3, dtype=_dt(qkv), cu_seqlens=_ptr(cu_seqlens), max_len=max_len,
-                           dbias_partial=_ptr(part), dbias=_ptr(db), seq_groups=_ptr(groups), num_groups=n_groups)
+            if ctx.d32s:
+                head, tail = _d32_short_common(q, k, v, cu_seqlens, b, max_len, l, h, hd3, scale, p, seed, ctx.sd, groups)
+                name = "gmlm_attention_d32_short_bwd"
+                check(getattr(lib(), name)(_ptr(q), _ptr(k), _ptr(v), _ptr(gout), _ptr(lse), *head, *tail, _ptr(dq), _ptr(dk), _ptr(dv),
+                                           hd3, hd3, hd3, _ptr(part), _ptr(db), _dt(qkv), _stream()), name)
+            else:
+                _attention_bwd(qkv.device, True, q=_ptr(q), k=_ptr(k), v=_ptr(v), out=_ptr(out), out_lo=_ptr(out_lo), dout=_ptr(gout),
+                               lse=_ptr(lse), kv_len=_ptr(kv_len), b=b, h=h, lq=l, lk=l, d=d, q_stride=hd3, k_stride=hd3, v_stride=hd3,
+                               scale=scale, dropout_p=p, seed=seed, seed_dev=ctx.sd, dq=_ptr(dq), dk=_ptr(dk), dv=_ptr(dv),
+                               dq_stride=hd3, dk_stride=hd3, dv_stride=hd3, dtype=_dt(qkv), cu_seqlens=_ptr(cu_seqlens), max_len=max_len,
+                               dbias_partial=_ptr(part), dbias=_ptr(db), seq_groups=_ptr(groups), num_groups=n_groups)
         dbs = ()
         if want_db:
             if db is None:
