@@ -27,9 +27,13 @@
 // words, so the route does not change the mask.  A sequence may start at an odd tile row; then the two elements of an adjacent
 // register pair lie in different 2 x 2 hash tiles, so this file evaluates two words per register pair (equal when the start is
 // even) instead of the one of the group-relative mask of attn_short.hip.
-#include "attn_short.hpp"
-#include "attn_host.hpp"
-#include "colreduce.hpp"
+//
+// Where the pieces live: the forward staging (short_stage_fwd), the backward staging helpers and the phase 1 / phase 2 block
+// loops of one head (shared with attn_short.hip and attn_gqa_short.hip) are in attn_short.hpp; the launcher, the
+// packed-and-grouped argument checks and the bias-sum tail in attn_short_host.hpp.  This file keeps the head-pair frames, the
+// one-head views of the swizzled images, the per-sequence dropout policy and its own bias-sum stage (pm as hi + lo).
+#include "attn_short.hpp"        // device side: mask step, item bookkeeping, staging, forward body, backward block loops
+#include "attn_short_host.hpp"   // host side: launcher, tile height, argument checks, bias-sum tail
 #include "../../include/gmlm_hip_d32_short.h"
 
 namespace gmlm {
@@ -81,56 +85,28 @@ __device__ __forceinline__ void mma_acc_sw_head(const bf16_t* ts, int row0, cons
   }
 }
 
-__device__ __forceinline__ void meta_carve(ShortMeta& mt, void* at, int rows) {
-  mt.q2k_lo = reinterpret_cast<int16_t*>(at);
-  mt.q2k_hi = mt.q2k_lo + rows; mt.k2q_lo = mt.q2k_hi + rows; mt.k2q_hi = mt.k2q_lo + rows;
-  mt.qid = reinterpret_cast<uint8_t*>(mt.k2q_hi + rows);
-  mt.kid = mt.qid + rows;
-}
-
 // ------------------------------------------------------------------------------------------------
 // forward
 // ------------------------------------------------------------------------------------------------
 template <bool DROP, int R>
 __global__ __launch_bounds__(2 * R, 4) void fwd_kernel(AttnParams p) {
   using T = bf16_t;
-  constexpr int NT = 2 * R, CPR = W / 8, PER = R * CPR / NT, NB = R / 32;
+  constexpr int NB = R / 32;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   T* tk = reinterpret_cast<T*>(smem_raw);
   T* tv = tk + R * W;
-  ShortMeta mt;
-  meta_carve(mt, tv + R * W, R);
+  const ShortMeta mt = ShortMeta::carve(smem_raw + kShortFwdLds.meta_at(R), R);
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 31, h = lane >> 5;
   const int64_t pairs = p.h >> 1, item = blockIdx.x / pairs, hp = blockIdx.x % pairs;
   int64_t qbase, kbase, row0;
   int nq, nk;
   short_item_setup<R>(p, item, tid, mt, qbase, kbase, nq, nk, row0, 0);      // lse base of head 0 = first row of the item
-  const T* qg = static_cast<const T*>(p.q) + qbase * p.q_stride + hp * W;
-  const T* kg = static_cast<const T*>(p.k) + kbase * p.k_stride + hp * W;
-  const T* vg = static_cast<const T*>(p.v) + kbase * p.v_stride + hp * W;
-  // K and V of both heads are staged (MFMA A operands of every wave); a query row is used by its own lane pair alone and goes
-  // from global memory straight into the B-operand registers, both heads at once, issued together with the K / V loads
+  // K and V of both heads are staged (MFMA A operands of every wave); the query row goes straight into the B-operand registers,
+  // both heads at once
   const int q_row = w * 32 + r;
   RowFrag<T, W> qf;
-  qf.load(qg + (uint32_t)((q_row < nq ? q_row : 0) * (int)p.q_stride), q_row < nq, h);
-  uint4 rk[PER], rv[PER];
-#pragma unroll
-  for (int k = 0; k < PER; ++k) {
-    const int i = tid + k * NT, row = i / CPR, col = (i % CPR) * 8;
-    rk[k] = rv[k] = make_uint4(0, 0, 0, 0);
-    if (row < nk) {
-      rk[k] = *reinterpret_cast<const uint4*>(kg + (uint32_t)(row * (int)p.k_stride + col));
-      rv[k] = *reinterpret_cast<const uint4*>(vg + (uint32_t)(row * (int)p.v_stride + col));
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < PER; ++k) {
-    const int i = tid + k * NT, row = i / CPR;
-    const int c = i % CPR;                                      // 16-byte chunk of the row -> swizzled slot (attn_common.hpp)
-    *reinterpret_cast<uint4*>(tk + row * W + ((c ^ sw_row(row)) << 3)) = rk[k];
-    *reinterpret_cast<uint4*>(tv + row * W + ((c ^ sw_tr(row)) << 3)) = rv[k];
-  }
-  __syncthreads();
+  short_stage_fwd<R>(p, static_cast<const T*>(p.q) + qbase * p.q_stride + hp * W, static_cast<const T*>(p.k) + kbase * p.k_stride + hp * W,
+                     static_cast<const T*>(p.v) + kbase * p.v_stride + hp * W, nq, nk, tk, tv, qf, tid, q_row, h);
   if (w * 32 >= nq) return;                                   // (no barrier below)
   const bf16x8 qm = antihot_frag(mt.qid[q_row], h);
   int b0, b1;
@@ -186,22 +162,41 @@ __global__ __launch_bounds__(2 * R, 4) void fwd_kernel(AttnParams p) {
 // ------------------------------------------------------------------------------------------------
 // backward
 // ------------------------------------------------------------------------------------------------
+// tiles K, V, Q, dO | lse, delta [2][R] each: per head of the pair | bias-gradient coefficients (p.dbias_part), bf16 hi + lo
+// pairs, per head: per key c_k = sum_q dS[q,k], per query pm_q = sum_k P'[q,k] (1 without dropout; with it any value around 1, and
+// one bf16 rounding of it is 2^-9 of the dV sums): [2][4][R] | meta
+constexpr ShortLds kBwdLds{4, kShortPitch, 4, 8};
+
+// the per-sequence dropout mask as the policy of the block loops.  u: base + (own >> 1) * C_own for the lane's own row counted from
+// its sequence's first row, odd: that row's parity, off: 4 h - first tile row of the sequence (tile row on the other axis -> row
+// of the sequence)
+template <bool DROP>
+struct BwdPolicy {
+  bool bias;
+  uint32_t u, th;
+  int odd, off;
+  float ks;
+  __device__ __forceinline__ void pair_q(int kb, int i, float&, float&, float& m0, float& m1) const {
+    if (DROP) drop_pair_rel<true>(u, odd, kb * 32 + acc_row(i, 0) + off, th, ks, m0, m1);
+  }
+  __device__ __forceinline__ void pair_k(int qb, int i, float&, float&, float& m0, float& m1) const {
+    if (DROP) drop_pair_rel<false>(u, odd, qb * 32 + acc_row(i, 0) + off, th, ks, m0, m1);
+  }
+};
+
 template <bool DROP, int R>
 __global__ __launch_bounds__(2 * R, R >= 96 ? 2 : 3) void bwd_kernel(AttnParams p) {
   using T = bf16_t;
-  constexpr int NT = 2 * R, PITCH = W + Pad<T>::v, CPR = W / 8, PER = R * CPR / NT, NB = R / 32;
+  constexpr int NT = 2 * R, PITCH = kShortPitch;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   T* tk = reinterpret_cast<T*>(smem_raw);
   T* tv = tk + R * PITCH;
   T* tq = tv + R * PITCH;
   T* tdo = tq + R * PITCH;
-  float* lse_s = reinterpret_cast<float*>(tdo + R * PITCH);   // [2][R]: per head of the pair
-  float* dl_s = lse_s + 2 * R;                                // [2][R]
-  // bias-gradient coefficients (p.dbias_part), bf16 hi + lo pairs, per head: per key c_k = sum_q dS[q,k], per query pm_q =
-  // sum_k P'[q,k] (1 without dropout; with it any value around 1, and one bf16 rounding of it is 2^-9 of the dV sums): [2][4][R]
-  T* coef = reinterpret_cast<T*>(dl_s + 2 * R);
-  ShortMeta mt;
-  meta_carve(mt, coef + 8 * R, R);
+  float* lse_s = reinterpret_cast<float*>(smem_raw + kBwdLds.floats_at(R));   // [2][R]
+  float* dl_s = lse_s + 2 * R;                                                // [2][R]
+  T* coef = reinterpret_cast<T*>(smem_raw + kBwdLds.coef_at(R));
+  const ShortMeta mt = ShortMeta::carve(smem_raw + kBwdLds.meta_at(R), R);
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 31, h = lane >> 5;
   const int64_t pairs = p.h >> 1, item = blockIdx.x / pairs, hp = blockIdx.x % pairs;
   const bool bgrad = p.dbias_part != nullptr;                // block-uniform
@@ -210,45 +205,19 @@ __global__ __launch_bounds__(2 * R, R >= 96 ? 2 : 3) void bwd_kernel(AttnParams 
   int64_t qbase, kbase, row0;
   int nq, nk;
   short_item_setup<R>(p, item, tid, mt, qbase, kbase, nq, nk, row0, 0);
-  const T* qg = static_cast<const T*>(p.q) + qbase * p.q_stride + hp * W;
-  const T* kg = static_cast<const T*>(p.k) + kbase * p.k_stride + hp * W;
-  const T* vg = static_cast<const T*>(p.v) + kbase * p.v_stride + hp * W;
   const int do_stride = (int)(p.h * D);
-  const T* dog = static_cast<const T*>(p.dout) + qbase * do_stride + hp * W;
-  // ---- staging: all loads first (32-bit offsets: rows <= 128, strides < 2^24), then the LDS image ----
-  uint4 rk[PER], rv[PER], rq[PER], rdo[PER];
-#pragma unroll
-  for (int k = 0; k < PER; ++k) {
-    const int i = tid + k * NT, row = i / CPR, col = (i % CPR) * 8;
-    rk[k] = rv[k] = rq[k] = rdo[k] = make_uint4(0, 0, 0, 0);
-    if (row < nk) {
-      rk[k] = *reinterpret_cast<const uint4*>(kg + (uint32_t)(row * (int)p.k_stride + col));
-      rv[k] = *reinterpret_cast<const uint4*>(vg + (uint32_t)(row * (int)p.v_stride + col));
-    }
-    if (row < nq) {
-      rq[k] = *reinterpret_cast<const uint4*>(qg + (uint32_t)(row * (int)p.q_stride + col));
-      rdo[k] = *reinterpret_cast<const uint4*>(dog + (uint32_t)(row * do_stride + col));
-    }
-  }
+  uint4 rg[4][4];
+  short_rows_load<R, 4>(rg, {static_cast<const T*>(p.k) + kbase * p.k_stride + hp * W, static_cast<const T*>(p.v) + kbase * p.v_stride + hp * W,
+                             static_cast<const T*>(p.q) + qbase * p.q_stride + hp * W, static_cast<const T*>(p.dout) + qbase * do_stride + hp * W},
+                        {(int)p.k_stride, (int)p.v_stride, (int)p.q_stride, do_stride}, {nk, nq}, tid);
   {                                                          // +inf: a row past the item gets probability 0
     const int hh = tid / R, row = tid % R;                    // NT = 2 R threads: one (head, row) each
     lse_s[tid] = row < nq ? p.lse[(2 * hp + hh) * p.lq + row0 + row] * kLog2e : INFINITY;
   }
-#pragma unroll
-  for (int k = 0; k < PER; ++k) {
-    const int i = tid + k * NT, row = i / CPR, col = (i % CPR) * 8;
-    *reinterpret_cast<uint4*>(tk + row * PITCH + col) = rk[k];
-    *reinterpret_cast<uint4*>(tv + row * PITCH + col) = rv[k];
-    *reinterpret_cast<uint4*>(tq + row * PITCH + col) = rq[k];
-    *reinterpret_cast<uint4*>(tdo + row * PITCH + col) = rdo[k];
-  }
+  short_rows_store<R, 4>({tk, tv, tq, tdo}, rg, tid);
   __syncthreads();
   const float sl2 = p.scale * kLog2e;
   const uint32_t seed_mix = drop_base(attn_seed(p), 0);
-  auto frag = [&](const T* tile, int row, RowFrag<T, D>& f) {          // MFMA B-operand fragment of one head's half of a staged row
-#pragma unroll
-    for (int s = 0; s < D / 16; ++s) f.v[s] = *reinterpret_cast<const bf16x8*>(tile + row * PITCH + 16 * s + 8 * h);
-  };
   // ---- phase 1: delta and dQ (query on the lane; K, V as MFMA A operands), head after head -----------------
   if (w * 32 < nq) {
     const int q_row = w * 32 + r;
@@ -256,53 +225,15 @@ __global__ __launch_bounds__(2 * R, R >= 96 ? 2 : 3) void bwd_kernel(AttnParams 
     int b0, b1;
     block_range(mt.q2k_lo, mt.q2k_hi, w, nq, b0, b1);
     const int lo = mt.q2k_lo[q_row];
-    const int q_rel = q_row - lo, q_odd = q_rel & 1, k_off = 4 * h - lo;
+    const int q_rel = q_row - lo;
 #pragma unroll
     for (int hh = 0; hh < 2; ++hh) {
       const int64_t hd = 2 * hp + hh;
-      const T *tkh = tk + hh * D, *tvh = tv + hh * D;
-      RowFrag<T, D> qf, dof;
-      frag(tq + hh * D, q_row, qf);
-      frag(tdo + hh * D, q_row, dof);
-      const float lse2 = lse_s[hh * R + q_row];
-      const uint32_t dq_u = seed_mix + (uint32_t)(hd * p.lq + row0 + lo) * kDropC3 + (uint32_t)(q_rel >> 1) * kDropC1;
-      // pass A: P and dP' (= dP through the dropout mask) of every key block, kept in registers; delta = sum_k P dP' in fp32
-      f32x16 pr[NB], dpm[NB];
-      float dsum = 0.f, pm = 0.f;                             // this half-wave's shares of delta and of sum_k P'[q,k]
-#pragma unroll
-      for (int kb = 0; kb < NB; ++kb) {
-        if (kb < b0 || kb >= b1) continue;                    // wave-uniform
-        f32x16 z;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) { z[i] = 0.f; dpm[kb][i] = 0.f; }
-        pr[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(onehot_frag(mt.kid[kb * 32 + r], h), qm, z, 0, 0, 0);
-        mma_rows<D>(tkh, PITCH, kb * 32, qf, pr[kb], r, h);
-        mma_rows<D>(tvh, PITCH, kb * 32, dof, dpm[kb], r, h);
-#pragma unroll
-        for (int i = 0; i < 16; i += 2) {
-          const float p0 = fast_exp2(fmaf(pr[kb][i], sl2, -lse2)), p1 = fast_exp2(fmaf(pr[kb][i + 1], sl2, -lse2));   // masked: exactly 0
-          float m0 = 1.f, m1 = 1.f;
-          if (DROP) drop_pair_rel<true>(dq_u, q_odd, kb * 32 + acc_row(i, 0) + k_off, p.drop_thresh, p.keep_scale, m0, m1);
-          const float d0 = dpm[kb][i] * m0, d1 = dpm[kb][i + 1] * m1;
-          dsum = fmaf(p1, d1, fmaf(p0, d0, dsum));
-          if (bgrad) pm = fmaf(p1, m1, fmaf(p0, m0, pm));
-          pr[kb][i] = p0; pr[kb][i + 1] = p1;
-          dpm[kb][i] = d0; dpm[kb][i + 1] = d1;
-        }
-      }
-      const float dl = xhalf_sum(dsum);
-      if (h == 0) dl_s[hh * R + q_row] = dl;
-      // pass B: dS = P (dP' - delta); dQ^T += K^T dS^T
+      const BwdPolicy<DROP> pol{bgrad, seed_mix + (uint32_t)(hd * p.lq + row0 + lo) * kDropC3 + (uint32_t)(q_rel >> 1) * kDropC1, p.drop_thresh,
+                                q_rel & 1, 4 * h - lo, p.keep_scale};
       f32x16 dq[1];
-#pragma unroll
-      for (int i = 0; i < 16; ++i) dq[0][i] = 0.f;
-#pragma unroll
-      for (int kb = 0; kb < NB; ++kb) {
-        if (kb < b0 || kb >= b1) continue;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) pr[kb][i] *= dpm[kb][i] - dl;
-        mma_acc<D>(tkh, PITCH, kb * 32, pr[kb], dq, lane);
-      }
+      float pm = short_bwd_phase1<D, R>(tk + hh * D, tv + hh * D, tq + hh * D, tdo + hh * D, lse_s + hh * R, dl_s + hh * R, mt, qm, b0, b1, sl2,
+                                        pol, q_row, lane, dq);
       if (q_row < nq) {
         T* dqg = static_cast<T*>(p.dq) + (qbase + q_row) * p.dq_stride + hd * D;
         store_t<T>(dqg, dq[0], p.scale, h);
@@ -327,54 +258,18 @@ __global__ __launch_bounds__(2 * R, R >= 96 ? 2 : 3) void bwd_kernel(AttnParams 
     block_range(mt.k2q_lo, mt.k2q_hi, w, nk, b0, b1);       // empty when the wave holds padding keys only
     const bf16x8 km = antihot_frag(mt.kid[key], h);
     const int lo = mt.k2q_lo[key];
-    const int k_rel = key - lo, k_odd = k_rel & 1, q_off = 4 * h - lo;
+    const int k_rel = key - lo;
 #pragma unroll
     for (int hh = 0; hh < 2; ++hh) {
       const int64_t hd = 2 * hp + hh;
-      const T *tqh = tq + hh * D, *tdoh = tdo + hh * D;
       f32x16 dk[1], dv[1];
 #pragma unroll
       for (int i = 0; i < 16; ++i) { dk[0][i] = 0.f; dv[0][i] = 0.f; }
       if (b1 > b0) {
-        RowFrag<T, D> kf, vf;
-        frag(tk + hh * D, key, kf);
-        frag(tv + hh * D, key, vf);
-        const uint32_t dk_u = seed_mix + (uint32_t)(hd * p.lq + row0 + lo) * kDropC3 + (uint32_t)(k_rel >> 1) * kDropC2;
-        const float* lse_h = lse_s + hh * R;
-        const float* dl_h = dl_s + hh * R;
-        float ck = 0.f;                                       // this half-wave's share of sum_q dS[q,key]
-#pragma unroll
-        for (int qb = 0; qb < NB; ++qb) {
-          if (qb < b0 || qb >= b1) continue;                  // wave-uniform
-          f32x16 s, dp, z;
-#pragma unroll
-          for (int i = 0; i < 16; ++i) { z[i] = 0.f; dp[i] = 0.f; }
-          s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(onehot_frag(mt.qid[qb * 32 + r], h), km, z, 0, 0, 0);
-          mma_rows<D>(tqh, PITCH, qb * 32, kf, s, r, h);
-          mma_rows<D>(tdoh, PITCH, qb * 32, vf, dp, r, h);
-#pragma unroll
-          for (int g4 = 0; g4 < 4; ++g4) {
-            const int q4 = qb * 32 + 8 * g4 + 4 * h;           // accumulator registers 4*g4 .. 4*g4+3 = queries q4 .. q4+3
-            const float4 l4 = *reinterpret_cast<const float4*>(lse_h + q4);
-            const float4 d4 = *reinterpret_cast<const float4*>(dl_h + q4);
-            const float lq4[4] = {l4.x, l4.y, l4.z, l4.w}, dq4[4] = {d4.x, d4.y, d4.z, d4.w};
-#pragma unroll
-            for (int j = 0; j < 4; j += 2) {
-              const int i = 4 * g4 + j;                        // registers i, i+1 = queries q4 + j, + 1 (even, odd tile rows)
-              // rows past the item carry lse = +inf in LDS, other sequences' rows / padding keys sit at -1.3e30: probability 0
-              const float p0 = fast_exp2(fmaf(s[i], sl2, -lq4[j])), p1 = fast_exp2(fmaf(s[i + 1], sl2, -lq4[j + 1]));
-              float m0 = 1.f, m1 = 1.f;
-              if (DROP) drop_pair_rel<false>(dk_u, k_odd, qb * 32 + 8 * g4 + j + q_off, p.drop_thresh, p.keep_scale, m0, m1);
-              s[i] = p0 * m0;
-              s[i + 1] = p1 * m1;
-              dp[i] = p0 * (dp[i] * m0 - dq4[j]);
-              dp[i + 1] = p1 * (dp[i + 1] * m1 - dq4[j + 1]);
-              if (bgrad) ck += dp[i] + dp[i + 1];
-            }
-          }
-          mma_acc<D>(tdoh, PITCH, qb * 32, s, dv, lane);
-          mma_acc<D>(tqh, PITCH, qb * 32, dp, dk, lane);
-        }
+        const BwdPolicy<DROP> pol{bgrad, seed_mix + (uint32_t)(hd * p.lq + row0 + lo) * kDropC3 + (uint32_t)(k_rel >> 1) * kDropC2, p.drop_thresh,
+                                  k_rel & 1, 4 * h - lo, p.keep_scale};
+        float ck = short_bwd_phase2<D, R>(tk + hh * D, tv + hh * D, tq + hh * D, tdo + hh * D, lse_s + hh * R, dl_s + hh * R, mt, km, b0, b1, sl2,
+                                          pol, key, lane, dk, dv);
         if (bgrad) {
           ck = xhalf_sum(ck);
           if (h == 0) {
@@ -425,14 +320,6 @@ __global__ __launch_bounds__(2 * R, R >= 96 ? 2 : 3) void bwd_kernel(AttnParams 
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-static size_t fwd_lds(int r) { return (size_t)2 * r * W * sizeof(bf16_t) + (size_t)r * (4 * sizeof(int16_t) + 2); }
-static size_t bwd_lds(int r) {
-  return (size_t)4 * r * (W + 8) * sizeof(bf16_t) + 4 * r * sizeof(float) + 8 * r * sizeof(bf16_t) + (size_t)r * (4 * sizeof(int16_t) + 2);
-}
-
-// no group holds more rows than the batch has, nor more than 128: the tile height, a multiple of 32
-static int tile_rows(int64_t total_rows) { return (int)((total_rows < 128 ? total_rows : 128) + 31) / 32 * 32; }
-
 // Validation up to the nothing-to-do return, in the order of include/gmlm_hip_d32_short.h; fills the launch parameters
 static int setup(const char* who, AttnParams& p, const void* q, const void* k, const void* v, const int32_t* cu, int64_t seqs,
                  int64_t max_len, int64_t rows, int64_t h, int64_t d, int64_t q_stride, int64_t k_stride, int64_t v_stride, float scale,
@@ -443,76 +330,23 @@ static int setup(const char* who, AttnParams& p, const void* q, const void* k, c
   GMLM_REQUIRE(h % 2 == 0, "%s: h = %ld heads: a work item is a pair of adjacent heads, h must be even", who, (long)h);
   GMLM_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "%s: dropout_p must be in [0,1)", who);
   GMLM_REQUIRE(scale > 0.f, "%s: scale must be positive", who);
-  GMLM_REQUIRE(cu, "%s: null cu_seqlens", who);
-  GMLM_REQUIRE(groups, "%s: null seq_groups", who);
-  GMLM_REQUIRE(num_groups >= 0, "%s: num_groups %ld must be >= 0", who, (long)num_groups);
-  GMLM_REQUIRE(max_len > 0 && max_len <= 128, "%s: max_len %ld must be in 1..128", who, (long)max_len);
-  GMLM_REQUIRE(rows >= 0 && rows < ((int64_t)1 << 30), "%s: total_rows %ld must be >= 0 and < 2^30", who, (long)rows);
+  int rc;
+  if ((rc = short_check_packed(who, cu, groups, num_groups, max_len, rows)) != GMLM_OK) return rc;
   GMLM_REQUIRE(num_groups > 0 || rows == 0 || seqs == 0, "%s: num_groups must be > 0 with rows present", who);
   // what the host can see of the group bounds without reading device memory (the kernels clamp the rest)
   GMLM_REQUIRE(num_groups == 0 || seqs <= num_groups * kShortMaxSeq, "%s: seq_groups: %ld sequences in %ld groups, a group takes at most %d",
                who, (long)seqs, (long)num_groups, kShortMaxSeq);
   GMLM_REQUIRE(num_groups == 0 || rows <= num_groups * 128, "%s: seq_groups: %ld rows in %ld groups, a group takes at most 128", who,
                (long)rows, (long)num_groups);
-  GMLM_REQUIRE(num_groups <= (((int64_t)1 << 31) - 1) / h, "%s: too many work items", who);
+  if ((rc = short_check_items(who, num_groups, h)) != GMLM_OK) return rc;
   p = AttnParams{};
   attn_fill(p, q, k, v, nullptr, seqs, h, rows, rows, q_stride, k_stride, v_stride, scale, dropout_p, seed, seed_dev);
   p.cu = cu; p.groups = groups;
   return GMLM_OK;
 }
 
-#define GMLM_D32S_FOR_R(M) M(128) M(96) M(64) M(32)
-
-static int launch_fwd(const AttnParams& p, int top, int64_t num_groups, hipStream_t st) {
-  static PerDeviceOnce once;
-  int rc = once([&]() -> int {
-#define GMLM_D32S_ATTR(RR)                                                                                                         \
-    GMLM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&fwd_kernel<false, RR>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fwd_lds(RR))); \
-    GMLM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&fwd_kernel<true, RR>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fwd_lds(RR)));
-    GMLM_D32S_FOR_R(GMLM_D32S_ATTR)
-#undef GMLM_D32S_ATTR
-    return GMLM_OK;
-  });
-  if (rc != GMLM_OK) return rc;
-  const unsigned grid = (unsigned)(num_groups * (p.h / 2));
-#define GMLM_D32S_LAUNCH(RR)                                                                    \
-  if (RR == top) {                                                                              \
-    if (p.drop_thresh) fwd_kernel<true, RR><<<grid, 2 * RR, fwd_lds(RR), st>>>(p);              \
-    else fwd_kernel<false, RR><<<grid, 2 * RR, fwd_lds(RR), st>>>(p);                           \
-  }
-  GMLM_D32S_FOR_R(GMLM_D32S_LAUNCH)
-#undef GMLM_D32S_LAUNCH
-  GMLM_LAUNCH_CHECK();
-  return GMLM_OK;
-}
-
-static int launch_bwd(const AttnParams& p, int top, int64_t num_groups, float* dbias, hipStream_t st) {
-  static PerDeviceOnce once;
-  int rc = once([&]() -> int {
-#define GMLM_D32S_ATTR(RR)                                                                                                         \
-    GMLM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&bwd_kernel<false, RR>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bwd_lds(RR))); \
-    GMLM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&bwd_kernel<true, RR>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bwd_lds(RR)));
-    GMLM_D32S_FOR_R(GMLM_D32S_ATTR)
-#undef GMLM_D32S_ATTR
-    return GMLM_OK;
-  });
-  if (rc != GMLM_OK) return rc;
-  const unsigned grid = (unsigned)(num_groups * (p.h / 2));
-#define GMLM_D32S_LAUNCH(RR)                                                                    \
-  if (RR == top) {                                                                              \
-    if (p.drop_thresh) bwd_kernel<true, RR><<<grid, 2 * RR, bwd_lds(RR), st>>>(p);              \
-    else bwd_kernel<false, RR><<<grid, 2 * RR, bwd_lds(RR), st>>>(p);                           \
-  }
-  GMLM_D32S_FOR_R(GMLM_D32S_LAUNCH)
-#undef GMLM_D32S_LAUNCH
-  GMLM_LAUNCH_CHECK();
-  if (dbias) {                                             // [groups, 3 h d] partial column sums -> [3 h d], fixed order
-    const int64_t width = 3 * p.h * D;
-    rows_sum_kernel<<<(unsigned)cdiv(width, 32), 256, 0, st>>>(p.dbias_part, (int)num_groups, width, dbias, 1.f);
-    GMLM_LAUNCH_CHECK();
-  }
-  return GMLM_OK;
-}
+#define GMLM_D32S_FWD(F, RR) fwd_kernel<F, RR>
+#define GMLM_D32S_BWD(F, RR) bwd_kernel<F, RR>
 
 }  // namespace d32s
 }  // namespace gmlm
@@ -534,7 +368,8 @@ extern "C" int gmlm_attention_d32_short_fwd(const void* q, const void* k, const 
   p.o_w = out; p.lse_w = lse;
   if ((rc = attn_check_fwd_operands(who, p, h * d, h * d, dtype)) != GMLM_OK) return rc;
   GMLM_REQUIRE(lse, "%s: null lse", who);
-  return launch_fwd(p, tile_rows(total_rows), num_groups, as_stream(stream));
+  static ShortKernels<AttnParams> t{GMLM_SHORT_KERNELS(GMLM_D32S_FWD), kShortFwdLds};
+  return short_launch(t, short_tile_rows(total_rows), p.drop_thresh != 0, (unsigned)(num_groups * (h / 2)), as_stream(stream), p);
 }
 
 extern "C" int gmlm_attention_d32_short_bwd(const void* q, const void* k, const void* v, const void* dout, const float* lse,
@@ -552,13 +387,9 @@ extern "C" int gmlm_attention_d32_short_bwd(const void* q, const void* k, const 
   if (num_groups == 0 || num_seqs == 0 || total_rows == 0) return GMLM_OK;
   attn_fill_bwd(p, nullptr, nullptr, dout, lse, dq, dk, dv, dq_stride, dk_stride, dv_stride, nullptr);
   p.dbias_part = dbias_partial;
-  const int64_t wd = h * d;
-  if ((rc = attn_stride_check(who, "q", p.q, p.q_stride, wd, dtype)) != GMLM_OK) return rc;
-  if ((rc = attn_stride_check(who, "k", p.k, p.k_stride, wd, dtype)) != GMLM_OK) return rc;
-  if ((rc = attn_stride_check(who, "v", p.v, p.v_stride, wd, dtype)) != GMLM_OK) return rc;
-  if ((rc = attn_stride_check(who, "dq", p.dq, p.dq_stride, wd, dtype)) != GMLM_OK) return rc;
-  if ((rc = attn_stride_check(who, "dk", p.dk, p.dk_stride, wd, dtype)) != GMLM_OK) return rc;
-  if ((rc = attn_stride_check(who, "dv", p.dv, p.dv_stride, wd, dtype)) != GMLM_OK) return rc;
-  GMLM_REQUIRE(p.dout && p.lse && aligned16(p.dout), "%s: null or misaligned dout/lse", who);
-  return launch_bwd(p, tile_rows(total_rows), num_groups, dbias, as_stream(stream));
+  if ((rc = attn_check_short_bwd_operands(who, p, h * d, h * d, dtype)) != GMLM_OK) return rc;
+  static ShortKernels<AttnParams> t{GMLM_SHORT_KERNELS(GMLM_D32S_BWD), kBwdLds};
+  rc = short_launch(t, short_tile_rows(total_rows), p.drop_thresh != 0, (unsigned)(num_groups * (h / 2)), as_stream(stream), p);
+  if (rc != GMLM_OK || !dbias) return rc;
+  return short_bias_sums(p.dbias_part, num_groups, 3 * h * d, dbias, as_stream(stream));   // [groups, 3 h d] -> [3 h d]
 }

@@ -73,18 +73,32 @@ inline int attn_check_fwd_operands(const char* who, const AttnParams& p, int64_t
   return GMLM_OK;
 }
 
-// operands of a filled backward call, then its outputs, then the workspace (p.delta; `need` = the family's *_workspace_bytes)
-inline int attn_check_bwd_operands(const char* who, const AttnParams& p, int64_t wq, int64_t wkv, int dtype, size_t workspace_bytes,
-                                   size_t need) {
+// the six strided tensors of a filled backward call: q, k, v, then dq, dk, dv
+inline int attn_check_bwd_strides(const char* who, const AttnParams& p, int64_t wq, int64_t wkv, int dtype) {
   int rc;
   if ((rc = attn_stride_check(who, "q", p.q, p.q_stride, wq, dtype)) != GMLM_OK) return rc;
   if ((rc = attn_stride_check(who, "k", p.k, p.k_stride, wkv, dtype)) != GMLM_OK) return rc;
   if ((rc = attn_stride_check(who, "v", p.v, p.v_stride, wkv, dtype)) != GMLM_OK) return rc;
   if ((rc = attn_stride_check(who, "dq", p.dq, p.dq_stride, wq, dtype)) != GMLM_OK) return rc;
   if ((rc = attn_stride_check(who, "dk", p.dk, p.dk_stride, wkv, dtype)) != GMLM_OK) return rc;
-  if ((rc = attn_stride_check(who, "dv", p.dv, p.dv_stride, wkv, dtype)) != GMLM_OK) return rc;
+  return attn_stride_check(who, "dv", p.dv, p.dv_stride, wkv, dtype);
+}
+
+// operands of a filled backward call, then its outputs, then the workspace (p.delta; `need` = the family's *_workspace_bytes)
+inline int attn_check_bwd_operands(const char* who, const AttnParams& p, int64_t wq, int64_t wkv, int dtype, size_t workspace_bytes,
+                                   size_t need) {
+  const int rc = attn_check_bwd_strides(who, p, wq, wkv, dtype);
+  if (rc != GMLM_OK) return rc;
   GMLM_REQUIRE(p.out && p.dout && p.lse && aligned16(p.out) && aligned16(p.dout), "%s: null or misaligned out/dout/lse", who);
   GMLM_REQUIRE_WS(p.delta && workspace_bytes >= need, "%s: workspace too small", who);
+  return GMLM_OK;
+}
+
+// the same for the one-launch short-sequence backwards (gqa_short, d32_short), which read neither out nor a workspace
+inline int attn_check_short_bwd_operands(const char* who, const AttnParams& p, int64_t wq, int64_t wkv, int dtype) {
+  const int rc = attn_check_bwd_strides(who, p, wq, wkv, dtype);
+  if (rc != GMLM_OK) return rc;
+  GMLM_REQUIRE(p.dout && p.lse && aligned16(p.dout), "%s: null or misaligned dout/lse", who);
   return GMLM_OK;
 }
 

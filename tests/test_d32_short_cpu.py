@@ -81,6 +81,9 @@ def test_the_makefile_names_the_new_source_and_header():
     text = open(os.path.join(ROOT, "gmlm_amd", "csrc", "attn_d32_short.hip")).read()
     assert '#include "attn_short.hpp"' in text and "onehot_frag(int" not in text and "struct ShortMeta" not in text
     assert text.count("__global__") == 2 and "namespace d32s" in text
+    # the launcher, the tile height and the meta carving are the shared ones (attn_short_host.hpp, ShortMeta::carve)
+    assert "attn_short_host.hpp" in deps and "hipFuncAttributeMaxDynamicSharedMemorySize" not in text
+    assert not re.search(r"\btile_rows\b", text) and "meta_carve" not in text
 
 
 # ------------------------------------------------------------------------------------------------- entry-point refusals

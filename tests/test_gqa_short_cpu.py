@@ -77,6 +77,10 @@ def test_the_makefile_names_the_new_source_and_headers():
     for src in ("attn_short.hip", "attn_gqa_short.hip"):                    # the shared helpers live in the header alone
         text = open(os.path.join(ROOT, "gmlm_amd", "csrc", src)).read()
         assert '#include "attn_short.hpp"' in text and "onehot_frag(int" not in text and "struct ShortMeta" not in text
+    assert "attn_short_host.hpp" in deps
+    for src in ("attn_short.hip", "attn_gqa_short.hip", "attn_d32_short.hip"):   # one launcher, one tile height: attn_short_host.hpp
+        text = open(os.path.join(ROOT, "gmlm_amd", "csrc", src)).read()
+        assert "hipFuncAttributeMaxDynamicSharedMemorySize" not in text and not re.search(r"\btile_rows\b", text), src
 
 
 # ------------------------------------------------------------------------------------------------- entry-point refusals
