@@ -101,8 +101,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_dq_pipe_kernel(AttnParams
   const int64_t q_row = (int64_t)blockIdx.x * (NW * 32) + w * 32 + r;
   const bool q_ok = q_row < lq_;
   const bool wave_live = (int64_t)blockIdx.x * (NW * 32) + w * 32 < lq_;   // else: staging helper only
-  int64_t kvlen = lk_;
-  if (p.kv_len) { kvlen = p.kv_len[b]; if (kvlen > lk_) kvlen = lk_; if (kvlen < 0) kvlen = 0; }
+  const int64_t kvlen = clamp_kvlen(p, b, lk_);
   const int kvl = (int)(kvlen < (1 << 30) ? kvlen : (1 << 30));
   const int ntiles = (kvl + KT - 1) / KT;
   const T* kg = static_cast<const T*>(p.k) + kbase * p.k_stride + hd * D;
@@ -215,8 +214,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_dkv_pipe_kernel(AttnParam
   int64_t lq_, lk_, qbase, kbase, lse_base;
   seq_view(p, b, hd, lq_, lk_, qbase, kbase, lse_base);
   if ((int64_t)blockIdx.x * (NW * 32) >= lk_) return;                 // varlen: tile past this sequence (block-uniform)
-  int64_t kvlen = lk_;
-  if (p.kv_len) { kvlen = p.kv_len[b]; if (kvlen > lk_) kvlen = lk_; if (kvlen < 0) kvlen = 0; }
+  const int64_t kvlen = clamp_kvlen(p, b, lk_);
   const int64_t key = (int64_t)blockIdx.x * (NW * 32) + w * 32 + r;
   const bool key_in = key < lk_;            // row exists in memory
   const bool key_ok = key < kvlen;          // takes part in the softmax

@@ -47,6 +47,21 @@ __device__ __forceinline__ void seq_view(const AttnParams& p, int64_t b, int64_t
   }
 }
 
+// kv_len of sequence b clamped into [0, lk_]; without a kv_len array every key counts
+__device__ __forceinline__ int64_t clamp_kvlen(const AttnParams& p, int64_t b, int64_t lk_) {
+  int64_t kvlen = lk_;
+  if (p.kv_len) { kvlen = p.kv_len[b]; if (kvlen > lk_) kvlen = lk_; if (kvlen < 0) kvlen = 0; }
+  return kvlen;
+}
+
+// work item of a 1-D grid -> (tile, batch or sequence, head); tiles are outermost
+struct Item { int64_t tile, b, hd; };
+__device__ __forceinline__ Item decode(const AttnParams& p) {
+  const int64_t pairs = p.b * p.h, item = blockIdx.x;
+  const int64_t bh = item % pairs;
+  return {item / pairs, bh / p.h, bh % p.h};
+}
+
 template <typename T> struct Pad;
 template <> struct Pad<bf16_t> { static constexpr int v = 8; };
 template <> struct Pad<float> { static constexpr int v = 4; };

@@ -25,17 +25,7 @@ struct Params {
   int64_t dout_stride;     // row stride of dO / O (= h * 128)
 };
 
-template <typename T> struct Cfg;
-template <> struct Cfg<bf16_t> { static constexpr int KT = 64, QT = 32; static constexpr bool DBUF = true; };
-template <> struct Cfg<float> { static constexpr int KT = 32, QT = 32; static constexpr bool DBUF = false; };
-
-// work item of the 1-D grid -> (tile, batch, head); tiles are outermost
-struct Item { int64_t tile, b, hd; };
-__device__ __forceinline__ Item decode(const AttnParams& p) {
-  const int64_t pairs = p.b * p.h, item = blockIdx.x;
-  const int64_t bh = item % pairs;
-  return {item / pairs, bh / p.h, bh % p.h};
-}
+// Cfg<T> (tile sizes) is attn_stream.hpp's, decode() (1-D grid -> tile, batch, head) attn_common.hpp's
 
 // forward: workgroup = 128 query rows of one (batch, head), loop over key tiles
 template <typename T, bool DROP>
@@ -73,8 +63,7 @@ __global__ __launch_bounds__(NT) void dq_kernel(Params x) {
   const int64_t q_row = q_tile0 + w * 32 + r;
   const bool q_ok = q_row < lq_;
   const bool wave_live = q_tile0 + w * 32 < lq_;
-  int64_t kvlen = lk_;
-  if (p.kv_len) { kvlen = p.kv_len[b]; if (kvlen > lk_) kvlen = lk_; if (kvlen < 0) kvlen = 0; }
+  const int64_t kvlen = clamp_kvlen(p, b, lk_);
   const int64_t qr = q_ok ? q_row : 0;
   const T* kg = static_cast<const T*>(p.k) + kbase * p.k_stride + hd * D;
   const T* vg = static_cast<const T*>(p.v) + kbase * p.v_stride + hd * D;
@@ -207,7 +196,7 @@ static int setup(const char* who, Params& x, const void* q, const void* k, const
                  uint64_t seed, const uint64_t* seed_dev, const void* out_lo, int dtype) {
   int rc = attn_check_shape(who, b >= 0 && h > 0 && lq >= 0 && lk >= 0, d == 128, d, "this entry point takes 128", dtype, out_lo);
   if (rc != GMLM_OK) return rc;
-  if ((rc = attn_check_rates(who, dropout_p, true, scale)) != GMLM_OK) return rc;
+  if ((rc = attn_check_rates(who, dropout_p, nullptr, scale)) != GMLM_OK) return rc;
   const int64_t rows = lq > lk ? lq : lk;
   GMLM_REQUIRE(cdiv(rows, BQ) * b * h < ((int64_t)1 << 31), "%s: too many work items", who);
   x = Params{};

@@ -30,14 +30,6 @@ template <typename T> struct Cfg;
 template <> struct Cfg<bf16_t> { static constexpr int KT = 64, QT = 64; static constexpr bool DBUF = true; };
 template <> struct Cfg<float> { static constexpr int KT = 32, QT = 32; static constexpr bool DBUF = false; };
 
-// work item of the 1-D grid -> (tile, batch or sequence, head); tiles are outermost
-struct Item { int64_t tile, b, hd; };
-__device__ __forceinline__ Item decode(const AttnParams& p) {
-  const int64_t pairs = p.b * p.h, item = blockIdx.x;
-  const int64_t bh = item % pairs;
-  return {item / pairs, bh / p.h, bh % p.h};
-}
-
 // forward: workgroup = NW * 32 query rows of one (sequence, head), loop over key tiles
 template <typename T, int NW, bool DROP>
 __global__ __launch_bounds__(NW * 64) void fwd_kernel(AttnParams p) {
@@ -78,7 +70,7 @@ static int setup(const char* who, AttnParams& p, int& nw, const void* q, const v
   int rc = attn_check_shape(who, b >= 0 && h > 0 && lq >= 0 && lk >= 0, d == 32, d, "this entry point takes 32", dtype, out_lo);
   if (rc != GMLM_OK) return rc;
   GMLM_REQUIRE(!cu_seqlens || (lq == lk && max_len > 0 && !kv_len), "%s: packed mode needs lq == lk = total rows, max_len > 0, kv_len NULL", who);
-  if ((rc = attn_check_rates(who, dropout_p, true, scale)) != GMLM_OK) return rc;
+  if ((rc = attn_check_rates(who, dropout_p, nullptr, scale)) != GMLM_OK) return rc;
   const int64_t rows = cu_seqlens ? max_len : (lq > lk ? lq : lk);
   nw = pick_waves(rows);
   // each factor and each partial product is bounded before the next multiply: no int64 overflow on the way to the answer

@@ -29,17 +29,7 @@ struct DisParams {
   float* dpt;            // [h, rows, w] gradient of t.pt
 };
 
-template <typename T> struct Cfg;
-template <> struct Cfg<bf16_t> { static constexpr int KT = 64, QT = 32; static constexpr bool DBUF = true; };
-template <> struct Cfg<float> { static constexpr int KT = 32, QT = 32; static constexpr bool DBUF = false; };
-
-// work item of the 1-D grid -> (tile, batch or sequence, head); tiles are outermost
-struct Item { int64_t tile, b, hd; };
-__device__ __forceinline__ Item decode(const AttnParams& p) {
-  const int64_t pairs = p.b * p.h, item = blockIdx.x;
-  const int64_t bh = item % pairs;
-  return {item / pairs, bh / p.h, bh % p.h};
-}
+// Cfg<T> (tile sizes) is attn_stream.hpp's, decode() (1-D grid -> tile, sequence, head) attn_common.hpp's
 
 template <typename T, bool DROP>
 __global__ __launch_bounds__(NT) void fwd_kernel(DisParams x) {
@@ -96,8 +86,7 @@ __device__ __forceinline__ void dtab_body(const DisParams& x, int64_t tile, int6
   int64_t lq_, lk_, base, kbase, lse_base;
   seq_view(p, b, hd, lq_, lk_, base, kbase, lse_base);      // lq == lk: base == kbase
   if (tile * BQ >= lq_) return;                             // varlen: tile past this sequence (block-uniform): no rows to write
-  int64_t kvlen = lk_;
-  if (p.kv_len) { kvlen = p.kv_len[b]; if (kvlen > lk_) kvlen = lk_; if (kvlen < 0) kvlen = 0; }
+  const int64_t kvlen = clamp_kvlen(p, b, lk_);
   const int rows = (int)lq_;                                // < 2^30 (host check)
   const int x_wave0 = (int)(tile * BQ) + w * 32, xi = x_wave0 + r;
   const bool x_in = xi < rows;                              // the row exists in memory
@@ -262,7 +251,7 @@ static int setup(const char* who, DisParams& x, const void* q, const void* k, co
                (long)(rows > 1 ? rows : 1), GMLM_DISENT_MAX_LEN);
   GMLM_REQUIRE(tab_w >= 1 && tab_w <= 2 * col_m - 1, "%s: tab_w %ld must be in [1, %ld] (no more columns than relative positions)", who,
                (long)tab_w, (long)(2 * col_m - 1));
-  if ((rc = attn_check_rates(who, dropout_p, true, scale)) != GMLM_OK) return rc;
+  if ((rc = attn_check_rates(who, dropout_p, nullptr, scale)) != GMLM_OK) return rc;
   // each factor and each partial product is bounded before the next multiply: no int64 overflow on the way to the answer
   const int64_t tiles = cdiv(rows, (int64_t)BQ), lim = (int64_t)1 << 31;
   GMLM_REQUIRE(lq < ((int64_t)1 << 30) && b < lim && h < lim && b * h < lim && tiles * (b * h) < lim, "%s: too many work items", who);

@@ -55,8 +55,7 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd_pipe_kernel(AttnParams p) {
   const bool q_ok = q_row < lq_;
   // a wave whose 32 queries all lie past the sequence (short packed sequences) only helps staging K/V
   const bool wave_live = (int64_t)qb * (NW * 32) + w * 32 < lq_;
-  int64_t kvlen64 = lk_;
-  if (p.kv_len) { kvlen64 = p.kv_len[b]; if (kvlen64 > lk_) kvlen64 = lk_; if (kvlen64 < 0) kvlen64 = 0; }
+  const int64_t kvlen64 = clamp_kvlen(p, b, lk_);
   const int kvlen = (int)(kvlen64 < (1 << 30) ? kvlen64 : (1 << 30));
   const T* qg = static_cast<const T*>(p.q) + (qbase + (q_ok ? q_row : 0)) * p.q_stride + hd * D;
   const T* kg = static_cast<const T*>(p.k) + kbase * p.k_stride + hd * D;

@@ -6,15 +6,12 @@
 //    half, and writes the same 16 bytes back: in place without a hazard.  fp32 arithmetic, one rounding on store; the table is
 //    built on the host.  1-D grid capped at kRopeMaxBlocks, a block-uniform stride loop over groups of 256 / LPR head rows.
 //    INV: the backward = the inverse rotation, so it needs no saved input and no workspace.
-//  * causal attention with grouped KV heads at head dim 64 (gmlm_attention_causal_d64_*, padded and packed): the d = 128
-//    family of attn_causal.hip at D = 64.  Forward and dQ are the streaming bodies of attn_stream.hpp with CAUSAL = GQA = true,
-//    delta is the shared delta body, dK/dV is causal_dkv_body (attn_causal_dkv.hpp): the same text as causal128::dkv_kernel.
-//    Tiling of causal128 (4 waves, 128 query rows; bf16: 64-key tiles double-buffered, fp32: 32-key tiles in one buffer): at
-//    D = 64 the tiles and the accumulators are half as large, so its register and LDS budget holds with room to spare
-//    (DESIGN.md section 4 "Llama, Qwen2 and Mistral encoders").
-#include "attn_stream.hpp"
-#include "attn_causal_dkv.hpp"
-#include "attn_host.hpp"
+//  * causal attention with grouped KV heads at head dim 64 (gmlm_attention_causal_d64_*, padded and packed): one of the three
+//    grouped families of attn_grouped.hpp (kernels described there; checks, launches and entry-point bodies held there),
+//    CAUSAL = true at D = 64; here the kernels under their names, the family, the exports.
+//    At D = 64 the tiles and the accumulators are half as large as at 128, so the register and LDS budget holds with room to
+//    spare (DESIGN.md section 4 "Llama, Qwen2 and Mistral encoders").
+#include "attn_grouped.hpp"
 #include "row_kernels.hpp"
 #include "../../include/gmlm_hip_gqa.h"
 
@@ -81,26 +78,9 @@ static int rope_heads(const char* who, void* qkv, int64_t stride, const float* c
   return GMLM_OK;
 }
 
-// ---- causal GQA attention at head dim 64 -------------------------------------------------------------
-constexpr int D = 64, NW = 4, NT = NW * 64, BQ = NW * 32;
-
-struct Params {
-  AttnParams a;            // a.h = query heads; lse / delta are [b, hq, l]; a.lq == a.lk
-  int64_t dout_stride;     // row stride of dO / O (= hq * 64)
-  int32_t group;           // query heads per KV head (hq / hkv)
-};
-
-template <typename T> struct Cfg;
-template <> struct Cfg<bf16_t> { static constexpr int KT = 64, QT = 32; static constexpr bool DBUF = true; };
-template <> struct Cfg<float> { static constexpr int KT = 32, QT = 32; static constexpr bool DBUF = false; };
-
-// work item of the 1-D grid -> (tile, batch, query head); tiles are outermost
-struct Item { int64_t tile, b, hd; };
-__device__ __forceinline__ Item decode(const AttnParams& p) {
-  const int64_t pairs = p.b * p.h, item = blockIdx.x;
-  const int64_t bh = item % pairs;
-  return {item / pairs, bh / p.h, bh % p.h};
-}
+// ---- causal GQA attention at head dim 64 (attn_grouped.hpp) ------------------------------------------
+using grouped::Params, grouped::NW, grouped::NT;
+constexpr int D = 64;
 
 template <typename T>
 __global__ __launch_bounds__(NT) void causal64_fwd_kernel(Params x) {
@@ -125,64 +105,13 @@ __global__ __launch_bounds__(NT) void causal64_dq_kernel(Params x) {
 template <typename T>
 __global__ __launch_bounds__(NT) void causal64_dkv_kernel(Params x) {
   const CausalKeyTile it = causal_key_tile(x.a, x.group);
-  int64_t kvlen = it.l;                                      // kv_len clamped into [0, l], as the streaming bodies do
-  if (x.a.kv_len) { kvlen = x.a.kv_len[it.b]; if (kvlen > it.l) kvlen = it.l; if (kvlen < 0) kvlen = 0; }
-  causal_dkv_body<T, D, NW, Cfg<T>::QT, Cfg<T>::DBUF>(x.a, x.dout_stride, x.group, it, kvlen);
+  causal_dkv_body<T, D, NW, Cfg<T>::QT, Cfg<T>::DBUF, true>(x.a, x.dout_stride, x.group, it, clamp_kvlen(x.a, it.b, it.l));
 }
 
-// the checks of attn_host.hpp up to the empty-problem return, in the order of the d = 128 family; fills the launch parameters
-static int setup(const char* who, Params& x, const void* q, const void* k, const void* v, const int32_t* kv_len, int64_t b,
-                 int64_t hq, int64_t hkv, int64_t lq, int64_t lk, int64_t d, int64_t q_stride, int64_t k_stride, int64_t v_stride,
-                 float scale, float dropout_p, const void* out_lo, int dtype, bool sizes_ok = true) {
-  int rc = attn_check_shape(who, sizes_ok && b >= 0 && hq > 0 && hkv > 0 && lq >= 0 && lk >= 0, d == 64, d, "this entry point takes 64",
-                            dtype, out_lo);
-  if (rc != GMLM_OK) return rc;
-  GMLM_REQUIRE(lq == lk, "%s: causal self-attention needs lq == lk (got %ld and %ld)", who, (long)lq, (long)lk);
-  GMLM_REQUIRE(hq % hkv == 0, "%s: %ld query heads are not a multiple of %ld KV heads", who, (long)hq, (long)hkv);
-  if ((rc = attn_check_rates(who, dropout_p, false, scale)) != GMLM_OK) return rc;
-  GMLM_REQUIRE(lq < ((int64_t)1 << 30) && cdiv(lq, BQ) * b * hq < ((int64_t)1 << 31), "%s: too many work items", who);
-  x = Params{};
-  attn_fill(x.a, q, k, v, kv_len, b, hq, lq, lk, q_stride, k_stride, v_stride, scale, 0.f, 0, nullptr);
-  x.dout_stride = hq * D;
-  x.group = (int32_t)(hq / hkv);
-  return GMLM_OK;
-}
-
-// packed layout: the same kernels with AttnParams::cu set: b = seqs, lq = lk = rows (lse / delta [hq, rows])
-static int setup_varlen(const char* who, Params& x, const void* q, const void* k, const void* v, const int32_t* cu, int64_t seqs,
-                        int64_t max_len, int64_t rows, int64_t hq, int64_t hkv, int64_t d, int64_t q_stride, int64_t k_stride,
-                        int64_t v_stride, float scale, float dropout_p, const void* out_lo, int dtype) {
-  GMLM_REQUIRE(cu, "%s: null cu_seqlens", who);
-  GMLM_REQUIRE(max_len > 0, "%s: max_len %ld must be positive", who, (long)max_len);
-  GMLM_REQUIRE(seqs >= 0 && rows >= 0 && rows < ((int64_t)1 << 30), "%s: %ld packed rows (must be >= 0 and < 2^30)", who, (long)rows);
-  int rc = setup(who, x, q, k, v, nullptr, 0, hq, hkv, 0, 0, d, q_stride, k_stride, v_stride, scale, dropout_p, out_lo, dtype,
-                 max_len < ((int64_t)1 << 30) && seqs < ((int64_t)1 << 30));
-  if (rc != GMLM_OK) return rc;
-  GMLM_REQUIRE(cdiv(max_len, BQ) * seqs * hq < ((int64_t)1 << 31), "%s: too many work items", who);
-  x.a.b = seqs; x.a.lq = x.a.lk = rows; x.a.cu = cu;
-  return GMLM_OK;
-}
-
-#define GMLM_GQA_LAUNCH(KERNEL, grid, st, prm)                            \
-  do {                                                                    \
-    if (dtype == GMLM_BF16) KERNEL<bf16_t><<<grid, NT, 0, st>>>(prm);     \
-    else KERNEL<float><<<grid, NT, 0, st>>>(prm);                         \
-  } while (0)
-
-// the three backward launches; tiles = query (= key) tiles of 128 per sequence, seqs = sequences, drows / dlq = the delta view
-static int launch_bwd(Params& x, int64_t tiles, int64_t seqs, int64_t hq, int64_t hkv, int64_t drows, int64_t dlq, int dtype,
-                      hipStream_t st) {
-  AttnParams& p = x.a;
-  GMLM_ATTN_DELTA_LAUNCH(causal64_delta_kernel, p, drows, dtype == GMLM_BF16 ? 8 : 16, st, dlq, hq);   // attn_delta_body: 64 / V lanes per row
-  GMLM_LAUNCH_CHECK();
-  const dim3 gq((unsigned)(tiles * seqs * hq));
-  GMLM_GQA_LAUNCH(causal64_dq_kernel, gq, st, x);
-  GMLM_LAUNCH_CHECK();
-  const dim3 gk((unsigned)(tiles * seqs * hkv));
-  GMLM_GQA_LAUNCH(causal64_dkv_kernel, gk, st, x);
-  GMLM_LAUNCH_CHECK();
-  return GMLM_OK;
-}
+static const grouped::Family kFamily = {
+    "this entry point takes 64", "causal self-attention", "causal",
+    {{causal64_fwd_kernel<bf16_t>, causal64_delta_kernel<bf16_t>, causal64_dq_kernel<bf16_t>, causal64_dkv_kernel<bf16_t>}, {}},
+    {{causal64_fwd_kernel<float>, causal64_delta_kernel<float>, causal64_dq_kernel<float>, causal64_dkv_kernel<float>}, {}}};
 
 }  // namespace gqa
 }  // namespace gmlm
@@ -204,18 +133,8 @@ extern "C" int gmlm_attention_causal_d64_fwd(const void* q, const void* k, const
                                              int64_t hkv, int64_t lq, int64_t lk, int64_t d, int64_t q_stride, int64_t k_stride,
                                              int64_t v_stride, float scale, float dropout_p, void* out, void* out_lo, float* lse,
                                              int dtype, gmlm_stream_t stream) {
-  static const char* who = "attention_causal_d64_fwd";
-  Params x;
-  int rc = setup(who, x, q, k, v, kv_len, b, hq, hkv, lq, lk, d, q_stride, k_stride, v_stride, scale, dropout_p, out_lo, dtype);
-  if (rc != GMLM_OK) return rc;
-  if (b == 0 || lq == 0) return GMLM_OK;
-  x.a.o_w = out; x.a.o_lo_w = out_lo; x.a.lse_w = lse;
-  if ((rc = attn_check_fwd_operands(who, x.a, hq * D, hkv * D, dtype)) != GMLM_OK) return rc;
-  hipStream_t st = as_stream(stream);
-  const dim3 grid((unsigned)(cdiv(lq, BQ) * b * hq));
-  GMLM_GQA_LAUNCH(causal64_fwd_kernel, grid, st, x);
-  GMLM_LAUNCH_CHECK();
-  return GMLM_OK;
+  return grouped::fwd(kFamily, "attention_causal_d64_fwd", grouped::padded(kv_len, b, lq, lk), q, k, v, hq, hkv, d, q_stride, k_stride,
+                      v_stride, scale, dropout_p, out, out_lo, lse, dtype, stream);
 }
 
 extern "C" size_t gmlm_attention_causal_d64_workspace_bytes(int64_t b, int64_t hq, int64_t lq) { return attn_delta_bytes(b, hq, lq); }
@@ -226,14 +145,9 @@ extern "C" int gmlm_attention_causal_d64_bwd(const void* q, const void* k, const
                                              int64_t v_stride, float scale, float dropout_p, void* dq, void* dk, void* dv,
                                              int64_t dq_stride, int64_t dk_stride, int64_t dv_stride, int dtype, void* workspace,
                                              size_t workspace_bytes, gmlm_stream_t stream) {
-  static const char* who = "attention_causal_d64_bwd";
-  Params x;
-  int rc = setup(who, x, q, k, v, kv_len, b, hq, hkv, lq, lk, d, q_stride, k_stride, v_stride, scale, dropout_p, out_lo, dtype);
-  if (rc != GMLM_OK) return rc;
-  if (b == 0 || lq == 0) return GMLM_OK;
-  attn_fill_bwd(x.a, out, out_lo, dout, lse, dq, dk, dv, dq_stride, dk_stride, dv_stride, workspace);
-  if ((rc = attn_check_bwd_operands(who, x.a, hq * D, hkv * D, dtype, workspace_bytes, attn_delta_bytes(b, hq, lq))) != GMLM_OK) return rc;
-  return launch_bwd(x, cdiv(lq, BQ), b, hq, hkv, b * lq * hq, lq, dtype, as_stream(stream));
+  return grouped::bwd(kFamily, "attention_causal_d64_bwd", grouped::padded(kv_len, b, lq, lk), q, k, v, out, out_lo, dout, lse, hq, hkv,
+                      d, q_stride, k_stride, v_stride, scale, dropout_p, dq, dk, dv, dq_stride, dk_stride, dv_stride, dtype, workspace,
+                      workspace_bytes, stream);
 }
 
 extern "C" int gmlm_attention_causal_d64_varlen_fwd(const void* q, const void* k, const void* v, const int32_t* cu_seqlens,
@@ -241,19 +155,8 @@ extern "C" int gmlm_attention_causal_d64_varlen_fwd(const void* q, const void* k
                                                     int64_t d, int64_t q_stride, int64_t k_stride, int64_t v_stride, float scale,
                                                     float dropout_p, void* out, void* out_lo, float* lse, int dtype,
                                                     gmlm_stream_t stream) {
-  static const char* who = "attention_causal_d64_varlen_fwd";
-  Params x;
-  int rc = setup_varlen(who, x, q, k, v, cu_seqlens, num_seqs, max_len, total_rows, hq, hkv, d, q_stride, k_stride, v_stride, scale,
-                        dropout_p, out_lo, dtype);
-  if (rc != GMLM_OK) return rc;
-  if (num_seqs == 0 || total_rows == 0) return GMLM_OK;
-  x.a.o_w = out; x.a.o_lo_w = out_lo; x.a.lse_w = lse;
-  if ((rc = attn_check_fwd_operands(who, x.a, hq * D, hkv * D, dtype)) != GMLM_OK) return rc;
-  hipStream_t st = as_stream(stream);
-  const dim3 grid((unsigned)(cdiv(max_len, BQ) * num_seqs * hq));
-  GMLM_GQA_LAUNCH(causal64_fwd_kernel, grid, st, x);
-  GMLM_LAUNCH_CHECK();
-  return GMLM_OK;
+  return grouped::fwd(kFamily, "attention_causal_d64_varlen_fwd", grouped::packed(cu_seqlens, num_seqs, max_len, total_rows), q, k, v, hq,
+                      hkv, d, q_stride, k_stride, v_stride, scale, dropout_p, out, out_lo, lse, dtype, stream);
 }
 
 extern "C" size_t gmlm_attention_causal_d64_varlen_workspace_bytes(int64_t total_rows, int64_t hq) {
@@ -267,14 +170,7 @@ extern "C" int gmlm_attention_causal_d64_varlen_bwd(const void* q, const void* k
                                                     float dropout_p, void* dq, void* dk, void* dv, int64_t dq_stride,
                                                     int64_t dk_stride, int64_t dv_stride, int dtype, void* workspace,
                                                     size_t workspace_bytes, gmlm_stream_t stream) {
-  static const char* who = "attention_causal_d64_varlen_bwd";
-  Params x;
-  int rc = setup_varlen(who, x, q, k, v, cu_seqlens, num_seqs, max_len, total_rows, hq, hkv, d, q_stride, k_stride, v_stride, scale,
-                        dropout_p, out_lo, dtype);
-  if (rc != GMLM_OK) return rc;
-  if (num_seqs == 0 || total_rows == 0) return GMLM_OK;
-  attn_fill_bwd(x.a, out, out_lo, dout, lse, dq, dk, dv, dq_stride, dk_stride, dv_stride, workspace);
-  if ((rc = attn_check_bwd_operands(who, x.a, hq * D, hkv * D, dtype, workspace_bytes, attn_delta_bytes(1, hq, total_rows))) != GMLM_OK)
-    return rc;
-  return launch_bwd(x, cdiv(max_len, BQ), num_seqs, hq, hkv, total_rows * hq, total_rows, dtype, as_stream(stream));
+  return grouped::bwd(kFamily, "attention_causal_d64_varlen_bwd", grouped::packed(cu_seqlens, num_seqs, max_len, total_rows), q, k, v, out,
+                      out_lo, dout, lse, hq, hkv, d, q_stride, k_stride, v_stride, scale, dropout_p, dq, dk, dv, dq_stride, dk_stride,
+                      dv_stride, dtype, workspace, workspace_bytes, stream);
 }

@@ -25,10 +25,11 @@ inline int attn_check_shape(const char* who, bool sizes_ok, bool d_ok, int64_t d
   return GMLM_OK;
 }
 
-// checks 6-7.  has_dropout = false: the causal kernels, which take dropout_p = 0 only
-inline int attn_check_rates(const char* who, float dropout_p, bool has_dropout, float scale) {
-  if (has_dropout) GMLM_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "%s: dropout_p must be in [0,1)", who);
-  else GMLM_REQUIRE(dropout_p == 0.f, "%s: attention-probability dropout is not implemented for the causal kernels (dropout_p must be 0)", who);
+// checks 6-7.  no_dropout: NULL for a family with dropout; else how the refusal names its kernels ("causal", "grouped"), which
+// take dropout_p = 0 only
+inline int attn_check_rates(const char* who, float dropout_p, const char* no_dropout, float scale) {
+  if (!no_dropout) GMLM_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "%s: dropout_p must be in [0,1)", who);
+  else GMLM_REQUIRE(dropout_p == 0.f, "%s: attention-probability dropout is not implemented for the %s kernels (dropout_p must be 0)", who, no_dropout);
   GMLM_REQUIRE(scale > 0.f, "%s: scale must be positive", who);
   return GMLM_OK;
 }

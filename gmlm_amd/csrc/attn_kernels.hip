@@ -60,7 +60,7 @@ static int attn_check(const char* who, int64_t b, int64_t h, int64_t lq, int64_t
   if (rc != GMLM_OK) return rc;
   GMLM_REQUIRE(!cu_seqlens || (lq == lk && max_len > 0 && !kv_len), "%s: packed mode needs lq == lk = total rows, max_len > 0, kv_len NULL", who);
   GMLM_REQUIRE(!seq_groups || (cu_seqlens && num_groups > 0 && num_groups <= b), "%s: seq_groups needs packed mode and 0 < num_groups <= b", who);
-  if ((rc = attn_check_rates(who, dropout_p, true, scale)) != GMLM_OK) return rc;
+  if ((rc = attn_check_rates(who, dropout_p, nullptr, scale)) != GMLM_OK) return rc;
   GMLM_REQUIRE(b * h <= 65535, "%s: batch*heads %ld > 65535", who, (long)(b * h));   // grid.y of the two-dimensional launches
   return GMLM_OK;
 }

@@ -30,17 +30,7 @@ struct RelParams {
   int m;
 };
 
-template <typename T> struct Cfg;
-template <> struct Cfg<bf16_t> { static constexpr int KT = 64, QT = 32; static constexpr bool DBUF = true; };
-template <> struct Cfg<float> { static constexpr int KT = 32, QT = 32; static constexpr bool DBUF = false; };
-
-// work item of the 1-D grid -> (tile, batch or sequence, head); tiles are outermost
-struct Item { int64_t tile, b, hd; };
-__device__ __forceinline__ Item decode(const AttnParams& p) {
-  const int64_t pairs = p.b * p.h, item = blockIdx.x;
-  const int64_t bh = item % pairs;
-  return {item / pairs, bh / p.h, bh % p.h};
-}
+// Cfg<T> (tile sizes) is attn_stream.hpp's, decode() (1-D grid -> tile, sequence, head) attn_common.hpp's
 
 // forward: workgroup = 128 query rows of one (sequence, head), loop over key tiles
 template <typename T, bool DROP>
@@ -100,8 +90,7 @@ __device__ __forceinline__ void dbias_body(const RelParams& x, int64_t tile, int
     const int64_t q_row = tile * BQ + w * 32 + r;
     const bool q_ok = q_row < lq_;
     const bool wave_live = tile * BQ + w * 32 < lq_;        // else: staging helper only
-    int64_t kvlen = lk_;
-    if (p.kv_len) { kvlen = p.kv_len[b]; if (kvlen > lk_) kvlen = lk_; if (kvlen < 0) kvlen = 0; }
+    const int64_t kvlen = clamp_kvlen(p, b, lk_);
     const int64_t qr = q_ok ? q_row : 0;
     const T* kg = static_cast<const T*>(p.k) + kbase * p.k_stride + hd * D;
     const T* vg = static_cast<const T*>(p.v) + kbase * p.v_stride + hd * D;
@@ -251,7 +240,7 @@ static int setup(const char* who, RelParams& x, const void* q, const void* k, co
   GMLM_REQUIRE(rel_m >= rows && rel_m >= 1 && rel_m <= GMLM_RELBIAS_MAX_LEN,
                "%s: rel_m %ld must be in [%ld, %d] (the longest sequence of the call up to GMLM_RELBIAS_MAX_LEN)", who, (long)rel_m,
                (long)(rows > 1 ? rows : 1), GMLM_RELBIAS_MAX_LEN);
-  if ((rc = attn_check_rates(who, dropout_p, true, scale)) != GMLM_OK) return rc;
+  if ((rc = attn_check_rates(who, dropout_p, nullptr, scale)) != GMLM_OK) return rc;
   // each factor and each partial product is bounded before the next multiply: no int64 overflow on the way to the answer
   const int64_t tiles = cdiv(rows, (int64_t)BQ), lim = (int64_t)1 << 31;
   GMLM_REQUIRE(lq < ((int64_t)1 << 30) && b < lim && h < lim && b * h < lim && tiles * (b * h) < lim, "%s: too many work items", who);

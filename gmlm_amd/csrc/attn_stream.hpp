@@ -9,6 +9,12 @@
 
 namespace gmlm {
 
+// Tiling of the 4-wave families at head dim 64 and 128 (128 query rows per workgroup): bf16 streams 64-row K / V tiles double-
+// buffered, fp32 32-row tiles in one buffer; dK/dV stages 32 query rows at a time.  attn_d32.hip has its own (QT = 64).
+template <typename T> struct Cfg;
+template <> struct Cfg<bf16_t> { static constexpr int KT = 64, QT = 32; static constexpr bool DBUF = true; };
+template <> struct Cfg<float> { static constexpr int KT = 32, QT = 32; static constexpr bool DBUF = false; };
+
 // Operands of the DISENT score mode (disentangled attention, attn_disent.hip): two fp32 tables [h, rows, w] with one row of `w`
 // columns per (head, token), rows = all token rows of the call in memory order (what a GEMM batched over the heads writes), and
 // the column table col[2m - 1], col[m - 1 + (i - j)] = the column that query i and key j of one sequence read in BOTH tables.
@@ -79,8 +85,7 @@ __device__ __forceinline__ void attn_fwd_body(const AttnParams& p, int64_t tile,
   const bool q_ok = q_row < lq_;
   // a wave whose 32 queries all lie past the sequence (short packed sequences) only helps staging K/V
   const bool wave_live = tile * (NW * 32) + w * 32 < lq_;
-  int64_t kvlen = lk_;
-  if (p.kv_len) { kvlen = p.kv_len[b]; if (kvlen > lk_) kvlen = lk_; if (kvlen < 0) kvlen = 0; }
+  const int64_t kvlen = clamp_kvlen(p, b, lk_);
   const T* qg = static_cast<const T*>(p.q) + (qbase + (q_ok ? q_row : 0)) * p.q_stride + hd * D;
   const int64_t khd = GQA ? kvh : hd;
   const T* kg = static_cast<const T*>(p.k) + kbase * p.k_stride + khd * D;
@@ -307,8 +312,7 @@ __device__ __forceinline__ void attn_dq_body(const AttnParams& p, int64_t tile, 
   const int64_t q_row = tile * (NW * 32) + w * 32 + r;
   const bool q_ok = q_row < lq_;
   const bool wave_live = tile * (NW * 32) + w * 32 < lq_;   // else: staging helper only
-  int64_t kvlen = lk_;
-  if (p.kv_len) { kvlen = p.kv_len[b]; if (kvlen > lk_) kvlen = lk_; if (kvlen < 0) kvlen = 0; }
+  const int64_t kvlen = clamp_kvlen(p, b, lk_);
   const int64_t qr = q_ok ? q_row : 0;
   const int64_t khd = GQA ? kvh : hd;
   const T* kg = static_cast<const T*>(p.k) + kbase * p.k_stride + khd * D;
@@ -515,8 +519,7 @@ __device__ __forceinline__ void attn_dkv_body(const AttnParams& p, int64_t tile,
   int64_t lq_, lk_, qbase, kbase, lse_base;
   seq_view(p, b, hd, lq_, lk_, qbase, kbase, lse_base);
   if (tile * (NW * 32) >= (true ? lk_ : lq_)) return;   // varlen: tile past this sequence (block-uniform)
-  int64_t kvlen = lk_;
-  if (p.kv_len) { kvlen = p.kv_len[b]; if (kvlen > lk_) kvlen = lk_; if (kvlen < 0) kvlen = 0; }
+  const int64_t kvlen = clamp_kvlen(p, b, lk_);
   const int64_t key = tile * (NW * 32) + w * 32 + r;
   const int64_t k_tile0 = tile * (NW * 32), k_wave0 = k_tile0 + w * 32;
   const int ki = (int)(key < (1 << 30) ? key : (1 << 30));

@@ -40,13 +40,6 @@ template <typename T, int D> struct Lds {
   static_assert(BYTES <= 160 * 1024, "LDS of one workgroup exceeds a CU");
 };
 
-struct Item { int64_t tile, b, hd; };
-__device__ __forceinline__ Item decode(const AttnParams& p) {
-  const int64_t pairs = p.b * p.h, item = blockIdx.x;
-  const int64_t bh = item % pairs;
-  return {item / pairs, bh / p.h, bh % p.h};
-}
-
 // s <- ((s_w0 + s_w1) + s_w2) + s_w3, the same expression in every wave.  Two barriers: partials visible / area free again.
 __device__ __forceinline__ void exchange(float* xs, f32x16& s, int w, int lane) {
 #pragma unroll
@@ -74,8 +67,7 @@ __global__ __launch_bounds__(NT) void fwd_kernel(Params x) {
   seq_view(p, b, hd, lq_, lk_, qbase, kbase, lse_base);
   const int64_t q_row = it.tile * R + r;
   const bool q_ok = q_row < lq_;
-  int64_t kvlen = lk_;
-  if (p.kv_len) { kvlen = p.kv_len[b]; if (kvlen > lk_) kvlen = lk_; if (kvlen < 0) kvlen = 0; }
+  const int64_t kvlen = clamp_kvlen(p, b, lk_);
   const T* kg = static_cast<const T*>(p.k) + kbase * p.k_stride + hd * D;
   const T* vg = static_cast<const T*>(p.v) + kbase * p.v_stride + hd * D;
   RowFrag<T, DS> qf;
@@ -212,8 +204,7 @@ __global__ __launch_bounds__(NT) void dq_kernel(Params x) {
   seq_view(p, b, hd, lq_, lk_, qbase, kbase, lse_base);
   const int64_t q_row = it.tile * R + r;
   const bool q_ok = q_row < lq_;
-  int64_t kvlen = lk_;
-  if (p.kv_len) { kvlen = p.kv_len[b]; if (kvlen > lk_) kvlen = lk_; if (kvlen < 0) kvlen = 0; }
+  const int64_t kvlen = clamp_kvlen(p, b, lk_);
   const int64_t qr = q_ok ? q_row : 0;
   const T* kg = static_cast<const T*>(p.k) + kbase * p.k_stride + hd * D;
   const T* vg = static_cast<const T*>(p.v) + kbase * p.v_stride + hd * D;
@@ -284,8 +275,7 @@ __global__ __launch_bounds__(NT) void dkv_kernel(Params x) {
   const int64_t b = it.b, hd = it.hd;
   int64_t lq_, lk_, qbase, kbase, lse_base;
   seq_view(p, b, hd, lq_, lk_, qbase, kbase, lse_base);
-  int64_t kvlen = lk_;
-  if (p.kv_len) { kvlen = p.kv_len[b]; if (kvlen > lk_) kvlen = lk_; if (kvlen < 0) kvlen = 0; }
+  const int64_t kvlen = clamp_kvlen(p, b, lk_);
   const int64_t key = it.tile * R + r;
   const bool key_in = key < lk_;           // row exists in memory
   const bool key_ok = key < kvlen;          // takes part in the softmax
@@ -367,7 +357,7 @@ static int setup(const char* who, Params& x, const void* q, const void* k, const
   int rc = attn_check_shape(who, b >= 0 && h > 0 && lq >= 0 && lk >= 0, d == 256 || d == 384 || d == 512, d,
                             "this entry point takes 256, 384 and 512", dtype, out_lo);
   if (rc != GMLM_OK) return rc;
-  if ((rc = attn_check_rates(who, dropout_p, true, scale)) != GMLM_OK) return rc;
+  if ((rc = attn_check_rates(who, dropout_p, nullptr, scale)) != GMLM_OK) return rc;
   const int64_t rows = lq > lk ? lq : lk;
   GMLM_REQUIRE(b < ((int64_t)1 << 31) && h < ((int64_t)1 << 31) && rows < ((int64_t)1 << 31) &&
                    (double)cdiv(rows, R) * (double)b * (double)h < 2147483648.0 &&

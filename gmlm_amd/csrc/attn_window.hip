@@ -30,17 +30,7 @@ struct WinParams {
   int64_t window;
 };
 
-template <typename T> struct Cfg;
-template <> struct Cfg<bf16_t> { static constexpr int KT = 64, QT = 32; static constexpr bool DBUF = true; };
-template <> struct Cfg<float> { static constexpr int KT = 32, QT = 32; static constexpr bool DBUF = false; };
-
-// work item of the 1-D grid -> (tile, batch or sequence, head); tiles are outermost
-struct Item { int64_t tile, b, hd; };
-__device__ __forceinline__ Item decode(const AttnParams& p) {
-  const int64_t pairs = p.b * p.h, item = blockIdx.x;
-  const int64_t bh = item % pairs;
-  return {item / pairs, bh / p.h, bh % p.h};
-}
+// Cfg<T> (tile sizes) is attn_stream.hpp's, decode() (1-D grid -> tile, sequence, head) attn_common.hpp's
 
 // forward: workgroup = 128 query rows of one (sequence, head), key tiles of the band
 template <typename T>

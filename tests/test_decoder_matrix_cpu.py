@@ -119,9 +119,17 @@ def test_the_sources_still_hold_the_restated_constants():
     assert "cdiv(items * 16, 256), 256, 0, st>>>((const bf16_t*)qkv" in dec and "cdiv(items * 32, 256), 256, 0, st>>>((const float*)qkv" in dec
     assert "rows_sum_kernel<<<8, 256, 0, st>>>(partial, nb, 256, dq_weight);" in dec
     assert dec.count(f"const int grid = grid_cap(cdiv(rows * (inter / v), 256), {SWIGLU_GRID_CAP});") == 2
-    assert "constexpr int D = 128, NW = 4, NT = NW * 64, BQ = NW * 32;" in cau
-    assert cau.count("cdiv(lq, BQ) * b * hq") == 3 and "cdiv(lk, BQ) * b * hkv" in cau          # the size check, fwd, dq; dkv
-    assert "if (kvlen > lk_) kvlen = lk_; if (kvlen < 0) kvlen = 0;" in cau
+    grp, com = _src("attn_grouped.hpp"), _src("attn_common.hpp")      # the host side and the tile constants of causal128 / clamp_kvlen
+    assert "constexpr int D = 128;" in cau and "using grouped::Params, grouped::NW, grouped::NT;" in cau
+    assert "constexpr int NW = 4, NT = NW * 64, BQ = NW * 32;" in grp
+    assert "cdiv(s.len, BQ) * s.n * hq < ((int64_t)1 << 31)" in grp                             # the size check
+    assert grp.count("const int64_t tiles = cdiv(s.len, BQ)") == 2 and grp.count(", x, tiles, s.n, ") == 4   # fwd, bwd; x dtype
+    assert grp.count("<<<(unsigned)(tiles * seqs * hq), NT, 0, st>>>(x);") == 2                 # fwd, dq
+    assert grp.count("<<<(unsigned)(tiles * seqs * hkv), NT, 0, st>>>(x);") == 1                # dkv
+    assert "padded(const int32_t* kv_len, int64_t b, int64_t lq, int64_t lk) { return {kv_len, nullptr, b, lq, lk, lq, false}; }" in grp
+    assert cau.count("grouped::padded(kv_len, b, lq, lk)") == 2
+    assert "if (kvlen > lk_) kvlen = lk_; if (kvlen < 0) kvlen = 0;" in com
+    assert "clamp_kvlen(x.a, it.b, it.l));" in cau
     col = _src("colreduce.hpp")
     assert "for (; r + 24 < nrows; r += 32)" in col and "for (; r < nrows; r += 8)" in col      # rows_sum_depth
 

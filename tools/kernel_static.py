@@ -8,7 +8,11 @@ stripped), from the code objects' metadata and disassembly.  Equal hashes = the 
 
 ``--dynamic-lds 'REGEX=BYTES'`` (repeatable) records the dynamic LDS the host adds at launch for kernels whose static
 ``lds_bytes`` is not the whole picture.  ``--match``: kernels (demangled name, regex) that must be the same in both builds; ``--added``: kernels only the new build
-has, listed with their figures.  Exit status 1 when a matched kernel differs or is missing.
+has, listed with their figures.  ``--bare`` pairs the kernels by name without the parameter list, for a build in which a kernel's
+parameter type moved namespace; a symbol of another length also moves the zero padding behind a kernel, which the disassembler
+prints as a line "...", so with this flag that line is neither counted nor hashed: for a kernel that ends in padding,
+``instructions`` is one less and ``body_sha1`` another than in a record made without the flag.  Exit status 1 when a matched
+kernel differs or is missing.
 """
 import argparse
 import hashlib
@@ -48,7 +52,7 @@ def demangle(names):
     return {n: torch._C._demangle(n) for n in names}
 
 
-def kernels(so):
+def kernels(so, skip_padding=False):
     res = {}
     with tempfile.TemporaryDirectory() as tmp:
         for co in code_objects(so, tmp):
@@ -66,6 +70,8 @@ def kernels(so):
                 if sym not in meta:
                     continue
                 text = re.sub(r"//.*", "", body)                    # the comment holds the address, the encoding and <symbol+offset>
+                if skip_padding:                                    # "...": zero padding up to the next symbol, layout and not code
+                    text = re.sub(r"^\s*\.\.\.\s*$", "", text, flags=re.M)
                 ops = re.findall(r"^\s*(\S+)", text, re.M)
                 stream = "\n".join(" ".join(ln.split()) for ln in text.splitlines() if ln.strip())
                 d = dict(meta[sym])
@@ -76,6 +82,18 @@ def kernels(so):
                 res[sym] = d
     names = demangle(list(res))
     return {re.sub(r"^void ", "", names[s]): dict(symbol=s, **d) for s, d in res.items()}
+
+
+def bare(name):
+    """The demangled name without its parameter list (template arguments kept)."""
+    depth = 0
+    for i, c in enumerate(name):
+        depth += (c == "<") - (c == ">")
+        if c == "(" and depth == 0:
+            name = name[:i]
+            break
+    # library templates (rocprim) run to a kilobyte: keep the head and a hash of the whole name
+    return name if len(name) <= 120 else name[:96] + "...#" + hashlib.sha1(name.encode()).hexdigest()[:10]
 
 
 def main():
@@ -89,8 +107,14 @@ def main():
                     help="dynamic LDS the host requests at launch for the kernels matching REGEX (lds_bytes is the static part only); "
                          "recorded as given")
     ap.add_argument("--compact", action="store_true", help="one short line per kernel (unchanged kernels: name and figures once)")
+    ap.add_argument("--bare", action="store_true",
+                    help="pair the kernels of the two builds by name without the parameter list (a parameter type that moved namespace)")
     a = ap.parse_args()
-    old, new = kernels(a.parent), kernels(a.new)
+    old, new = kernels(a.parent, a.bare), kernels(a.new, a.bare)
+    if a.bare:
+        for ks in (old, new):
+            assert len({bare(k) for k in ks}) == len(ks), "two kernels share a name without its parameter list"
+        old, new = ({bare(k): dict(d, symbol=bare(k)) for k, d in ks.items()} for ks in (old, new))
     keys = ("symbol", "vgpr", "lds_bytes", "scratch_bytes", "v_mfma", "scratch_instr", "packed_f32", "instructions", "body_sha1")
     rows, bad = [], 0
     for name in sorted(k for k in old if re.search(a.match, k)):
@@ -110,15 +134,6 @@ def main():
     text = json.dumps(res, indent=1)
     if a.compact:
         # one line per kernel: [name without its parameter list, figures in the order of "columns"]; a changed kernel keeps its full row
-        def bare(name):
-            depth = 0
-            for i, c in enumerate(name):
-                depth += (c == "<") - (c == ">")
-                if c == "(" and depth == 0:
-                    name = name[:i]
-                    break
-            # library templates (rocprim) run to a kilobyte: keep the head and a hash of the whole name
-            return name if len(name) <= 120 else name[:96] + "...#" + hashlib.sha1(name.encode()).hexdigest()[:10]
         flat = [[bare(r["kernel"])] + [r["parent"][k] for k in keys[1:]] if r["unchanged"] else r for r in rows]
         extra = [k for k in (added[0] if added else {}) if k != "kernel" and k not in keys]
         new_rows = [[bare(d["kernel"])] + [d[k] for k in list(keys[1:]) + extra] for d in added]
