@@ -62,9 +62,11 @@ __device__ __forceinline__ float disent_term(const DisentTabs& t, const float* c
 // DISENT (lq == lk): the score of query i and key j gets C[row i][col[i - j]] + Pt[row j][col[i - j]] BEFORE the scale (struct
 //   DisentTabs above), s' = (s + C + Pt) * scale * log2 e right behind the QK^T chain, and everything after it works on s' as
 //   with BIAS.  The row of a query or key past its sequence is clamped into the sequence; such a pair is masked or never stored.
-//   Dropout: the P V product takes P * (0 or 1) and the keep scale multiplies the output once, with 1 / l (bf16: the scaled
+//   Dropout (DISENT and BIAS): the P V product takes P * (0 or 1) and the keep scale multiplies the output once, with 1 / l (bf16: the scaled
 //   probability is never rounded, so O and the backward's delta = rowsum(dO * O) agree with D * dP to fp32 rounding; a row
-//   with one key, P = 1, then has dS = 0 as it must).
+//   with one key, P = 1, then has dS = 0 as it must).  Folded into the probabilities, the largest one of every row, exp2(0) = 1, would
+//   become bf16(keep scale) each time, e.g. 256 / 230 -> 1.109375: 3.3e-3 low in every row, which biases delta and with it the
+//   gradients of the tables that BIAS and DISENT add to the scores.
 template <typename T, int D, int NW, bool DROP, int KT, bool DBUF, bool CAUSAL = false, bool GQA = false, bool WINDOW = false,
           bool BIAS = false, bool DISENT = false>
 __device__ __forceinline__ void attn_fwd_body(const AttnParams& p, int64_t tile, int64_t b, int64_t hd, int64_t o_stride,
@@ -192,7 +194,7 @@ __device__ __forceinline__ void attn_fwd_body(const AttnParams& p, int64_t tile,
         rsum += e0 + e1;                                               // the normaliser uses the un-dropped probabilities
         if (DROP) {
           float m0, m1;                                // keys (k, k+1): (kv0 + kb*32 + acc_row(i, 0)) >> 1 pairs on from the tile start
-          drop_pair_q(dq_u + ((uint32_t)(t * (KT / 2)) + (uint32_t)((kb * 32 + acc_row(i, 0)) >> 1)) * kDropC2, q_odd, p.drop_thresh, DISENT ? 1.f : p.keep_scale, m0, m1);
+          drop_pair_q(dq_u + ((uint32_t)(t * (KT / 2)) + (uint32_t)((kb * 32 + acc_row(i, 0)) >> 1)) * kDropC2, q_odd, p.drop_thresh, (DISENT || BIAS) ? 1.f : p.keep_scale, m0, m1);
           s[kb][i] = e0 * m0;
           s[kb][i + 1] = e1 * m1;
         } else {
@@ -228,7 +230,7 @@ __device__ __forceinline__ void attn_fwd_body(const AttnParams& p, int64_t tile,
     }
   }
   if (q_ok) {
-    const float inv = l > 0.f ? (DISENT && DROP ? p.keep_scale : 1.f) / l : 0.f;
+    const float inv = l > 0.f ? ((DISENT || BIAS) && DROP ? p.keep_scale : 1.f) / l : 0.f;
     T* og = static_cast<T*>(p.o_w) + (qbase + q_row) * o_stride + hd * D;
 #pragma unroll
     for (int d = 0; d < DB; ++d) store_t<T>(og + d * 32, o[d], inv, h);

@@ -668,7 +668,8 @@ class AttentionQKV(torch.autograd.Function):
         if groups is not None and not (packed and short):
             groups = None                                       # only the short-sequence kernels pack sequences into work items
         n_groups = 0 if groups is None else groups.numel() - 1
-        out_lo = torch.empty_like(out) if (qkv.dtype == torch.bfloat16 and not short and qkv.requires_grad) else None
+        # (a backward runs when ANY input needs a gradient: trainable bias masters behind a frozen qkv get the same delta)
+        out_lo = torch.empty_like(out) if (qkv.dtype == torch.bfloat16 and not short and any(ctx.needs_input_grad)) else None
         nb = out.numel() * out.element_size()                   # one of q, k, v, o
         with _span("attn_fwd_d%d" % d, flops=flops, bytes=(4 + (1 if out_lo is not None else 0)) * nb):
             sd = ctx.sd = _sd()
@@ -698,7 +699,9 @@ class AttentionQKV(torch.autograd.Function):
         else:
             qkv, lse, kv_len, cu_seqlens, groups, out, out_lo = ctx.saved_tensors
         h, scale, p, seed, max_len, b, l, flops = ctx.cfg
-        want_db = bool(ctx.bias_shapes) and any(ctx.needs_input_grad[10:])
+        # per master; a frozen one gets None, never a missing entry (cut to the masters: _RopeAttention runs this with its own ctx)
+        need_db = ctx.needs_input_grad[10:10 + len(ctx.bias_shapes)] if ctx.bias_shapes else ()
+        want_db = any(need_db)
         hd3 = qkv.shape[-1]
         hd = hd3 // 3
         d = hd // h
@@ -727,12 +730,12 @@ class AttentionQKV(torch.autograd.Function):
                                scale=scale, dropout_p=p, seed=seed, seed_dev=ctx.sd, dq=_ptr(dq), dk=_ptr(dk), dv=_ptr(dv),
                                dq_stride=hd3, dk_stride=hd3, dv_stride=hd3, dtype=_dt(qkv), cu_seqlens=_ptr(cu_seqlens), max_len=max_len,
                                dbias_partial=_ptr(part), dbias=_ptr(db), seq_groups=_ptr(groups), num_groups=n_groups)
-        dbs = ()
+        dbs = (None,) * len(ctx.bias_shapes)
         if want_db:
             if db is None:
                 db = column_sum(dqkv.reshape(-1, hd3))
-            dbs = tuple(g if g.dtype == dt_ else g.to(dt_)
-                        for g, (_, dt_) in zip(db.split([n_ for n_, _ in ctx.bias_shapes], 0), ctx.bias_shapes))
+            dbs = tuple((g if g.dtype == dt_ else g.to(dt_)) if need else None
+                        for g, (_, dt_), need in zip(db.split([n_ for n_, _ in ctx.bias_shapes], 0), ctx.bias_shapes, need_db))
         return (dqkv, None, None, None, None, None, None, None, None, None, *dbs)
 
 
@@ -855,9 +858,10 @@ class MeanPoolScatter(torch.autograd.Function):
             dhs[valid_rows:].zero_()
         check(lib().gmlm_meanpool_scatter_bwd(_ptr(g), _ptr(lens), _ptr(node_idx), b, l, p, _ptr(dhs), _dt(dhs),
                                               _ptr(cu_seqlens), _stream()), "gmlm_meanpool_scatter_bwd")
-        # rows written by this micro-batch were overwritten: no gradient flows to their previous value;
-        # the previous value is the zero-initialised buffer (a constant), so passing g through is harmless.
-        return g, dhs, None, None, None, None
+        # rows written by this micro-batch were overwritten: no gradient flows to their previous value (out of place: g may
+        # be the caller's tensor).  The first micro-batch's buffer is a constant and gets nothing.
+        dprev = g.index_fill(0, node_idx[:b].long(), 0.0) if ctx.needs_input_grad[0] else None
+        return dprev, dhs, None, None, None, None
 
 
 # ---------------------------------------------------------------------------------------------

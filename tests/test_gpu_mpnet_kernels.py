@@ -17,7 +17,7 @@ Budgets.  out, dq, dk, dv: ``test_gpu_attention_matrix._budget`` (fp32 1e-4 max 
 8e-3 gradients).  d_rel_bias: the rows of dS sum to zero, so its entries cancel and the error is measured against the norm of
 the whole tensor: fp32 1e-5 of it.  bf16 has no fixed number: the bias-gradient kernel itself keeps S, P, dP and dS in fp32
 (its q, k, v, dO are the stored bf16 values), and what it inherits is delta = rowsum(dO * O) of an output whose forward fed
-bf16(P * D) to the P V product.  ``_bf16_floor`` evaluates the dense formula in float64 with exactly that rounding; its error
+bf16 probabilities to the P V product.  ``_dense(..., round_p=True)`` evaluates the dense formula in float64 with bf16(P * D); its error
 against the unrounded float64 result is the floor, the kernel must be within 2x of it (as the encoder tests do with HF's bf16
 run), and both figures are printed.
 
