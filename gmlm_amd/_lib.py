@@ -1,5 +1,5 @@
 """ctypes binding of libgmlm_hip.so (C ABI: include/gmlm_hip.h, gmlm_hip_split.h, gmlm_hip_optim.h, gmlm_hip_d32.h,
-gmlm_hip_wide.h, gmlm_hip_modernbert.h, gmlm_hip_relbias.h, gmlm_hip_disent.h, gmlm_hip_gqa.h, gmlm_hip_bidir.h, gmlm_hip_gqa_short.h and gmlm_hip_d32_short.h): one signature table per header, positional argument types only.  Which attention entry point a head dim
+gmlm_hip_wide.h, gmlm_hip_modernbert.h, gmlm_hip_relbias.h, gmlm_hip_disent.h, gmlm_hip_gqa.h, gmlm_hip_bidir.h, gmlm_hip_gqa_short.h, gmlm_hip_d32_short.h and gmlm_hip_gqa_wide.h): one signature table per header, positional argument types only.  Which attention entry point a head dim
 takes, and where each ABI puts its arguments by name, is the family table of ops.py (``_ATTN_FAMILIES``).
 
 The product path has NO fallback: if the shared library is missing or a call fails, a Python
@@ -203,8 +203,35 @@ SIGNATURES_D32_SHORT = {
                                                _u64, _p, _p, _i64, _p, _p, _p, _i64, _i64, _i64, _p, _p, _i32, _p]),
 }
 
+# thirteenth header, include/gmlm_hip_gqa_wide.h (Gemma3 text encoders: grouped-KV attention at head dim 256, causal or not, the
+# sandwich RMSNorm pair, Q / K head norm + rotary embedding at head dim 256, tanh-GELU gated unit).  The attention entry points
+# take the argument lists of their gmlm_attention_bidir_gqa_* namesakes with `causal` (int) after dropout_p, the rotary ones
+# those of gmlm_qknorm_rope_* with `w_offset` (float) after d
+_GQAW_FWD = (C.c_int, [_p, _p, _p, _p] + [_i64] * 9 + [_f32, _f32, _i32, _p, _p, _p, _i32, _p])
+_GQAW_BWD = (C.c_int, [_p] * 8 + [_i64] * 9 + [_f32, _f32, _i32, _p, _p, _p, _i64, _i64, _i64, _i32, _p, _sz, _p])
+SIGNATURES_GQA_WIDE = {
+    "gmlm_attention_gqa_d256_fwd": _GQAW_FWD,
+    "gmlm_attention_gqa_d256_bwd_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "gmlm_attention_gqa_d256_bwd": _GQAW_BWD,
+    "gmlm_attention_gqa_d256_varlen_fwd": _GQAW_FWD,
+    "gmlm_attention_gqa_d256_varlen_bwd_workspace_bytes": (_sz, [_i64, _i64]),
+    "gmlm_attention_gqa_d256_varlen_bwd": _GQAW_BWD,
+    "gmlm_sandwich_rmsnorm_fwd": (C.c_int, [_p, _p, _p, _p, _i64, _i64, _f32, _f32, _p, _p, _p, _p, _i32, _p]),
+    "gmlm_sandwich_rmsnorm_bwd_workspace_bytes": (_sz, [_i64, _i64]),
+    "gmlm_sandwich_rmsnorm_bwd": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _f32, _p, _p, _p, _p, _i32, _p, _sz, _p]),
+    "gmlm_qknorm_rope_d256_fwd": (C.c_int, [_p, _i64, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _f32, _p, _i64, _p, _i32, _p]),
+    "gmlm_qknorm_rope_d256_pos_fwd": (C.c_int, [_p, _i64, _p, _p, _p, _i64, _i64, _p, _i64, _i64, _i64, _f32, _f32, _p, _i64, _p, _i32, _p]),
+    "gmlm_qknorm_rope_d256_bwd_workspace_bytes": (_sz, [_i64, _i64, _i64, _i32]),
+    "gmlm_qknorm_rope_d256_bwd": (C.c_int, [_p, _i64, _p, _i64, _p, _p, _p, _i64, _p, _i64, _i64, _i64, _i64, _i64, _f32, _p, _p, _i32, _p,
+                                            _sz, _p]),
+    "gmlm_qknorm_rope_d256_pos_bwd": (C.c_int, [_p, _i64, _p, _i64, _p, _p, _p, _i64, _p, _i64, _p, _i64, _i64, _i64, _f32, _p, _p, _i32, _p,
+                                                _sz, _p]),
+    "gmlm_geglu_tanh_fwd": (C.c_int, [_p, _i64, _i64, _p, _i32, _p]),
+    "gmlm_geglu_tanh_bwd": (C.c_int, [_p, _p, _i64, _i64, _p, _i32, _p]),
+}
+
 SIGNATURE_TABLES_LATER = (SIGNATURES_RELBIAS, SIGNATURES_GQA, SIGNATURES_BIDIR, SIGNATURES_GQA_SHORT, SIGNATURES_D32_SHORT,
-                          SIGNATURES_DISENT)
+                          SIGNATURES_GQA_WIDE, SIGNATURES_DISENT)
 
 
 class GmlmHipError(RuntimeError):

@@ -1,4 +1,4 @@
-"""What the text encoders (bert.py, mpnet.py, qwen3.py, modernbert.py, deberta.py, llama.py, eurobert.py, nomic_bert.py) share: the loop over the layers with its checkpoint
+"""What the text encoders (bert.py, mpnet.py, qwen3.py, modernbert.py, deberta.py, llama.py, eurobert.py, nomic_bert.py, gemma3.py) share: the loop over the layers with its checkpoint
 rule, the rotary cos / sin table, the argument checks, and the post-LayerNorm layer of the BERT geometry (its weights and
 everything after the attention)."""
 from __future__ import annotations

@@ -1167,8 +1167,20 @@ def qknorm_rope(qkv, q_weight, k_weight, cos_sin, hq, hkv, eps=1e-6, pos_ids=Non
 def _gqa_entry(d, bidir):
     """(entry-point stem, span stem) of a grouped-KV attention family: causal at d = 128 (gmlm_attention_causal_d128_*) or 64
     (gmlm_attention_causal_d64_*, include/gmlm_hip_gqa.h), or ``bidir``: no causal mask, d = 64 / 128 (gmlm_attention_bidir_gqa_*,
-    include/gmlm_hip_bidir.h).  One argument list for all of them."""
+    include/gmlm_hip_bidir.h).  One argument list for all of them.  d = 256 (gmlm_attention_gqa_d256_*, include/gmlm_hip_gqa_wide.h):
+    one family for both masks, whose argument list has ``causal`` after the dropout rate (``_gqa_causal_arg``) and whose workspace
+    queries are named ``*_bwd_workspace_bytes`` (``_gqa_ws``)."""
+    if d == GQA_WIDE_HEAD_DIM:
+        return "gmlm_attention_gqa_d256", "attn_gqaw"
     return ("gmlm_attention_bidir_gqa", "attn_bidir") if bidir else (f"gmlm_attention_causal_d{d}", "attn_causal")
+
+
+def _gqa_causal_arg(d, bidir):
+    return (0 if bidir else 1,) if d == GQA_WIDE_HEAD_DIM else ()
+
+
+def _gqa_ws(stem, d, varlen=""):
+    return stem + varlen + ("_bwd_workspace_bytes" if d == GQA_WIDE_HEAD_DIM else "_workspace_bytes")
 
 
 def _causal_fwd(q, k, v, kv_len, hq, hkv, scale, want_lo, d=128, bidir=False):
@@ -1181,7 +1193,7 @@ def _causal_fwd(q, k, v, kv_len, hq, hkv, scale, want_lo, d=128, bidir=False):
     name = stem + "_fwd"
     with _span(f"{tag}_fwd_d{d}", flops=(4.0 if bidir else 2.0) * b * hq * l * l * d):
         check(getattr(lib(), name)(_ptr(q), _ptr(k), _ptr(v), _ptr(kv_len), b, hq, hkv, l, k.shape[1], d, qs, ks, vs, float(scale), 0.0,
-                                   _ptr(out), _ptr(out_lo), _ptr(lse), _dt(q), _stream()), name)
+                                   *_gqa_causal_arg(d, bidir), _ptr(out), _ptr(out_lo), _ptr(lse), _dt(q), _stream()), name)
     return out, out_lo, lse
 
 
@@ -1189,12 +1201,13 @@ def _causal_bwd(q, k, v, out, out_lo, gout, lse, kv_len, hq, hkv, scale, dq, dk,
     stem, tag = _gqa_entry(d, bidir)
     b, l = q.shape[0], q.shape[1]
     gout = gout.contiguous().to(q.dtype)
-    ws = _ws(getattr(lib(), stem + "_workspace_bytes")(b, hq, l), q.device)
+    ws = _ws(getattr(lib(), _gqa_ws(stem, d))(b, hq, l), q.device)
     name = stem + "_bwd"
     with _span(f"{tag}_bwd_d{d}", flops=(10.0 if bidir else 5.0) * b * hq * l * l * d):
         check(getattr(lib(), name)(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(out_lo), _ptr(gout), _ptr(lse), _ptr(kv_len), b, hq, hkv, l,
-                                   k.shape[1], d, q.stride(1), k.stride(1), v.stride(1), float(scale), 0.0, _ptr(dq), _ptr(dk), _ptr(dv),
-                                   dq.stride(1), dk.stride(1), dv.stride(1), _dt(q), _ptr(ws), ws.numel(), _stream()), name)
+                                   k.shape[1], d, q.stride(1), k.stride(1), v.stride(1), float(scale), 0.0, *_gqa_causal_arg(d, bidir),
+                                   _ptr(dq), _ptr(dk), _ptr(dv), dq.stride(1), dk.stride(1), dv.stride(1), _dt(q), _ptr(ws), ws.numel(),
+                                   _stream()), name)
 
 
 class CausalAttention(torch.autograd.Function):
@@ -1299,7 +1312,7 @@ def _causal_varlen_fwd(q, k, v, cu, s, max_len, hq, hkv, scale, want_lo, d=128, 
     name = stem + "_varlen_fwd"
     with _span(f"{tag}_varlen_fwd_d{d}", flops=(4.0 if bidir else 2.0) * s * hq * max_len * max_len * d):
         check(getattr(lib(), name)(_ptr(q), _ptr(k), _ptr(v), _ptr(cu), s, max_len, t, hq, hkv, d, qs, ks, vs, float(scale), 0.0,
-                                   _ptr(out), _ptr(out_lo), _ptr(lse), _dt(q), _stream()), name)
+                                   *_gqa_causal_arg(d, bidir), _ptr(out), _ptr(out_lo), _ptr(lse), _dt(q), _stream()), name)
     return out, out_lo, lse
 
 
@@ -1315,12 +1328,12 @@ def _causal_varlen_bwd(q, k, v, out, out_lo, gout, lse, cu, s, max_len, hq, hkv,
                                        _groups_arg(groups, cu), _ptr(dq), _ptr(dk), _ptr(dv), dq.stride(0), dk.stride(0),
                                        dv.stride(0), _dt(q), _stream()), name)
         return
-    ws = _ws(getattr(lib(), stem + "_varlen_workspace_bytes")(t, hq), q.device)
+    ws = _ws(getattr(lib(), _gqa_ws(stem, d, "_varlen"))(t, hq), q.device)
     name = stem + "_varlen_bwd"
     with _span(f"{tag}_varlen_bwd_d{d}", flops=(10.0 if bidir else 5.0) * s * hq * max_len * max_len * d):
         check(getattr(lib(), name)(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(out_lo), _ptr(gout), _ptr(lse), _ptr(cu), s, max_len, t, hq,
-                                   hkv, d, q.stride(0), k.stride(0), v.stride(0), float(scale), 0.0, _ptr(dq), _ptr(dk), _ptr(dv),
-                                   dq.stride(0), dk.stride(0), dv.stride(0), _dt(q), _ptr(ws), ws.numel(), _stream()), name)
+                                   hkv, d, q.stride(0), k.stride(0), v.stride(0), float(scale), 0.0, *_gqa_causal_arg(d, bidir), _ptr(dq), _ptr(dk),
+                                   _ptr(dv), dq.stride(0), dk.stride(0), dv.stride(0), _dt(q), _ptr(ws), ws.numel(), _stream()), name)
 
 
 class CausalAttentionVarlen(torch.autograd.Function):
@@ -1440,6 +1453,11 @@ def add_layernorm(a, b, gamma, beta=None, eps=1e-5):
 
 def geglu(u):
     return _GLU.apply("geglu", u)
+
+
+def geglu_tanh(u):
+    """[..., 2 I] = [gate | up] -> gelu_tanh(gate) * up, the tanh form of GELU (Gemma3: ``gelu_pytorch_tanh``; gmlm_geglu_tanh_*)."""
+    return _GLU.apply("geglu_tanh", u)
 
 
 def rope64_(qkv, cos_sin, h, seq_len=0, pos_ids=None, inverse=False):
@@ -1568,6 +1586,7 @@ def rope_attention_varlen(qkv, cos_sin, pos_ids, cu_seqlens, max_len, num_heads,
 # (include/gmlm_hip_gqa.h); EuroBERT encoders: the same with bidirectional GQA attention (include/gmlm_hip_bidir.h)
 # ---------------------------------------------------------------------------------------------
 GQA_HEAD_DIMS = (64, 128)        # gmlm_rope_heads_*; causal attention: gmlm_attention_causal_d64_* / _d128_*
+GQA_WIDE_HEAD_DIM = 256          # gmlm_attention_gqa_d256_*, gmlm_qknorm_rope_d256_* (Gemma3 encoders, include/gmlm_hip_gqa_wide.h)
 
 
 def rope_heads_(qkv, cos_sin, heads, d, seq_len=0, pos_ids=None, inverse=False):
@@ -1848,3 +1867,10 @@ def attention_disent_qkv_varlen(qkv, c2p, p2c, col, cu_seqlens, max_len, num_hea
     col int32 [2M - 1] with M >= max_len."""
     p = float(dropout_p) if training else 0.0
     return AttentionDisentQKV.apply(qkv, c2p, p2c, col, None, num_heads, scale, p, draw_seed() if p > 0 else 0, cu_seqlens, int(max_len))
+
+
+# ---------------------------------------------------------------------------------------------
+# Gemma3 encoders (include/gmlm_hip_gqa_wide.h): the sandwich RMSNorm pair and head norm + rotary embedding + grouped-KV attention
+# at head dim 256; ``geglu_tanh`` is above, the plain attention nodes are CausalAttention / CausalAttentionVarlen with d = 256
+# ---------------------------------------------------------------------------------------------
+from .ops_gemma import gqa_d256_attention, gqa_d256_attention_varlen, rope_gqa_d256, rope_gqa_d256_varlen, sandwich_rmsnorm  # noqa: E402,F401
