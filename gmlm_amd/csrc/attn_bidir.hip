@@ -40,7 +40,7 @@ __global__ __launch_bounds__(NT) void gqa_dkv_kernel(Params x) {
 }
 
 static const grouped::Family kFamily = {
-    "this entry point takes 64 or 128", "self-attention", "grouped",
+    {"this entry point takes 64 or 128", "self-attention", "grouped"},
     {{gqa_fwd_kernel<bf16_t, 64>, gqa_delta_kernel<bf16_t, 64>, gqa_dq_kernel<bf16_t, 64>, gqa_dkv_kernel<bf16_t, 64>},
      {gqa_fwd_kernel<bf16_t, 128>, gqa_delta_kernel<bf16_t, 128>, gqa_dq_kernel<bf16_t, 128>, gqa_dkv_kernel<bf16_t, 128>}},
     {{gqa_fwd_kernel<float, 64>, gqa_delta_kernel<float, 64>, gqa_dq_kernel<float, 64>, gqa_dkv_kernel<float, 64>},

@@ -37,7 +37,7 @@ __global__ __launch_bounds__(NT) void dkv_kernel(Params x) {
 }
 
 static const grouped::Family kFamily = {
-    "this entry point takes 128", "causal self-attention", "causal",
+    {"this entry point takes 128", "causal self-attention", "causal"},
     {{}, {fwd_kernel<bf16_t>, delta_kernel<bf16_t>, dq_kernel<bf16_t>, dkv_kernel<bf16_t>}},
     {{}, {fwd_kernel<float>, delta_kernel<float>, dq_kernel<float>, dkv_kernel<float>}}};
 

@@ -109,7 +109,7 @@ __global__ __launch_bounds__(NT) void causal64_dkv_kernel(Params x) {
 }
 
 static const grouped::Family kFamily = {
-    "this entry point takes 64", "causal self-attention", "causal",
+    {"this entry point takes 64", "causal self-attention", "causal"},
     {{causal64_fwd_kernel<bf16_t>, causal64_delta_kernel<bf16_t>, causal64_dq_kernel<bf16_t>, causal64_dkv_kernel<bf16_t>}, {}},
     {{causal64_fwd_kernel<float>, causal64_delta_kernel<float>, causal64_dq_kernel<float>, causal64_dkv_kernel<float>}, {}}};
 

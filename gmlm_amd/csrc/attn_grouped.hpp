@@ -2,6 +2,8 @@
 //   gmlm_attention_causal_d128_*  attn_causal.hip  causal128::*       causal, d = 128        (Qwen3)
 //   gmlm_attention_causal_d64_*   attn_gqa.hip     gqa::causal64_*    causal, d = 64         (Llama, Qwen2, Mistral)
 //   gmlm_attention_bidir_gqa_*    attn_bidir.hip   bidir::gqa_*       bidirectional, d = 64 / 128   (EuroBERT, NomicBERT)
+// and, for the launch parameters and the argument checks alone (its kernels are the four-waves-per-head plan of attn_wide.hpp):
+//   gmlm_attention_gqa_d256_*     attn_gqa_wide.hip  gqaw::*          causal or bidirectional, d = 256   (Gemma3)
 // A family's file holds its __global__ wrappers, one Family (its kernels, head dims and words) and its exports; everything else
 // is here: the launch parameters, the argument checks in the order of attn_host.hpp, the launches and the two entry-point
 // bodies.  A wrapper is decode() + one call: forward and dQ ARE attn_fwd_body / attn_dq_body (attn_stream.hpp) with GQA = true,
@@ -52,12 +54,19 @@ struct Kernels {
   void (*dq)(Params);
   void (*dkv)(Params);
 };
-struct Family {
+// what setup() is told about a family: its words in the refusals and its grids
+struct Contract {
   const char* dims;             // how the head-dim refusal names the head dims taken
   const char* self;             // "causal self-attention" or "self-attention": the lq == lk refusal
   const char* no_dropout;       // how the dropout refusal names the kernels (attn_check_rates)
+  int wave_rows = 0;            // 0: work items of BQ rows, delta by attn_delta_body.  > 0 (attn_gqa_wide.hip): work items of this many
+                                // rows and a delta launch of one wave per (row, head), both grids bounded by setup()
+};
+struct Family {
+  Contract c;
   Kernels<bf16_t> bf[2];        // [d == 128]; a head dim the family does not take stays empty
-  Kernels<float> fp[2];         // INV: filled for the same head dims as bf (setup() reads the head dims taken from bf alone)
+  Kernels<float> fp[2];         // INV: filled for the same head dims as bf (fwd() / bwd() read the head dims taken from bf alone)
+  bool takes(int64_t d) const { return (d == 64 || d == 128) && bf[d == 128].fwd; }
 };
 
 // The sequences of a call.  Padded: n sequences of len rows each (= lk), rows = len.  Packed: n sequences of at most len rows,
@@ -72,9 +81,10 @@ struct Seqs {
 inline Seqs padded(const int32_t* kv_len, int64_t b, int64_t lq, int64_t lk) { return {kv_len, nullptr, b, lq, lk, lq, false}; }
 inline Seqs packed(const int32_t* cu, int64_t seqs, int64_t max_len, int64_t rows) { return {nullptr, cu, seqs, max_len, max_len, rows, true}; }
 
-// the checks of attn_host.hpp up to the empty-problem return, with the family's head dims and words; fills the launch parameters
-inline int setup(const Family& f, const char* who, Params& x, const Seqs& s, const void* q, const void* k, const void* v, int64_t hq,
-                 int64_t hkv, int64_t d, int64_t q_stride, int64_t k_stride, int64_t v_stride, float scale, float dropout_p,
+// the checks of attn_host.hpp up to the empty-problem return, with the family's words and grids; d_ok = the family takes head
+// dim d; fills the launch parameters
+inline int setup(const Contract& c, bool d_ok, const char* who, Params& x, const Seqs& s, const void* q, const void* k, const void* v,
+                 int64_t hq, int64_t hkv, int64_t d, int64_t q_stride, int64_t k_stride, int64_t v_stride, float scale, float dropout_p,
                  const void* out_lo, int dtype) {
   constexpr int64_t k2_30 = (int64_t)1 << 30;
   if (s.packed) {
@@ -83,12 +93,16 @@ inline int setup(const Family& f, const char* who, Params& x, const Seqs& s, con
     GMLM_REQUIRE(s.n >= 0 && s.rows >= 0 && s.rows < k2_30, "%s: %ld packed rows (must be >= 0 and < 2^30)", who, (long)s.rows);
   }
   int rc = attn_check_shape(who, (s.packed ? s.len < k2_30 && s.n < k2_30 : s.n >= 0 && s.len >= 0 && s.lk >= 0) && hq > 0 && hkv > 0,
-                            (d == 64 || d == 128) && f.bf[d == 128].fwd, d, f.dims, dtype, out_lo);
+                            d_ok, d, c.dims, dtype, out_lo);
   if (rc != GMLM_OK) return rc;
-  GMLM_REQUIRE(s.len == s.lk, "%s: %s needs lq == lk (got %ld and %ld)", who, f.self, (long)s.len, (long)s.lk);
+  GMLM_REQUIRE(s.len == s.lk, "%s: %s needs lq == lk (got %ld and %ld)", who, c.self, (long)s.len, (long)s.lk);
   GMLM_REQUIRE(hq % hkv == 0, "%s: %ld query heads are not a multiple of %ld KV heads", who, (long)hq, (long)hkv);
-  if ((rc = attn_check_rates(who, dropout_p, f.no_dropout, scale)) != GMLM_OK) return rc;
-  GMLM_REQUIRE(s.len < k2_30 && cdiv(s.len, BQ) * s.n * hq < ((int64_t)1 << 31), "%s: too many work items", who);
+  if ((rc = attn_check_rates(who, dropout_p, c.no_dropout, scale)) != GMLM_OK) return rc;
+  const bool fits = !c.wave_rows ? cdiv(s.len, BQ) * s.n * hq < ((int64_t)1 << 31)
+                                 : hq < k2_30 && s.n < ((int64_t)1 << 31) &&
+                                       (double)cdiv(s.len, (int64_t)c.wave_rows) * (double)s.n * (double)hq < 2147483648.0 &&
+                                       (double)s.rows * (double)s.lse_seqs() * (double)hq < 4.0 * 2147483648.0;   // the delta launch
+  GMLM_REQUIRE(s.len < k2_30 && fits, "%s: too many work items", who);
   x = Params{};
   attn_fill(x.a, q, k, v, s.kv_len, s.n, hq, s.rows, s.rows, q_stride, k_stride, v_stride, scale, 0.f, 0, nullptr);
   x.a.cu = s.cu;
@@ -127,7 +141,7 @@ inline int fwd(const Family& f, const char* who, const Seqs& s, const void* q, c
                int64_t d, int64_t q_stride, int64_t k_stride, int64_t v_stride, float scale, float dropout_p, void* out, void* out_lo,
                float* lse, int dtype, gmlm_stream_t stream) {
   Params x;
-  int rc = setup(f, who, x, s, q, k, v, hq, hkv, d, q_stride, k_stride, v_stride, scale, dropout_p, out_lo, dtype);
+  int rc = setup(f.c, f.takes(d), who, x, s, q, k, v, hq, hkv, d, q_stride, k_stride, v_stride, scale, dropout_p, out_lo, dtype);
   if (rc != GMLM_OK) return rc;
   if (s.empty()) return GMLM_OK;
   x.a.o_w = out; x.a.o_lo_w = out_lo; x.a.lse_w = lse;
@@ -142,7 +156,7 @@ inline int bwd(const Family& f, const char* who, const Seqs& s, const void* q, c
                int64_t k_stride, int64_t v_stride, float scale, float dropout_p, void* dq, void* dk, void* dv, int64_t dq_stride,
                int64_t dk_stride, int64_t dv_stride, int dtype, void* workspace, size_t workspace_bytes, gmlm_stream_t stream) {
   Params x;
-  int rc = setup(f, who, x, s, q, k, v, hq, hkv, d, q_stride, k_stride, v_stride, scale, dropout_p, out_lo, dtype);
+  int rc = setup(f.c, f.takes(d), who, x, s, q, k, v, hq, hkv, d, q_stride, k_stride, v_stride, scale, dropout_p, out_lo, dtype);
   if (rc != GMLM_OK) return rc;
   if (s.empty()) return GMLM_OK;
   attn_fill_bwd(x.a, out, out_lo, dout, lse, dq, dk, dv, dq_stride, dk_stride, dv_stride, workspace);

@@ -218,6 +218,32 @@ def test_repeated_call_gives_identical_bytes(dev, causal, dtype):
                            y.view(torch.int16 if y.element_size() == 2 else torch.int32)), name
 
 
+@pytest.mark.parametrize("dtype", DTYPES, ids=("fp32", "bf16"))
+def test_group_of_one_bidirectional_padded_is_the_plain_body(dev, dtype):
+    """gqaw:: and wide:: are one body (csrc/attn_wide.hpp).  With one query head per KV head, no causal mask, the padded layout
+    and p = 0, what GROUPED adds is h / 1, a group loop of one turn and an early return no tile takes: the same expressions in
+    the same order as wide:: at d = 256, so ``ops.gqa_d256_attention`` and ``ops.Attention`` give the same bytes on the same
+    contiguous q, k, v, dO.  L = 31, 33, 65 (one short of and one past a tile, two tiles and a row); per L three sequences with
+    kv_len L, 1 and 0."""
+    from gmlm_amd import ops
+    h = 2
+    for L in (31, 33, 65):
+        g = torch.Generator().manual_seed(900 + L)
+        q, k, v, go = (torch.randn(3, L, h * D, generator=g).to(dev, dtype) for _ in range(4))
+        kv_len = torch.tensor([L, 1, 0], dtype=torch.int32, device=dev)
+        got = []
+        for fwd in (lambda a, b_, c: ops.gqa_d256_attention(a, b_, c, kv_len, h, h, SCALE, False),
+                    lambda a, b_, c: ops.Attention.apply(a, b_, c, kv_len, h, SCALE, 0.0, 0)):
+            qd, kd, vd = (t.clone().requires_grad_(True) for t in (q, k, v))
+            out = fwd(qd, kd, vd)
+            lse = out.grad_fn.saved_tensors[4]
+            out.backward(go)
+            got.append((out.detach(), lse, qd.grad, kd.grad, vd.grad))
+        assert float(got[0][0][0].abs().max()) > 0 and float(got[0][3][0].abs().max()) > 0
+        for name, a, b_ in zip(("out", "lse", "dq", "dk", "dv"), *got):
+            assert torch.equal(a, b_), (L, name, float((a.double() - b_.double()).abs().max()))
+
+
 def test_every_column_slice_reaches_the_scores_exactly_once(dev):
     """fp32, 4 / 2 heads.  q is non-zero only in the columns of wave 1 of every head and k only in those of wave 2: every score is
     exactly 0, so a bidirectional output row is the mean of v, and dq is exactly zero wherever k is, dk wherever q is.  A partial

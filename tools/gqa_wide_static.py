@@ -1,6 +1,6 @@
 """Static figures of the Gemma3 kernels (csrc/attn_gqa_wide.hip, csrc/gemma_kernels.hip) from the compiler's own resource-usage
-remarks: compiles the two files with the Makefile's flags plus ``-Rpass-analysis=kernel-resource-usage`` (objects go to a
-temporary directory) and writes profiles/gqa_wide_static.json.  Needs hipcc, no GPU.
+remarks: compiles the two files with the Makefile's flags (the ones it adds for a single object included) plus
+``-Rpass-analysis=kernel-resource-usage`` (objects go to a temporary directory) and writes profiles/gqa_wide_static.json.  Needs hipcc, no GPU.
 
     python tools/gqa_wide_static.py
 """
@@ -17,14 +17,18 @@ FILES = ("attn_gqa_wide.hip", "gemma_kernels.hip")
 FIELDS = (("sgpr", "TotalSGPRs"), ("vgpr", "VGPRs"), ("agpr", "AGPRs"), ("scratch_bytes_per_lane", r"ScratchSize \[bytes/lane\]"),
           ("waves_per_simd", r"Occupancy \[waves/SIMD\]"), ("sgpr_spill", "SGPRs Spill"), ("vgpr_spill", "VGPRs Spill"),
           ("static_lds_bytes", r"LDS Size \[bytes/block\]"))
-# dynamic LDS is a launch argument the compiler does not see: Lds<T>::BYTES of attn_gqa_wide.hip = 2 tiles of 32 x (256 + pad)
+# dynamic LDS is a launch argument the compiler does not see: Lds<T, 256>::BYTES of attn_wide.hpp = 2 tiles of 32 x (256 + pad)
 # elements + the 16 KiB exchange area + 256 bytes of row constants
 DYNAMIC_LDS = {"unsigned short": 2 * 32 * (256 + 8) * 2 + 16384 + 256, "float": 2 * 32 * (256 + 4) * 4 + 16384 + 256}
 
 
-def _flags():
+def _flags(src):
     mk = open(os.path.join(CSRC, "Makefile")).read()
     flags = re.search(r"^CXXFLAGS\s*=(.*)$", mk, re.M).group(1).split()
+    obj = "$(BUILD)/" + src[:-len(".hip")] + ".o"
+    for targets, extra in re.findall(r"^(\$\(BUILD\)/.*?):\s*CXXFLAGS\s*\+=(.*)$", mk, re.M):
+        if obj in targets.split():
+            flags += extra.split()
     return [f.replace("$(ARCH)", "gfx950") for f in flags]
 
 
@@ -34,7 +38,7 @@ def main():
     rows = []
     with tempfile.TemporaryDirectory() as tmp:
         for src in FILES:
-            err = subprocess.run([hipcc, *_flags(), "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", os.path.join(tmp, src + ".o")],
+            err = subprocess.run([hipcc, *_flags(src), "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", os.path.join(tmp, src + ".o")],
                                  cwd=CSRC, check=True, capture_output=True, text=True).stderr
             for block in re.split(r"remark: Function Name: ", err)[1:]:
                 mangled = block.split()[0]
@@ -51,7 +55,7 @@ def main():
     rows.sort(key=lambda r: r["kernel"])
     out = {"what": "registers, LDS and scratch of every kernel of attn_gqa_wide.hip and gemma_kernels.hip as hipcc's "
                    "-Rpass-analysis=kernel-resource-usage remarks report them (the Makefile's flags, gfx950); dynamic_lds_bytes is "
-                   "the launch argument Lds<T>::BYTES",
+                   "the launch argument Lds<T, 256>::BYTES",
            "kernels": rows,
            "max_scratch_bytes_per_lane": max(r["scratch_bytes_per_lane"] for r in rows),
            "max_vgpr_spill": max(r["vgpr_spill"] for r in rows)}
