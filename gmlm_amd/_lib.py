@@ -1,5 +1,5 @@
 """ctypes binding of libgmlm_hip.so (C ABI: include/gmlm_hip.h, gmlm_hip_split.h, gmlm_hip_optim.h, gmlm_hip_d32.h,
-gmlm_hip_wide.h, gmlm_hip_modernbert.h, gmlm_hip_relbias.h, gmlm_hip_disent.h, gmlm_hip_gqa.h, gmlm_hip_bidir.h, gmlm_hip_gqa_short.h, gmlm_hip_d32_short.h and gmlm_hip_gqa_wide.h): one signature table per header, positional argument types only.  Which attention entry point a head dim
+gmlm_hip_wide.h, gmlm_hip_modernbert.h, gmlm_hip_relbias.h, gmlm_hip_disent.h, gmlm_hip_gqa.h, gmlm_hip_bidir.h, gmlm_hip_gqa_short.h, gmlm_hip_d32_short.h, gmlm_hip_gqa_wide.h and gmlm_hip_gqa_band.h): one signature table per header, positional argument types only.  Which attention entry point a head dim
 takes, and where each ABI puts its arguments by name, is the family table of ops.py (``_ATTN_FAMILIES``).
 
 The product path has NO fallback: if the shared library is missing or a call fails, a Python
@@ -230,8 +230,22 @@ SIGNATURES_GQA_WIDE = {
     "gmlm_geglu_tanh_bwd": (C.c_int, [_p, _p, _i64, _i64, _p, _i32, _p]),
 }
 
+# fourteenth header, include/gmlm_hip_gqa_band.h (band-limited form of the grouped-KV attention at head dim 256: the sliding layers
+# of a Gemma3 encoder past the window).  The argument lists of the gmlm_attention_gqa_d256_* namesakes with `window` (int64_t) after
+# `causal`; the workspace queries are the namesakes'
+_GQAB_FWD = (C.c_int, [_p, _p, _p, _p] + [_i64] * 9 + [_f32, _f32, _i32, _i64, _p, _p, _p, _i32, _p])
+_GQAB_BWD = (C.c_int, [_p] * 8 + [_i64] * 9 + [_f32, _f32, _i32, _i64, _p, _p, _p, _i64, _i64, _i64, _i32, _p, _sz, _p])
+SIGNATURES_GQA_BAND = {
+    "gmlm_attention_gqa_d256_band_fwd": _GQAB_FWD,
+    "gmlm_attention_gqa_d256_band_bwd_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "gmlm_attention_gqa_d256_band_bwd": _GQAB_BWD,
+    "gmlm_attention_gqa_d256_band_varlen_fwd": _GQAB_FWD,
+    "gmlm_attention_gqa_d256_band_varlen_bwd_workspace_bytes": (_sz, [_i64, _i64]),
+    "gmlm_attention_gqa_d256_band_varlen_bwd": _GQAB_BWD,
+}
+
 SIGNATURE_TABLES_LATER = (SIGNATURES_RELBIAS, SIGNATURES_GQA, SIGNATURES_BIDIR, SIGNATURES_GQA_SHORT, SIGNATURES_D32_SHORT,
-                          SIGNATURES_GQA_WIDE, SIGNATURES_DISENT)
+                          SIGNATURES_GQA_WIDE, SIGNATURES_GQA_BAND, SIGNATURES_DISENT)
 
 
 class GmlmHipError(RuntimeError):

@@ -30,6 +30,7 @@
 //    the query tiles (causal: from the diagonal on), accumulating into the same registers.  No atomics, no expanded K / V or
 //    dK / dV in HBM.
 #pragma once
+#include <optional>
 #include "attn_stream.hpp"
 #include "attn_causal_dkv.hpp"
 #include "attn_host.hpp"
@@ -82,10 +83,11 @@ inline Seqs padded(const int32_t* kv_len, int64_t b, int64_t lq, int64_t lk) { r
 inline Seqs packed(const int32_t* cu, int64_t seqs, int64_t max_len, int64_t rows) { return {nullptr, cu, seqs, max_len, max_len, rows, true}; }
 
 // the checks of attn_host.hpp up to the empty-problem return, with the family's words and grids; d_ok = the family takes head
-// dim d; fills the launch parameters
+// dim d; fills the launch parameters.  `window` (given by attn_gqa_band.hip alone): the band width of the call, refused outside [1, 2^30)
+// right after the scale check; it is not stored here
 inline int setup(const Contract& c, bool d_ok, const char* who, Params& x, const Seqs& s, const void* q, const void* k, const void* v,
                  int64_t hq, int64_t hkv, int64_t d, int64_t q_stride, int64_t k_stride, int64_t v_stride, float scale, float dropout_p,
-                 const void* out_lo, int dtype) {
+                 const void* out_lo, int dtype, std::optional<int64_t> window = std::nullopt) {
   constexpr int64_t k2_30 = (int64_t)1 << 30;
   if (s.packed) {
     GMLM_REQUIRE(s.cu, "%s: null cu_seqlens", who);
@@ -98,6 +100,7 @@ inline int setup(const Contract& c, bool d_ok, const char* who, Params& x, const
   GMLM_REQUIRE(s.len == s.lk, "%s: %s needs lq == lk (got %ld and %ld)", who, c.self, (long)s.len, (long)s.lk);
   GMLM_REQUIRE(hq % hkv == 0, "%s: %ld query heads are not a multiple of %ld KV heads", who, (long)hq, (long)hkv);
   if ((rc = attn_check_rates(who, dropout_p, c.no_dropout, scale)) != GMLM_OK) return rc;
+  if (window.has_value()) GMLM_REQUIRE(*window >= 1 && *window < k2_30, "%s: window %ld must be in [1, 2^30)", who, (long)*window);
   const bool fits = !c.wave_rows ? cdiv(s.len, BQ) * s.n * hq < ((int64_t)1 << 31)
                                  : hq < k2_30 && s.n < ((int64_t)1 << 31) &&
                                        (double)cdiv(s.len, (int64_t)c.wave_rows) * (double)s.n * (double)hq < 2147483648.0 &&

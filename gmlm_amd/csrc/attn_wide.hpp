@@ -30,7 +30,17 @@
 //  * CAUSAL: query tiles and key tiles are both 32 rows, so tile t of the keys is the diagonal tile of query tile t.  The key
 //    loop of the forward and of dQ ends at the diagonal, the query loop of dK/dV starts there; tiles off the diagonal take the
 //    compare-free path, the diagonal one compares key <= query per element.  Key kv0 of a tile that is computed is valid for
-//    each of the 32 queries (kv0 <= 32 t <= query, kv0 < kv_len), so the running max stays finite.
+//    each of the 32 queries (kv0 <= 32 t <= query, kv0 < kv_len), so the running max stays finite;
+//  * BAND (attn_gqa_band.hip, gqab::*; only with GROUPED): query i sees key j iff j < kv_len and 0 <= i - j < w (CAUSAL) or
+//    |i - j| < w, w = `window` >= 1, an argument of the bodies that the other kernels leave at 0.  The key loop of the forward
+//    and of dQ and the query loop of dK/dV cover the tiles the band of the 32 rows touches (key_range / query_range, block-
+//    uniform); a tile that lies whole inside the band of every row and below kv_len keeps the compare-free path, every other
+//    one applies the rule per element.  The sentence above no longer holds: with w < 32 a row can see no key in the first tile of
+//    its loop, and a padded query at or past kv_len + w - 1 sees none at all.  The forward keeps such a row's running max at
+//    -inf without forming -inf - -inf (the guards of attn_stream.hpp's WINDOW flag) and a row that never sees a key gets
+//    output 0 and lse = -inf; both backward kernels read lse = -inf as "probability 0 everywhere", so its dQ is 0 and it adds
+//    nothing to dK / dV.  A finite value is never changed by a guard: with w >= l the bytes are those of the kernels without
+//    the flag.
 #pragma once
 #include <type_traits>
 #include "attn_grouped.hpp"
@@ -52,8 +62,9 @@ template <typename T, int D> struct Lds {
 };
 
 // the instantiations that exist: the grouped family has no dropout and one head dim, the plain one no causal mask
-template <int D, bool DROP, bool CAUSAL, bool GROUPED> constexpr bool kSupported =
-    (D == 256 || D == 384 || D == 512) && (GROUPED ? !DROP && D == 256 : !CAUSAL);
+// (and the band only in the grouped one)
+template <int D, bool DROP, bool CAUSAL, bool GROUPED, bool BAND = false> constexpr bool kSupported =
+    (D == 256 || D == 384 || D == 512) && (GROUPED ? !DROP && D == 256 : !CAUSAL) && (!BAND || (GROUPED && D == 256));
 
 // s <- ((s_w0 + s_w1) + s_w2) + s_w3, the same expression in every wave.  Two barriers: partials visible / area free again.
 __device__ __forceinline__ void exchange(float* xs, f32x16& s, int w, int lane) {
@@ -73,10 +84,36 @@ __device__ __forceinline__ int key_tiles(int64_t kvlen, int64_t tile) {
   return (int)(CAUSAL && tile + 1 < n ? tile + 1 : n);
 }
 
+// BAND: the band rule between a query and a key of one sequence (the caller adds key < kv_len)
+template <bool CAUSAL, typename I>
+__device__ __forceinline__ bool band_sees(I q, I key, I window) {
+  return CAUSAL ? key <= q && q - key < window : q - key < window && key - q < window;
+}
+
+// BAND: rows [a0, a0 + 32) and [b0, b0 + 32) of the two operands see each other pair by pair (a = query tile, b = key tile)
+template <bool CAUSAL>
+__device__ __forceinline__ bool band_whole(int64_t q0, int64_t kv0, int64_t window) {
+  return kv0 + (window - 1) >= q0 + R - 1 && (CAUSAL ? kv0 < q0 : kv0 + KT - 1 <= q0 + (window - 1));
+}
+
+// key tiles [t0, t1) of query tile `tile`; BAND: from the tile of key 32 tile - (w - 1) to the diagonal tile (CAUSAL) or the
+// tile of key 32 tile + 31 + (w - 1), cut to kv_len; t0 >= t1: the rows see no key
+template <bool CAUSAL, bool BAND>
+__device__ __forceinline__ void key_range(int64_t kvlen, int64_t tile, int64_t window, int& t0, int& t1) {
+  t0 = 0;
+  t1 = key_tiles<CAUSAL>(kvlen, tile);
+  if constexpr (BAND) {
+    const int64_t n = (kvlen + KT - 1) / KT, lo = tile * R - (window - 1);
+    const int64_t hi = CAUSAL ? tile + 1 : (tile * R + R - 1 + (window - 1)) / KT + 1;
+    t0 = (int)((lo > 0 ? lo : 0) / KT);
+    t1 = (int)(hi < n ? hi : n);
+  }
+}
+
 // forward: workgroup = 32 query rows of one (sequence, query head), loop over the key tiles of its KV head
-template <typename T, int D, bool DROP, bool CAUSAL, bool GROUPED>
-__device__ __forceinline__ void fwd_body(const Params& x, const Item& it) {
-  static_assert(kSupported<D, DROP, CAUSAL, GROUPED>, "no kernel of either family has this combination");
+template <typename T, int D, bool DROP, bool CAUSAL, bool GROUPED, bool BAND = false>
+__device__ __forceinline__ void fwd_body(const Params& x, const Item& it, int64_t window = 0) {
+  static_assert(kSupported<D, DROP, CAUSAL, GROUPED, BAND>, "no kernel of either family has this combination");
   const AttnParams& p = x.a;
   constexpr int DS = D / NW, PITCH = Lds<T, D>::PITCH, DB = DS / 32;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_wide[];
@@ -108,8 +145,9 @@ __device__ __forceinline__ void fwd_body(const Params& x, const Item& it) {
   const float sl2 = p.scale * kLog2e;
   const uint32_t dq_u = drop_base(attn_seed(p), lse_base) + (uint32_t)(q_row >> 1) * kDropC1 + (uint32_t)(2 * h) * kDropC2;
   const int q_odd = (int)(q_row & 1);
-  const int ntiles = key_tiles<CAUSAL>(kvlen, it.tile);
-  for (int t = 0; t < ntiles; ++t) {
+  int t0, ntiles;
+  key_range<CAUSAL, BAND>(kvlen, it.tile, window, t0, ntiles);
+  for (int t = t0; t < ntiles; ++t) {
     const int64_t kv0 = (int64_t)t * KT;
     stage_rows<T, D, KT, NT>(ks, kg, p.k_stride, kv0, lk_, tid);
     stage_rows<T, D, KT, NT>(vs, vg, p.v_stride, kv0, lk_, tid);
@@ -120,29 +158,41 @@ __device__ __forceinline__ void fwd_body(const Params& x, const Item& it) {
     mma_rows<DS>(ks + w * DS, PITCH, 0, qf, s, r, h);
     exchange(xs, s, w, lane);
     float rmax = -INFINITY;
-    if (kv0 + KT <= kvlen && !(CAUSAL && t == it.tile)) {           // whole tile valid (block-uniform): no per-key compare
+    // whole tile valid (block-uniform): no per-key compare.  (BAND is a constant: the conditional is folded where it stands, and
+    // the branches of the kernels without the flag stay as they were; a bool formed first changes the causal forward's code)
+    if (kv0 + KT <= kvlen && (BAND ? band_whole<CAUSAL>(it.tile * R, kv0, window) : !(CAUSAL && t == it.tile))) {
 #pragma unroll
       for (int i = 0; i < 16; ++i) rmax = fmaxf(rmax, s[i]);
     } else {
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
         const int64_t key = kv0 + acc_row(i, h);
-        const float v = key < kvlen && (!CAUSAL || key <= q_row) ? s[i] : -INFINITY;
+        const float v = key < kvlen && (BAND ? band_sees<CAUSAL>(q_row, key, window) : !CAUSAL || key <= q_row) ? s[i] : -INFINITY;
         s[i] = v;
         rmax = fmaxf(rmax, v);
       }
     }
     rmax = xhalf_max(rmax);
-    float m_new = fmaxf(m, rmax * sl2);             // finite: key kv0 is valid for every row of the tile
-    const bool keep = __all(m_new - m <= kDefer);   // identical in the four waves (identical scores); m = -inf -> false
-    float alpha = 1.f;
-    if (keep) m_new = m;
-    else alpha = fast_exp2(m - m_new);
+    float m_new = fmaxf(m, rmax * sl2);             // finite: key kv0 is valid for every row of the tile (BAND: -inf while the row has seen no key)
+    bool keep;                                      // identical in the four waves (identical scores); m = -inf -> false
+    float alpha = 1.f, m_ref;                       // m_ref: the exponent reference
+    if constexpr (BAND) {
+      // a row still at -inf that stays there changes nothing: -inf - -inf would be NaN and end the deferral for the wave
+      keep = __all(m_new == -INFINITY || m_new - m <= kDefer);
+      if (keep) m_new = m;
+      else alpha = m == -INFINITY ? 0.f : fast_exp2(m - m_new);   // also when m_new = -inf
+      m_ref = m_new == -INFINITY ? 0.f : m_new;                   // exp2(-inf - 0) = 0 for a row with no key yet
+    } else {
+      keep = __all(m_new - m <= kDefer);
+      if (keep) m_new = m;
+      else alpha = fast_exp2(m - m_new);
+      m_ref = m_new;
+    }
     float rsum = 0.f;
 #pragma unroll
     for (int i = 0; i < 16; i += 2) {
-      const float e0 = fast_exp2(fmaf(s[i], sl2, -m_new));        // masked: exp2(-inf) = 0
-      const float e1 = fast_exp2(fmaf(s[i + 1], sl2, -m_new));
+      const float e0 = fast_exp2(fmaf(s[i], sl2, -m_ref));        // masked: exp2(-inf) = 0
+      const float e1 = fast_exp2(fmaf(s[i + 1], sl2, -m_ref));
       rsum += e0 + e1;                                            // the normaliser uses the un-dropped probabilities
       if constexpr (DROP) {
         float m0, m1;
@@ -217,9 +267,9 @@ __device__ __forceinline__ void delta_body(const T* __restrict__ o, const T* __r
 // backward: dQ.  workgroup = 32 queries of one (sequence, query head), loop over the key tiles of its KV head.
 //   S^T = K Q^T and dP^T = V dO^T as sums of four partials, P^T = exp(scale * S^T - lse[q]), dS^T = P^T * (dP^T - delta[q]),
 //   dQ_w^T += K_w^T dS^T  (query on the lane)
-template <typename T, int D, bool DROP, bool CAUSAL, bool GROUPED>
-__device__ __forceinline__ void dq_body(const Params& x, const Item& it) {
-  static_assert(kSupported<D, DROP, CAUSAL, GROUPED>, "no kernel of either family has this combination");
+template <typename T, int D, bool DROP, bool CAUSAL, bool GROUPED, bool BAND = false>
+__device__ __forceinline__ void dq_body(const Params& x, const Item& it, int64_t window = 0) {
+  static_assert(kSupported<D, DROP, CAUSAL, GROUPED, BAND>, "no kernel of either family has this combination");
   const AttnParams& p = x.a;
   constexpr int DS = D / NW, PITCH = Lds<T, D>::PITCH, DB = DS / 32;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_wide[];
@@ -245,7 +295,10 @@ __device__ __forceinline__ void dq_body(const Params& x, const Item& it) {
   qf.load(static_cast<const T*>(p.q) + (qbase + qr) * p.q_stride + hd * D + w * DS, q_ok, h);
   dof.load(static_cast<const T*>(p.dout) + (qbase + qr) * x.dout_stride + hd * D + w * DS, q_ok, h);
   const float sl2 = p.scale * kLog2e;
-  const float lse2 = q_ok ? p.lse[lse_base + q_row] * kLog2e : INFINITY;   // a row past the sequence: probability 0 everywhere
+  float lse2 = q_ok ? p.lse[lse_base + q_row] * kLog2e : INFINITY;   // a row past the sequence: probability 0 everywhere
+  if constexpr (BAND) {
+    if (lse2 == -INFINITY) lse2 = INFINITY;                           // and a row that saw no key: never exp2(+inf)
+  }
   const float dl = q_ok ? p.delta[lse_base + q_row] : 0.f;
   const int kvl = (int)(kvlen < (1 << 30) ? kvlen : (1 << 30));
   const int qi = (int)(q_row < (1 << 30) ? q_row : (1 << 30));
@@ -256,8 +309,10 @@ __device__ __forceinline__ void dq_body(const Params& x, const Item& it) {
   for (int d = 0; d < DB; ++d)
 #pragma unroll
     for (int i = 0; i < 16; ++i) dq[d][i] = 0.f;
-  const int ntiles = key_tiles<CAUSAL>(kvlen, it.tile);
-  for (int t = 0; t < ntiles; ++t) {
+  const int wi = (int)window;
+  int t0, ntiles;
+  key_range<CAUSAL, BAND>(kvlen, it.tile, window, t0, ntiles);
+  for (int t = t0; t < ntiles; ++t) {
     const int64_t kv0 = (int64_t)t * KT;
     stage_rows<T, D, KT, NT>(ks, kg, p.k_stride, kv0, lk_, tid);
     stage_rows<T, D, KT, NT>(vs, vg, p.v_stride, kv0, lk_, tid);
@@ -269,14 +324,20 @@ __device__ __forceinline__ void dq_body(const Params& x, const Item& it) {
     exchange(xs, s, w, lane);
     mma_rows<DS>(vs + w * DS, PITCH, 0, dof, dp, r, h);
     exchange(xs, dp, w, lane);
-    const bool full = kv0 + KT <= kvlen && !(CAUSAL && t == it.tile);    // block-uniform
+    bool full = kv0 + KT <= kvlen && !(CAUSAL && t == it.tile);          // block-uniform
+    if constexpr (BAND) full = kv0 + KT <= kvlen && band_whole<CAUSAL>(it.tile * R, kv0, window);
 #pragma unroll
     for (int i = 0; i < 16; i += 2) {
       const int key = (int)kv0 + acc_row(i, h);                   // even; registers i, i+1 = keys key, key+1
       float a0 = fmaf(s[i], sl2, -lse2), a1 = fmaf(s[i + 1], sl2, -lse2);
       if (!full) {                                                // a masked pair has P = exp2(-inf) = 0 whatever its score
-        a0 = key < kvl && (!CAUSAL || key <= qi) ? a0 : -INFINITY;
-        a1 = key + 1 < kvl && (!CAUSAL || key + 1 <= qi) ? a1 : -INFINITY;
+        if constexpr (BAND) {
+          a0 = key < kvl && band_sees<CAUSAL>(qi, key, wi) ? a0 : -INFINITY;
+          a1 = key + 1 < kvl && band_sees<CAUSAL>(qi, key + 1, wi) ? a1 : -INFINITY;
+        } else {
+          a0 = key < kvl && (!CAUSAL || key <= qi) ? a0 : -INFINITY;
+          a1 = key + 1 < kvl && (!CAUSAL || key + 1 <= qi) ? a1 : -INFINITY;
+        }
       }
       const float p0 = fast_exp2(a0), p1 = fast_exp2(a1);
       float m0 = 1.f, m1 = 1.f;
@@ -294,15 +355,24 @@ __device__ __forceinline__ void dq_body(const Params& x, const Item& it) {
   }
 }
 
+// BAND: query tiles [t0, t1) of key tile `kt` in a sequence of l rows: from the diagonal tile (CAUSAL) or the tile of query
+// 32 kt - (w - 1) to the tile of query 32 kt + 31 + (w - 1)
+template <bool CAUSAL>
+__device__ __forceinline__ void query_range(int64_t l, int64_t kt, int64_t window, int& t0, int& t1) {
+  const int64_t n = (l + KT - 1) / KT, lo = kt * R - (window - 1), hi = (kt * R + R - 1 + (window - 1)) / KT + 1;
+  t0 = (int)(CAUSAL ? kt : (lo > 0 ? lo : 0) / KT);
+  t1 = (int)(hi < n ? hi : n);
+}
+
 // backward: dK, dV.  workgroup = 32 keys of one (sequence, KV head): key rows lk_ from kbase, query rows lq_ from qbase (the
 // plain family has lq != lk).  GROUPED: for each query head of the group, in order; per head the query tiles of 32 in order
 // (CAUSAL: from the diagonal tile on), all into the same registers (deterministic).
 //   S = Q K^T and dP = dO V^T as sums of four partials, P = exp(scale * S - lse[q]), dV_w^T += dO_w^T P,
 //   dS = P * (dP - delta[q]), dK_w^T += Q_w^T dS  (key on the lane, the query in the accumulator registers)
 // The work item is decode()'s for the plain family and causal_key_tile()'s for the grouped one.
-template <typename T, int D, bool DROP, bool CAUSAL, bool GROUPED>
-__device__ __forceinline__ void dkv_body(const Params& x, const std::conditional_t<GROUPED, CausalKeyTile, Item>& it) {
-  static_assert(kSupported<D, DROP, CAUSAL, GROUPED>, "no kernel of either family has this combination");
+template <typename T, int D, bool DROP, bool CAUSAL, bool GROUPED, bool BAND = false>
+__device__ __forceinline__ void dkv_body(const Params& x, const std::conditional_t<GROUPED, CausalKeyTile, Item>& it, int64_t window = 0) {
+  static_assert(kSupported<D, DROP, CAUSAL, GROUPED, BAND>, "no kernel of either family has this combination");
   const AttnParams& p = x.a;
   constexpr int DS = D / NW, PITCH = Lds<T, D>::PITCH, DB = DS / 32, QT = KT;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_wide[];
@@ -343,7 +413,9 @@ __device__ __forceinline__ void dkv_body(const Params& x, const std::conditional
 #pragma unroll
     for (int i = 0; i < 16; ++i) { dk[d][i] = 0.f; dv[d][i] = 0.f; }
   if (tile * R < kvlen) {                  // a whole workgroup past kv_len has nothing to accumulate (block-uniform)
-    const int t0 = CAUSAL ? (int)tile : 0, ntiles = (int)((lq_ + QT - 1) / QT);
+    int t0 = CAUSAL ? (int)tile : 0, ntiles = (int)((lq_ + QT - 1) / QT);
+    if constexpr (BAND) query_range<CAUSAL>(lq_, tile, window, t0, ntiles);
+    const int wi = (int)window;
     int heads = 1;
     if constexpr (GROUPED) heads = x.group;
     for (int g = 0; g < heads; ++g) {
@@ -361,7 +433,11 @@ __device__ __forceinline__ void dkv_body(const Params& x, const std::conditional
         stage_rows<T, D, QT, NT>(dos, dog, x.dout_stride, q0, lq_, tid);
         if (tid < QT) {
           const bool ok = q0 + tid < lq_;
-          lse_s[tid] = ok ? lse_g[q0 + tid] * kLog2e : INFINITY;   // +inf: probability 0 for a row past the sequence
+          float lv = ok ? lse_g[q0 + tid] * kLog2e : INFINITY;     // +inf: probability 0 for a row past the sequence
+          if constexpr (BAND) {
+            if (lv == -INFINITY) lv = INFINITY;                     // and for a row that saw no key: never exp2(+inf)
+          }
+          lse_s[tid] = lv;
           dl_s[tid] = ok ? dl_g[q0 + tid] : 0.f;
         }
         __syncthreads();
@@ -373,6 +449,8 @@ __device__ __forceinline__ void dkv_body(const Params& x, const std::conditional
         mma_rows<DS>(dos + w * DS, PITCH, 0, vf, dp, r, h);
         exchange(xs, dp, w, lane);
         const bool diag = CAUSAL && t == t0;                        // block-uniform
+        bool inside = false;                                        // BAND: every pair of the tile is in the band (block-uniform)
+        if constexpr (BAND) inside = band_whole<CAUSAL>(q0, tile * R, window);
 #pragma unroll
         for (int g4 = 0; g4 < 4; ++g4) {
           const int q4 = 8 * g4 + 4 * h;                 // accumulator registers 4*g4 .. 4*g4+3 = queries q4 .. q4+3
@@ -388,7 +466,8 @@ __device__ __forceinline__ void dkv_body(const Params& x, const std::conditional
 #pragma unroll
           for (int j = 0; j < 4; ++j) {                  // one element at a time: formed in pairs, P and dS cost ~100 VGPRs
             const int i = 4 * g4 + j;
-            const bool on = key_ok && (!diag || (int)q0 + q4 + j >= ki);         // P = exp2(-inf) = 0 above the diagonal
+            bool on = key_ok && (!diag || (int)q0 + q4 + j >= ki);               // P = exp2(-inf) = 0 above the diagonal
+            if constexpr (BAND) on = key_ok && (inside || band_sees<CAUSAL>((int)q0 + q4 + j, ki, wi));
             const float pr = fast_exp2(on ? fmaf(s[i], sl2, -lv[j]) : -INFINITY);
             s[i] = pr * mk[j];
             dp[i] = pr * (dp[i] * mk[j] - dv4[j]);

@@ -14,9 +14,14 @@ norms with weight ``1 + w``.  Per layer, given (residual stream s, y = input nor
     final ``norm``).
 The first layer's input norm is ``ops.add_rmsnorm`` without a branch, fed ``1 + w``.  The rotary table is built per layer type
 (``sliding_attention``: local base frequency; ``full_attention``: global, rope types default and linear) from the model's own
-``rotary_emb``.  A sliding layer is accepted as long as no sequence of the call reaches past the window (``check_window``): there
-is no band kernel at this head dim.  Two layouts: padded (``gemma3_encode``) and packed / varlen (``gemma3_encode_packed``).
-There is no hipGraph, bucketed, short-sequence or ring form of this encoder (DESIGN.md section 4 "Gemma3 encoder").
+``rotary_emb``.  Sliding layers: by default (``band=False``) a call is accepted as long as no sequence reaches past the window
+(``check_window``; the message still says what this default path lacks).  With ``band=True`` a call whose longest sequence exceeds
+``config.sliding_window`` runs its sliding layers on the band-limited kernels (``ops.rope_gqa_d256(..., window=sliding_window)``,
+gmlm_attention_gqa_d256_band_*: query i sees key j iff |i - j| < window, causal 0 <= i - j < window, HF's exclusive window); its
+full layers, and every layer of a call that fits under the window, run the kernels of the default path, so a short batch
+launches exactly the same kernel set either way.  Two layouts: padded (``gemma3_encode``) and packed / varlen
+(``gemma3_encode_packed``).  There is no hipGraph, bucketed, short-sequence or ring form of this encoder (DESIGN.md section 4
+"Gemma3 encoder").
 """
 from __future__ import annotations
 
@@ -90,6 +95,16 @@ def check_window(cfg, longest: int) -> None:
         raise ValueError(f"sequence length {int(longest)} exceeds sliding_window {int(w)}: there is no band kernel at head dim 256")
 
 
+def band_window(cfg, longest: int, band: bool) -> int:
+    """The ``window`` of the call's sliding layers: ``config.sliding_window`` when ``band`` is set and the longest sequence
+    exceeds it, else 0 (the kernels without a band; ``band`` False: after ``check_window``)."""
+    if not band:
+        check_window(cfg, longest)
+        return 0
+    w = getattr(cfg, "sliding_window", None)
+    return int(w) if w and "sliding_attention" in _layer_types(cfg) and int(longest) > int(w) else 0
+
+
 _TABLES = weakref.WeakKeyDictionary()      # rotary module -> {(layer type, device type, index): table}
 
 
@@ -150,15 +165,17 @@ def prepare_weights(plm, cd, gemm_precision="native"):
     return out
 
 
-def _layer(lw, stream, y, lens, tables, hq, hkv, scale, causal, eps, packed=None):
+def _layer(lw, stream, y, lens, tables, hq, hkv, scale, causal, eps, window, packed=None):
     """(residual stream, its input norm) -> the same pair for the next layer (after the last: the model's output is the second).
-    ``packed`` = (pos_ids, cu_seqlens, max_len): the rows are [T, .] packed sequences."""
+    ``window``: 0, or the band of the sliding layers.  ``packed`` = (pos_ids, cu_seqlens, max_len): the rows are [T, .] packed
+    sequences."""
     cs = tables[lw.layer_type]
     qkv = _mm(y, lw.wqkv, None, lw.m_qkv)
+    w = window if lw.layer_type == "sliding_attention" else 0
     if packed is not None:
-        ctx = ops.rope_gqa_d256_varlen(qkv, lw.qn, lw.kn, cs, *packed, hq, hkv, scale, causal, W_OFFSET, eps)
+        ctx = ops.rope_gqa_d256_varlen(qkv, lw.qn, lw.kn, cs, *packed, hq, hkv, scale, causal, W_OFFSET, eps, window=w)
     else:
-        ctx = ops.rope_gqa_d256(qkv, lw.qn, lw.kn, cs, lens, hq, hkv, scale, causal, W_OFFSET, eps)
+        ctx = ops.rope_gqa_d256(qkv, lw.qn, lw.kn, cs, lens, hq, hkv, scale, causal, W_OFFSET, eps, window=w)
     s1, y1 = ops.sandwich_rmsnorm(stream, _mm(ctx, lw.wo, None, lw.m_wo), lw.ln_post_attn, lw.ln_pre_ff, W_OFFSET, eps)
     m = ops.geglu_tanh(_mm(y1, lw.wgu, None, lw.m_gu))
     return ops.sandwich_rmsnorm(s1, _mm(m, lw.wdown, None, lw.m_down), lw.ln_post_ff, lw.ln_next, W_OFFSET, eps)
@@ -172,7 +189,7 @@ def _embed(plm, ids, cd):
     return (x * emb.embed_scale.to(device=x.device, dtype=emb.weight.dtype)).to(cd)
 
 
-def _encode_rows(plm, x, lens, tables, cd, training, gradient_checkpointing, weights, *packed):
+def _encode_rows(plm, x, lens, tables, cd, training, gradient_checkpointing, weights, window, *packed):
     cfg = plm.config
     hq, hkv = cfg.num_attention_heads, cfg.num_key_value_heads
     eps, scale = cfg.rms_norm_eps, float(cfg.query_pre_attn_scalar) ** -0.5
@@ -182,33 +199,37 @@ def _encode_rows(plm, x, lens, tables, cd, training, gradient_checkpointing, wei
     if not weights:
         return ops.add_rmsnorm(x, None, W_OFFSET + plm.norm.weight, eps)[1]
     y = ops.add_rmsnorm(x, None, W_OFFSET + plm.layers[0].input_layernorm.weight, eps)[1]   # the one norm without a branch before it
-    return encoder.run_layers(_layer, weights, (x, y), (lens, tables, hq, hkv, scale, causal, eps, *packed), training,
+    return encoder.run_layers(_layer, weights, (x, y), (lens, tables, hq, hkv, scale, causal, eps, window, *packed), training,
                               gradient_checkpointing)[1]
 
 
 def gemma3_encode(plm, input_ids: torch.Tensor, lens: torch.Tensor, cd: torch.dtype, training: bool = False,
-                  gradient_checkpointing: bool = False, weights=None) -> torch.Tensor:
+                  gradient_checkpointing: bool = False, weights=None, band: bool = False) -> torch.Tensor:
     """input_ids int [B, L] (left-aligned: padding anywhere past ``lens[b]`` is ignored), lens int32 [B] -> [B, L, P] in ``cd``.
 
     Positions are 0..L-1 per row; a query sees the keys below ``lens[b]`` (a causal model: those at or before it).  Rows at or
-    past ``lens[b]`` are computed but never read by the pooling.  ``weights``: optional ``prepare_weights(plm, cd)`` result."""
+    past ``lens[b]`` are computed but never read by the pooling.  ``weights``: optional ``prepare_weights(plm, cd)`` result.
+    ``band``: False refuses L > ``sliding_window``; True runs the sliding layers of such a call on the band-limited kernels (the
+    longest sequence of a padded call is its width L: no device value is read)."""
     cfg = plm.config
     b, l = input_ids.shape
     encoder.check_length(cfg, l)
-    check_window(cfg, l)
+    window = band_window(cfg, l, band)
     x = _embed(plm, input_ids, cd)
-    return _encode_rows(plm, x, lens, rope_tables(plm, l, x.device), cd, training, gradient_checkpointing, weights)
+    return _encode_rows(plm, x, lens, rope_tables(plm, l, x.device), cd, training, gradient_checkpointing, weights, window)
 
 
 def gemma3_encode_packed(plm, tok: torch.Tensor, pos: torch.Tensor, cu_seqlens: torch.Tensor, max_len: int, cd: torch.dtype,
-                         training: bool = False, gradient_checkpointing: bool = False, weights=None) -> torch.Tensor:
+                         training: bool = False, gradient_checkpointing: bool = False, weights=None, band: bool = False) -> torch.Tensor:
     """Packed (varlen) pass: tok / pos int [T] (token id and position of every row, the sequences back to back), cu_seqlens
-    int32 [S + 1] (sequence i = rows [cu[i], cu[i+1]), covering all T rows), max_len >= the longest sequence -> [T, P] in ``cd``."""
+    int32 [S + 1] (sequence i = rows [cu[i], cu[i+1]), covering all T rows), max_len >= the longest sequence -> [T, P] in ``cd``.
+    ``band`` as in ``gemma3_encode``, decided by ``max_len``."""
     cfg = plm.config
     max_len = int(max_len)
     encoder.check_length(cfg, max_len)
-    check_window(cfg, max_len)
+    window = band_window(cfg, max_len, band)
     encoder.check_packed(tok, pos)
     x = _embed(plm, tok, cd)
     tables = rope_tables(plm, max_len, x.device)
-    return _encode_rows(plm, x, None, tables, cd, training, gradient_checkpointing, weights, (pos.to(torch.int32), cu_seqlens, max_len))
+    return _encode_rows(plm, x, None, tables, cd, training, gradient_checkpointing, weights, window,
+                        (pos.to(torch.int32), cu_seqlens, max_len))

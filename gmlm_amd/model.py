@@ -181,6 +181,10 @@ class GraphTextLM(nn.Module):
         # pad every packed text batch to the static sizes of ``bucketed_layout`` (what a captured encoder replays; set it on an
         # eager model to run the very same padded batch without hipGraphs)
         self.plm_bucketed = False
+        # Gemma3 text encoders: run the sliding layers of a batch whose longest text exceeds config.sliding_window on the band-limited
+        # attention kernels (gemma3.py ``band``) instead of refusing it.  Off: existing callers see the refusal (DESIGN.md section 4
+        # "Gemma3 encoder")
+        self.plm_band_attention = False
         # variable-length token packing in the text encoder (head dim 32 / 64 / 96)
         self.active_index = None   # set by encode_texts: ascending device index of the active nodes of the last call
         self._graphs = GraphCache(capacity=4)
@@ -491,6 +495,8 @@ class GraphTextLM(nn.Module):
                             # grouped-KV encoders at head dim 64: the same groups (the dummy pad sequence included) put their
                             # attention on the short-sequence kernels of attn_gqa_short.hip (ops._gqa_short_path)
                             more["groups"] = to_dev(ops.pack_sequence_groups(lh.tolist() + ([pad] if pad else [])))
+                        if self._enc is gemma3:
+                            more["band"] = self.plm_band_attention
                         hs = encode(self.plm_encoder, tok, pos, cu_all, lmax, cd, self.plm_encoder.training,
                                     self.plm_gradient_checkpointing, weights, **more)
                         plm_embeds = ops.MeanPoolScatter.apply(plm_embeds, hs, None, bi, cu, total)
@@ -505,7 +511,8 @@ class GraphTextLM(nn.Module):
                 else:
                     ids = tokens.input_ids[bi, :lmax]
                     encode = getattr(self._enc, _ENCODERS[self._plm_kind][1])
-                    hs = encode(self.plm_encoder, ids, lens, cd, self.plm_encoder.training, self.plm_gradient_checkpointing, weights)
+                    more = {"band": self.plm_band_attention} if self._enc is gemma3 else {}
+                    hs = encode(self.plm_encoder, ids, lens, cd, self.plm_encoder.training, self.plm_gradient_checkpointing, weights, **more)
                     plm_embeds = ops.MeanPoolScatter.apply(plm_embeds, hs, lens, bi)
         return plm_embeds
 

@@ -1874,3 +1874,4 @@ def attention_disent_qkv_varlen(qkv, c2p, p2c, col, cu_seqlens, max_len, num_hea
 # at head dim 256; ``geglu_tanh`` is above, the plain attention nodes are CausalAttention / CausalAttentionVarlen with d = 256
 # ---------------------------------------------------------------------------------------------
 from .ops_gemma import gqa_d256_attention, gqa_d256_attention_varlen, rope_gqa_d256, rope_gqa_d256_varlen, sandwich_rmsnorm  # noqa: E402,F401
+from .ops_gemma import gqa_d256_band_attention, gqa_d256_band_attention_varlen  # noqa: E402,F401
