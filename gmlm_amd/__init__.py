@@ -6,6 +6,7 @@ Importing the package does not need a GPU; calling any operator does, and fails 
 from ._lib import GmlmHipError, LIB_PATH, lib  # noqa: F401
 from .dense import mm_bf16x3  # noqa: F401
 from .gemma3 import gemma3_encode, gemma3_encode_packed  # noqa: F401
+from .gemma2 import gemma2_encode, gemma2_encode_packed  # noqa: F401
 from .graph import GraphCache, RelCSR, build_rel_csr  # noqa: F401
 from .model import GraphTextLM, TokenizedTexts  # noqa: F401
 from .nn import CrossAttention, GraphNorm, MultiScaleFusion, RGCNConv, degree  # noqa: F401
@@ -19,4 +20,4 @@ _ops.mm_bf16x3 = mm_bf16x3
 
 __all__ = ["GraphTextLM", "TokenizedTexts", "RGCNConv", "GraphNorm", "CrossAttention", "MultiScaleFusion", "degree",
            "soft_masking_gnn_input", "edge_types_from_degree", "mm_bf16x3", "build_rel_csr", "GraphCache", "RelCSR", "lib",
-           "GmlmHipError", "LIB_PATH", "FusedAdamW", "gemma3_encode", "gemma3_encode_packed"]
+           "GmlmHipError", "LIB_PATH", "FusedAdamW", "gemma3_encode", "gemma3_encode_packed", "gemma2_encode", "gemma2_encode_packed"]

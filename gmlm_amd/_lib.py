@@ -1,5 +1,5 @@
 """ctypes binding of libgmlm_hip.so (C ABI: include/gmlm_hip.h, gmlm_hip_split.h, gmlm_hip_optim.h, gmlm_hip_d32.h,
-gmlm_hip_wide.h, gmlm_hip_modernbert.h, gmlm_hip_relbias.h, gmlm_hip_disent.h, gmlm_hip_gqa.h, gmlm_hip_bidir.h, gmlm_hip_gqa_short.h, gmlm_hip_d32_short.h, gmlm_hip_gqa_wide.h and gmlm_hip_gqa_band.h): one signature table per header, positional argument types only.  Which attention entry point a head dim
+gmlm_hip_wide.h, gmlm_hip_modernbert.h, gmlm_hip_relbias.h, gmlm_hip_disent.h, gmlm_hip_gqa.h, gmlm_hip_bidir.h, gmlm_hip_gqa_short.h, gmlm_hip_d32_short.h, gmlm_hip_gqa_wide.h, gmlm_hip_gqa_band.h and gmlm_hip_gqa_softcap.h): one signature table per header, positional argument types only.  Which attention entry point a head dim
 takes, and where each ABI puts its arguments by name, is the family table of ops.py (``_ATTN_FAMILIES``).
 
 The product path has NO fallback: if the shared library is missing or a call fails, a Python
@@ -244,8 +244,25 @@ SIGNATURES_GQA_BAND = {
     "gmlm_attention_gqa_d256_band_varlen_bwd": _GQAB_BWD,
 }
 
+# fifteenth header, include/gmlm_hip_gqa_softcap.h (Gemma2 text encoders: the grouped-KV attention at head dim 256 with attention-logit
+# soft-capping, with or without a band, and the rotary embedding on head rows at d = 256).  The argument lists of the
+# gmlm_attention_gqa_d256_band_* namesakes with `softcap` (float) after `window` (0 = no band); the rotary pair takes the lists of
+# gmlm_rope_heads_*
+_GQAC_FWD = (C.c_int, [_p, _p, _p, _p] + [_i64] * 9 + [_f32, _f32, _i32, _i64, _f32, _p, _p, _p, _i32, _p])
+_GQAC_BWD = (C.c_int, [_p] * 8 + [_i64] * 9 + [_f32, _f32, _i32, _i64, _f32, _p, _p, _p, _i64, _i64, _i64, _i32, _p, _sz, _p])
+SIGNATURES_GQA_SOFTCAP = {
+    "gmlm_attention_gqa_d256_softcap_fwd": _GQAC_FWD,
+    "gmlm_attention_gqa_d256_softcap_bwd_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "gmlm_attention_gqa_d256_softcap_bwd": _GQAC_BWD,
+    "gmlm_attention_gqa_d256_softcap_varlen_fwd": _GQAC_FWD,
+    "gmlm_attention_gqa_d256_softcap_varlen_bwd_workspace_bytes": (_sz, [_i64, _i64]),
+    "gmlm_attention_gqa_d256_softcap_varlen_bwd": _GQAC_BWD,
+    "gmlm_rope_heads_d256_fwd": SIGNATURES_GQA["gmlm_rope_heads_fwd"],
+    "gmlm_rope_heads_d256_bwd": SIGNATURES_GQA["gmlm_rope_heads_bwd"],
+}
+
 SIGNATURE_TABLES_LATER = (SIGNATURES_RELBIAS, SIGNATURES_GQA, SIGNATURES_BIDIR, SIGNATURES_GQA_SHORT, SIGNATURES_D32_SHORT,
-                          SIGNATURES_GQA_WIDE, SIGNATURES_GQA_BAND, SIGNATURES_DISENT)
+                          SIGNATURES_GQA_WIDE, SIGNATURES_GQA_BAND, SIGNATURES_GQA_SOFTCAP, SIGNATURES_DISENT)
 
 
 class GmlmHipError(RuntimeError):

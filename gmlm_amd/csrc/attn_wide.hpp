@@ -41,6 +41,12 @@
 //    output 0 and lse = -inf; both backward kernels read lse = -inf as "probability 0 everywhere", so its dQ is 0 and it adds
 //    nothing to dK / dV.  A finite value is never changed by a guard: with w >= l the bytes are those of the kernels without
 //    the flag.
+//  * SOFTCAP (attn_gqa_softcap.hip, gqac::*; only with GROUPED, with or without BAND): the scores enter the softmax as
+//    z = c tanh(score * scale / c), c = `softcap` > 0, the last argument of the bodies.  The forward replaces every score by z right
+//    after exchange() and BEFORE any mask select (tanh(-inf) = -1 is finite: a mask applied first would give a masked key the
+//    probability of a score of -c) and runs the rest of its loop on z with log2 e in place of scale * log2 e; lse is that of the
+//    capped scores.  dQ and dK/dV recompute z the same way and multiply dS by 1 - tanh^2 before it is rounded for the second
+//    product; the p.scale at their stores is the scale of dz/ds = scale (1 - tanh^2).  softcap_z() below says how tanh is formed.
 #pragma once
 #include <type_traits>
 #include "attn_grouped.hpp"
@@ -63,8 +69,21 @@ template <typename T, int D> struct Lds {
 
 // the instantiations that exist: the grouped family has no dropout and one head dim, the plain one no causal mask
 // (and the band only in the grouped one)
-template <int D, bool DROP, bool CAUSAL, bool GROUPED, bool BAND = false> constexpr bool kSupported =
-    (D == 256 || D == 384 || D == 512) && (GROUPED ? !DROP && D == 256 : !CAUSAL) && (!BAND || (GROUPED && D == 256));
+template <int D, bool DROP, bool CAUSAL, bool GROUPED, bool BAND = false, bool SOFTCAP = false> constexpr bool kSupported =
+    (D == 256 || D == 384 || D == 512) && (GROUPED ? !DROP && D == 256 : !CAUSAL) && (!BAND || (GROUPED && D == 256)) &&
+    (!SOFTCAP || (GROUPED && D == 256));
+
+// SOFTCAP: z = c tanh(x), x = score * scale / c (`k` = scale / c), and fac = 1 - tanh(x)^2 = dz / d(score * scale), both from ONE
+// exponential of -2|x| taken as em = expm1(-2|x|): tanh|x| = -em / (2 + em) and fac = 4 (1 + em) / (2 + em)^2.  The error is
+// relative to |z| (1 - exp(-2|x|) would leave an absolute c 2^-24 on every small score); a saturated score gives em = -1:
+// z = +-c and fac = 0 exactly; no finite score gives a NaN (2 + em >= 1).
+__device__ __forceinline__ float softcap_z(float s, float k, float c, float& fac) {
+  const float x = s * k;
+  const float em = expm1f(-2.f * fabsf(x));
+  const float r = __builtin_amdgcn_rcpf(2.f + em);
+  fac = 4.f * (1.f + em) * r * r;
+  return c * copysignf(-em * r, x);
+}
 
 // s <- ((s_w0 + s_w1) + s_w2) + s_w3, the same expression in every wave.  Two barriers: partials visible / area free again.
 __device__ __forceinline__ void exchange(float* xs, f32x16& s, int w, int lane) {
@@ -111,9 +130,9 @@ __device__ __forceinline__ void key_range(int64_t kvlen, int64_t tile, int64_t w
 }
 
 // forward: workgroup = 32 query rows of one (sequence, query head), loop over the key tiles of its KV head
-template <typename T, int D, bool DROP, bool CAUSAL, bool GROUPED, bool BAND = false>
-__device__ __forceinline__ void fwd_body(const Params& x, const Item& it, int64_t window = 0) {
-  static_assert(kSupported<D, DROP, CAUSAL, GROUPED, BAND>, "no kernel of either family has this combination");
+template <typename T, int D, bool DROP, bool CAUSAL, bool GROUPED, bool BAND = false, bool SOFTCAP = false>
+__device__ __forceinline__ void fwd_body(const Params& x, const Item& it, int64_t window = 0, float softcap = 0.f) {
+  static_assert(kSupported<D, DROP, CAUSAL, GROUPED, BAND, SOFTCAP>, "no kernel of either family has this combination");
   const AttnParams& p = x.a;
   constexpr int DS = D / NW, PITCH = Lds<T, D>::PITCH, DB = DS / 32;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_wide[];
@@ -142,7 +161,8 @@ __device__ __forceinline__ void fwd_body(const Params& x, const Item& it, int64_
 #pragma unroll
     for (int i = 0; i < 16; ++i) o[d][i] = 0.f;
   float m = -INFINITY, l = 0.f;              // running max / sum in the log2 domain (scores * scale * log2 e)
-  const float sl2 = p.scale * kLog2e;
+  const float sl2 = SOFTCAP ? kLog2e : p.scale * kLog2e;          // SOFTCAP: the capped scores carry the scale already
+  [[maybe_unused]] const float kcap = SOFTCAP ? p.scale / softcap : 0.f;
   const uint32_t dq_u = drop_base(attn_seed(p), lse_base) + (uint32_t)(q_row >> 1) * kDropC1 + (uint32_t)(2 * h) * kDropC2;
   const int q_odd = (int)(q_row & 1);
   int t0, ntiles;
@@ -157,6 +177,13 @@ __device__ __forceinline__ void fwd_body(const Params& x, const Item& it, int64_
     for (int i = 0; i < 16; ++i) s[i] = 0.f;
     mma_rows<DS>(ks + w * DS, PITCH, 0, qf, s, r, h);
     exchange(xs, s, w, lane);
+    if constexpr (SOFTCAP) {                                        // before any mask: tanh(-inf) = -1 would un-mask a key
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        float fac;
+        s[i] = softcap_z(s[i], kcap, softcap, fac);
+      }
+    }
     float rmax = -INFINITY;
     // whole tile valid (block-uniform): no per-key compare.  (BAND is a constant: the conditional is folded where it stands, and
     // the branches of the kernels without the flag stay as they were; a bool formed first changes the causal forward's code)
@@ -267,9 +294,9 @@ __device__ __forceinline__ void delta_body(const T* __restrict__ o, const T* __r
 // backward: dQ.  workgroup = 32 queries of one (sequence, query head), loop over the key tiles of its KV head.
 //   S^T = K Q^T and dP^T = V dO^T as sums of four partials, P^T = exp(scale * S^T - lse[q]), dS^T = P^T * (dP^T - delta[q]),
 //   dQ_w^T += K_w^T dS^T  (query on the lane)
-template <typename T, int D, bool DROP, bool CAUSAL, bool GROUPED, bool BAND = false>
-__device__ __forceinline__ void dq_body(const Params& x, const Item& it, int64_t window = 0) {
-  static_assert(kSupported<D, DROP, CAUSAL, GROUPED, BAND>, "no kernel of either family has this combination");
+template <typename T, int D, bool DROP, bool CAUSAL, bool GROUPED, bool BAND = false, bool SOFTCAP = false>
+__device__ __forceinline__ void dq_body(const Params& x, const Item& it, int64_t window = 0, float softcap = 0.f) {
+  static_assert(kSupported<D, DROP, CAUSAL, GROUPED, BAND, SOFTCAP>, "no kernel of either family has this combination");
   const AttnParams& p = x.a;
   constexpr int DS = D / NW, PITCH = Lds<T, D>::PITCH, DB = DS / 32;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_wide[];
@@ -294,7 +321,8 @@ __device__ __forceinline__ void dq_body(const Params& x, const Item& it, int64_t
   RowFrag<T, DS> qf, dof;
   qf.load(static_cast<const T*>(p.q) + (qbase + qr) * p.q_stride + hd * D + w * DS, q_ok, h);
   dof.load(static_cast<const T*>(p.dout) + (qbase + qr) * x.dout_stride + hd * D + w * DS, q_ok, h);
-  const float sl2 = p.scale * kLog2e;
+  const float sl2 = SOFTCAP ? kLog2e : p.scale * kLog2e;          // SOFTCAP: the capped scores carry the scale already
+  [[maybe_unused]] const float kcap = SOFTCAP ? p.scale / softcap : 0.f;
   float lse2 = q_ok ? p.lse[lse_base + q_row] * kLog2e : INFINITY;   // a row past the sequence: probability 0 everywhere
   if constexpr (BAND) {
     if (lse2 == -INFINITY) lse2 = INFINITY;                           // and a row that saw no key: never exp2(+inf)
@@ -329,6 +357,11 @@ __device__ __forceinline__ void dq_body(const Params& x, const Item& it, int64_t
 #pragma unroll
     for (int i = 0; i < 16; i += 2) {
       const int key = (int)kv0 + acc_row(i, h);                   // even; registers i, i+1 = keys key, key+1
+      [[maybe_unused]] float f0, f1;                              // SOFTCAP: 1 - tanh^2 of the pair
+      if constexpr (SOFTCAP) {
+        s[i] = softcap_z(s[i], kcap, softcap, f0);
+        s[i + 1] = softcap_z(s[i + 1], kcap, softcap, f1);
+      }
       float a0 = fmaf(s[i], sl2, -lse2), a1 = fmaf(s[i + 1], sl2, -lse2);
       if (!full) {                                                // a masked pair has P = exp2(-inf) = 0 whatever its score
         if constexpr (BAND) {
@@ -344,6 +377,10 @@ __device__ __forceinline__ void dq_body(const Params& x, const Item& it, int64_t
       if constexpr (DROP) drop_pair_q(dq_u + ((uint32_t)(t * (KT / 2)) + (uint32_t)(acc_row(i, 0) >> 1)) * kDropC2, q_odd, p.drop_thresh, p.keep_scale, m0, m1);
       s[i] = p0 * (dp[i] * m0 - dl);
       s[i + 1] = p1 * (dp[i + 1] * m1 - dl);
+      if constexpr (SOFTCAP) {
+        s[i] *= f0;
+        s[i + 1] *= f1;
+      }
     }
     mma_acc<DS>(ks + w * DS, PITCH, 0, s, dq, lane);
     __syncthreads();
@@ -370,9 +407,10 @@ __device__ __forceinline__ void query_range(int64_t l, int64_t kt, int64_t windo
 //   S = Q K^T and dP = dO V^T as sums of four partials, P = exp(scale * S - lse[q]), dV_w^T += dO_w^T P,
 //   dS = P * (dP - delta[q]), dK_w^T += Q_w^T dS  (key on the lane, the query in the accumulator registers)
 // The work item is decode()'s for the plain family and causal_key_tile()'s for the grouped one.
-template <typename T, int D, bool DROP, bool CAUSAL, bool GROUPED, bool BAND = false>
-__device__ __forceinline__ void dkv_body(const Params& x, const std::conditional_t<GROUPED, CausalKeyTile, Item>& it, int64_t window = 0) {
-  static_assert(kSupported<D, DROP, CAUSAL, GROUPED, BAND>, "no kernel of either family has this combination");
+template <typename T, int D, bool DROP, bool CAUSAL, bool GROUPED, bool BAND = false, bool SOFTCAP = false>
+__device__ __forceinline__ void dkv_body(const Params& x, const std::conditional_t<GROUPED, CausalKeyTile, Item>& it, int64_t window = 0,
+                                         float softcap = 0.f) {
+  static_assert(kSupported<D, DROP, CAUSAL, GROUPED, BAND, SOFTCAP>, "no kernel of either family has this combination");
   const AttnParams& p = x.a;
   constexpr int DS = D / NW, PITCH = Lds<T, D>::PITCH, DB = DS / 32, QT = KT;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_wide[];
@@ -404,7 +442,8 @@ __device__ __forceinline__ void dkv_body(const Params& x, const std::conditional
   const T* dog = static_cast<const T*>(p.dout) + qbase * x.dout_stride + kvh * D;
   const float* lse_g = p.lse + lse_base;
   const float* dl_g = p.delta + lse_base;
-  const float sl2 = p.scale * kLog2e;
+  const float sl2 = SOFTCAP ? kLog2e : p.scale * kLog2e;          // SOFTCAP: the capped scores carry the scale already
+  [[maybe_unused]] const float kcap = SOFTCAP ? p.scale / softcap : 0.f;
   const uint32_t dk_u = drop_base(attn_seed(p), lse_base) + (uint32_t)(key >> 1) * kDropC2 + (uint32_t)(2 * h) * kDropC1;
   const int k_odd = (int)(key & 1);
   f32x16 dk[DB], dv[DB];
@@ -468,9 +507,12 @@ __device__ __forceinline__ void dkv_body(const Params& x, const std::conditional
             const int i = 4 * g4 + j;
             bool on = key_ok && (!diag || (int)q0 + q4 + j >= ki);               // P = exp2(-inf) = 0 above the diagonal
             if constexpr (BAND) on = key_ok && (inside || band_sees<CAUSAL>((int)q0 + q4 + j, ki, wi));
+            [[maybe_unused]] float fac;                  // SOFTCAP: 1 - tanh^2
+            if constexpr (SOFTCAP) s[i] = softcap_z(s[i], kcap, softcap, fac);
             const float pr = fast_exp2(on ? fmaf(s[i], sl2, -lv[j]) : -INFINITY);
             s[i] = pr * mk[j];
             dp[i] = pr * (dp[i] * mk[j] - dv4[j]);
+            if constexpr (SOFTCAP) dp[i] *= fac;
           }
         }
         mma_acc<DS>(dos + w * DS, PITCH, 0, s, dv, lane);

@@ -44,13 +44,18 @@ def _layer_types(cfg):
     return list(getattr(cfg, "layer_types", None) or ["full_attention"] * cfg.num_hidden_layers)
 
 
+def _rope_type(sub) -> str:
+    """The rope type of one ``rope_parameters`` dict (absent or empty: default)."""
+    return (sub or {}).get("rope_type", (sub or {}).get("type", "default"))
+
+
 def _rope_types(cfg):
     """{layer type in use: its rope type}, read from ``rope_parameters[layer type]`` (absent: default)."""
     rp = getattr(cfg, "rope_parameters", None) or {}
     out = {}
     for lt in dict.fromkeys(_layer_types(cfg)):
         sub = rp.get(lt) if isinstance(rp, dict) else None
-        out[lt] = (sub or {}).get("rope_type", (sub or {}).get("type", "default"))
+        out[lt] = _rope_type(sub)
     return out
 
 
@@ -133,7 +138,7 @@ def rope_tables(plm, max_len: int, device) -> dict:
 
 
 class LayerWeights:
-    """Per-forward view of one Gemma3DecoderLayer: the GEMM operands in the compute dtype (fused ``wqkv`` [q|k|v] and ``wgu``
+    """Per-forward view of one Gemma3DecoderLayer (or Gemma2DecoderLayer: ``qn`` and ``kn`` None): the GEMM operands in the compute dtype (fused ``wqkv`` [q|k|v] and ``wgu``
     [gate|up], ``wo``, ``wdown``; no autograd history) next to the fp32 masters their gradients go to (``dense._mm``), the norm
     weights (``ln_next``: the next layer's input norm, or the model's final norm) and the layer type."""
     __slots__ = ("wqkv", "wo", "wgu", "wdown", "m_qkv", "m_wo", "m_gu", "m_down", "ln_post_attn", "ln_pre_ff", "ln_post_ff", "ln_next",
@@ -156,7 +161,8 @@ def prepare_weights(plm, cd, gemm_precision="native"):
         lw.ln_post_attn, lw.ln_pre_ff = layer.post_attention_layernorm.weight, layer.pre_feedforward_layernorm.weight
         lw.ln_post_ff = layer.post_feedforward_layernorm.weight
         lw.ln_next = plm.layers[i + 1].input_layernorm.weight if i + 1 < n else plm.norm.weight
-        lw.qn, lw.kn = sa.q_norm.weight, sa.k_norm.weight
+        # a Gemma2 layer (gemma2.py shares this function) has no Q / K head norm
+        lw.qn, lw.kn = (sa.q_norm.weight, sa.k_norm.weight) if hasattr(sa, "q_norm") else (None, None)
         lw.layer_type = types[i]
         out.append(lw)
     operands = encoder_operands(specs, cd, gemm_precision)

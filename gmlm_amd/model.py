@@ -20,7 +20,7 @@ import torch
 import torch.nn as nn
 from torch.utils.checkpoint import checkpoint
 
-from . import bert, deberta, eurobert, gemma3, llama, modernbert, mpnet, nomic_bert, ops, qwen3
+from . import bert, deberta, eurobert, gemma2, gemma3, llama, modernbert, mpnet, nomic_bert, ops, qwen3
 from .dense import SPLITK_ROW_QUANTUM, _linear, check_gemm_precision, linear_specs, shadow_params, use_shadow
 from .graph import GraphCache, RelCSR
 from .nn import CrossAttention, GraphNorm, MultiScaleFusion, RGCNConv, compute_dtype, cross_attention_specs
@@ -36,6 +36,7 @@ _ENCODERS = {"bert": (bert, "bert_encode", "bert_encode_packed"), "qwen3": (qwen
              "eurobert": (eurobert, "eurobert_encode", "eurobert_encode_packed"),
              "nomic_bert": (nomic_bert, "nomic_bert_encode", "nomic_bert_encode_packed"),
              "gemma3_text": (gemma3, "gemma3_encode", "gemma3_encode_packed"),
+             "gemma2": (gemma2, "gemma2_encode", "gemma2_encode_packed"),
              **{kind: (llama, "llama_encode", "llama_encode_packed") for kind in llama.MODEL_TYPES}}
 
 # encoder modules whose packed pass takes ``groups`` (ops.pack_sequence_groups): grouped-KV attention at head dim 64 on the
@@ -155,7 +156,7 @@ class GraphTextLM(nn.Module):
                 plm_tokenizer = AutoTokenizer.from_pretrained(model_name, trust_remote_code=True)
         # the encoder pass is picked by the PLM's model type: Qwen3 (gmlm_amd.qwen3), ModernBERT (gmlm_amd.modernbert), MPNet
         # (gmlm_amd.mpnet), DeBERTa-v2 / v3 (gmlm_amd.deberta), Llama / Qwen2 / Mistral (gmlm_amd.llama), EuroBERT
-        # (gmlm_amd.eurobert), NomicBERT (gmlm_amd.nomic_bert), Gemma3 text (gmlm_amd.gemma3), else BERT geometry (gmlm_amd.bert)
+        # (gmlm_amd.eurobert), NomicBERT (gmlm_amd.nomic_bert), Gemma3 text (gmlm_amd.gemma3), Gemma2 (gmlm_amd.gemma2), else BERT geometry (gmlm_amd.bert)
         model_type = getattr(plm_encoder.config, "model_type", None)
         self._plm_kind = model_type if model_type in _ENCODERS else "bert"
         self._enc.check_supported(plm_encoder)
@@ -243,8 +244,8 @@ class GraphTextLM(nn.Module):
         ModernBERT (``modernbert.modernbert_encode_packed``, head dim 64), MPNet (``mpnet.mpnet_encode_packed``, head dim 64),
         DeBERTa-v2 / v3 (``deberta.deberta_encode_packed``, head dim 64), Llama / Qwen2 / Mistral
         (``llama.llama_encode_packed``, head dim 64 or 128), EuroBERT (``eurobert.eurobert_encode_packed``, head dim 64 or 128)
-        NomicBERT (``nomic_bert.nomic_bert_encode_packed``, head dim 64) and Gemma3 text (``gemma3.gemma3_encode_packed``, head dim
-        256)."""
+        NomicBERT (``nomic_bert.nomic_bert_encode_packed``, head dim 64) Gemma3 text (``gemma3.gemma3_encode_packed``, head dim
+        256) and Gemma2 (``gemma2.gemma2_encode_packed``, head dim 256)."""
         return self._enc is not bert or self._packed_head_dim() in bert.NATIVE_HEAD_DIMS
 
     def graph(self, edge_index: torch.Tensor, num_nodes: int, edge_type=None) -> RelCSR:

@@ -1875,3 +1875,5 @@ def attention_disent_qkv_varlen(qkv, c2p, p2c, col, cu_seqlens, max_len, num_hea
 # ---------------------------------------------------------------------------------------------
 from .ops_gemma import gqa_d256_attention, gqa_d256_attention_varlen, rope_gqa_d256, rope_gqa_d256_varlen, sandwich_rmsnorm  # noqa: E402,F401
 from .ops_gemma import gqa_d256_band_attention, gqa_d256_band_attention_varlen  # noqa: E402,F401
+from .ops_softcap import gqa_d256_softcap_attention, gqa_d256_softcap_attention_varlen, rope_heads_d256_  # noqa: E402,F401
+from .ops_softcap import rope_softcap_gqa_d256, rope_softcap_gqa_d256_varlen  # noqa: E402,F401

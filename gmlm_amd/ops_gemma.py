@@ -6,6 +6,8 @@ tanh-GELU gated unit is ``ops.geglu_tanh`` (the ``_GLU`` node) and attention alo
 The band-limited (sliding-window) form of that attention (include/gmlm_hip_gqa_band.h, gmlm_attention_gqa_d256_band_*) has two
 nodes of its own here: ``BandAttention256`` (``ops.gqa_d256_band_attention`` / ``_varlen``) and ``RopeGQABand256``, which
 ``rope_gqa_d256`` / ``_varlen`` run when their ``window`` keyword is not 0.
+The soft-capped form (include/gmlm_hip_gqa_softcap.h) has its nodes in ops_softcap.py; ``_band_fwd`` / ``_band_bwd`` here make
+its calls when given a ``softcap``.
 
 Every node returns one gradient entry per input whatever is frozen, like the nodes of ops.py; their frozen-input tests are
 tests/test_gpu_gemma_rowops.py, tests/test_gpu_gqa_wide_kernels.py and tests/test_gqa_band_cpu.py
@@ -83,10 +85,13 @@ def gqa_d256_attention_varlen(q, k, v, cu_seqlens, max_len, hq, hkv, scale, caus
 # ---- the band-limited (sliding-window) form, include/gmlm_hip_gqa_band.h -------------------------------------------------------
 # visible(i, j) = j < kv_len and (0 <= i - j < window if causal else |i - j| < window): HF's exclusive window, window >= 1
 _BAND = "gmlm_attention_gqa_d256_band"
+_CAP = "gmlm_attention_gqa_d256_softcap"      # include/gmlm_hip_gqa_softcap.h: the same with ``softcap`` after ``window`` (0: no band)
 
 
-def _band_fwd(q, k, v, kv_len, cu, max_len, hq, hkv, scale, causal, window, want_lo):
-    """Padded ([b, l, .] with ``kv_len``) or, with ``cu`` (int32 [S + 1]), packed ([T, .]) -> (out, out_lo, lse)."""
+def _band_fwd(q, k, v, kv_len, cu, max_len, hq, hkv, scale, causal, window, want_lo, softcap=None):
+    """Padded ([b, l, .] with ``kv_len``) or, with ``cu`` (int32 [S + 1]), packed ([T, .]) -> (out, out_lo, lse).  ``softcap``
+    given: the soft-capped kernels, for which ``window`` may be 0."""
+    base, cap = (_CAP, (float(softcap),)) if softcap is not None else (_BAND, ())
     if cu is not None:
         t = q.shape[0]
         qs, ks, vs = _o._packed_stride(q, hq, D), _o._packed_stride(k, hkv, D), _o._packed_stride(v, hkv, D)
@@ -94,33 +99,34 @@ def _band_fwd(q, k, v, kv_len, cu, max_len, hq, hkv, scale, causal, window, want
             raise ValueError("packed q, k and v must have the same number of rows")
         out = torch.empty(t, hq * D, dtype=q.dtype, device=q.device)
         lse = torch.empty(hq, t, dtype=torch.float32, device=q.device)
-        head, name = (_o._ptr(cu), cu.numel() - 1, max_len, t), _BAND + "_varlen_fwd"
+        head, name = (_o._ptr(cu), cu.numel() - 1, max_len, t), base + "_varlen_fwd"
     else:
         b, l = q.shape[0], q.shape[1]
         qs, ks, vs = _o._rows_view(q, hq, D), _o._rows_view(k, hkv, D), _o._rows_view(v, hkv, D)
         out = torch.empty(b, l, hq * D, dtype=q.dtype, device=q.device)
         lse = torch.empty(b, hq, l, dtype=torch.float32, device=q.device)
-        head, name = (_o._ptr(kv_len), b), _BAND + "_fwd"
+        head, name = (_o._ptr(kv_len), b), base + "_fwd"
     out_lo = torch.empty_like(out) if want_lo else None
     mid = () if cu is not None else (l, k.shape[1])
     check(getattr(lib(), name)(_o._ptr(q), _o._ptr(k), _o._ptr(v), *head, hq, hkv, *mid, D, qs, ks, vs, float(scale), 0.0, 1 if causal else 0,
-                               int(window), _o._ptr(out), _o._ptr(out_lo), _o._ptr(lse), _o._dt(q), _o._stream()), name)
+                               int(window), *cap, _o._ptr(out), _o._ptr(out_lo), _o._ptr(lse), _o._dt(q), _o._stream()), name)
     return out, out_lo, lse
 
 
-def _band_bwd(q, k, v, out, out_lo, gout, lse, kv_len, cu, max_len, hq, hkv, scale, causal, window, dq, dk, dv):
+def _band_bwd(q, k, v, out, out_lo, gout, lse, kv_len, cu, max_len, hq, hkv, scale, causal, window, dq, dk, dv, softcap=None):
+    base, cap = (_CAP, (float(softcap),)) if softcap is not None else (_BAND, ())
     gout = gout.contiguous().to(q.dtype)
     if cu is not None:
         t = q.shape[0]
-        ws = _o._ws(getattr(lib(), _BAND + "_varlen_bwd_workspace_bytes")(t, hq), q.device)
-        head, mid, name, r = (_o._ptr(cu), cu.numel() - 1, max_len, t), (), _BAND + "_varlen_bwd", 0
+        ws = _o._ws(getattr(lib(), base + "_varlen_bwd_workspace_bytes")(t, hq), q.device)
+        head, mid, name, r = (_o._ptr(cu), cu.numel() - 1, max_len, t), (), base + "_varlen_bwd", 0
     else:
         b, l = q.shape[0], q.shape[1]
-        ws = _o._ws(getattr(lib(), _BAND + "_bwd_workspace_bytes")(b, hq, l), q.device)
-        head, mid, name, r = (_o._ptr(kv_len), b), (l, k.shape[1]), _BAND + "_bwd", 1
+        ws = _o._ws(getattr(lib(), base + "_bwd_workspace_bytes")(b, hq, l), q.device)
+        head, mid, name, r = (_o._ptr(kv_len), b), (l, k.shape[1]), base + "_bwd", 1
     check(getattr(lib(), name)(_o._ptr(q), _o._ptr(k), _o._ptr(v), _o._ptr(out), _o._ptr(out_lo), _o._ptr(gout), _o._ptr(lse), *head, hq, hkv,
                                *mid, D, q.stride(r), k.stride(r), v.stride(r), float(scale), 0.0, 1 if causal else 0, int(window),
-                               _o._ptr(dq), _o._ptr(dk), _o._ptr(dv), dq.stride(r), dk.stride(r), dv.stride(r), _o._dt(q), _o._ptr(ws),
+                               *cap, _o._ptr(dq), _o._ptr(dk), _o._ptr(dv), dq.stride(r), dk.stride(r), dv.stride(r), _o._dt(q), _o._ptr(ws),
                                ws.numel(), _o._stream()), name)
 
 
